@@ -12,9 +12,15 @@ parallelism is one video per worker, find_motion.py:1071-1075).  RCCL is used
 only for the timing barrier and the max-over-ranks reduction.
 
 Prints ONE JSON line on rank 0 (driver contract), with a "roofline" object
-for the dominant kernel (HIP-event timing inside the library, on the stream
-the kernels run on) and a "cpu_baseline" object (the C restatement in
-oracle/, OpenMP, one thread per stream, rank 0 at N=1 only).
+for the dominant kernel (in-kernel stamps of the timed steps' own launches).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+results if --dump-outputs DIR is given, and prints the line.  --full adds the
+figures that take runs of their own (1-GPU run only): the measured device copy
+peak, "host_fed_per_gpu", "mjpeg_fed_per_gpu", the "side_configs" (mode D,
+configs[2], configs[4] with and without Haar, one child process each) and
+"cpu_baseline" (the C restatement in oracle/, OpenMP, one thread per stream);
+without it those keys are null.
 """
 from __future__ import annotations
 
@@ -617,6 +623,67 @@ def rank_devices(local: int, pl, active: bool) -> list:
     return dist.gather_to_root(me, pl, active) or []
 
 
+def copy_peak_gbs(local: int) -> float:
+    """GB/s (read + write) of ten 256 MiB device-to-device copies, timed by HIP events."""
+    import torch
+
+    a = torch.empty(1 << 28, dtype=torch.uint8, device=f"cuda:{local}")
+    b = torch.empty_like(a)
+    for _ in range(3):
+        b.copy_(a)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(10):
+        b.copy_(a)
+    e1.record()
+    torch.cuda.synchronize()
+    return 10 * 2 * a.numel() / (e0.elapsed_time(e1) / 1e3) / 1e9
+
+
+DUMP_SEED = 20240607
+# bytes of .npy data --dump-outputs writes at most per array: 59 MiB in all, inside 64 MB
+DUMP_BUDGET = {"counts": 1 << 20, "contours": 4 << 20, "background": 26 << 20, "mask_frames": 1 << 10, "masks": 28 << 20}
+DUMP_MASKS = 3  # (t, s) pairs whose masks are written (1080p: 3 x 2 MPx as f32 = 24.9 MB)
+
+
+def _bounded(name: str, a: np.ndarray, dtype) -> np.ndarray:
+    """`a` as `dtype`, whole if it fits in DUMP_BUDGET[name] bytes, else a sample of its elements (flat, in
+    index order) drawn from a generator seeded by the array's size: the same elements on every run."""
+    n = DUMP_BUDGET[name] // np.dtype(dtype).itemsize
+    if a.size <= n:
+        return np.ascontiguousarray(a, dtype=dtype)
+    rng = np.random.default_rng([DUMP_SEED, a.size])
+    idx = np.sort(rng.choice(a.size, size=n, replace=False))
+    return a.reshape(-1)[idx].astype(dtype)
+
+
+def dump_outputs(eng, outdir: str, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs: what a caller of the timed path reads after its last step (the last waited batch):
+    counts [T][S], every contour's row (t, s, x, y, w, h, origin_x, origin_y), each stream's background
+    model [S][h][w] (f64) and the dilated threshold masks of a fixed seeded choice of (t, s) pairs (listed
+    in mask_frames).  float64 / float32 .npy files; an array over its budget is written as a seeded sample
+    of its elements.  Returns {name: shape}."""
+    os.makedirs(outdir, exist_ok=True)
+    counts = eng.counts()
+    T, S = counts.shape
+    rows = [(t, s, c.x, c.y, c.w, c.h, c.origin[0], c.origin[1])
+            for t in range(T) for s in range(S) if counts[t, s] for c in eng.contours(t, s)]
+    rng = np.random.default_rng([DUMP_SEED, T, S])
+    picks = sorted(map(int, rng.choice(T * S, size=min(DUMP_MASKS, T * S), replace=False)))
+    arrays = {
+        "counts": _bounded("counts", counts, np.float64),
+        "contours": _bounded("contours", np.asarray(rows, np.float64).reshape(-1, 8), np.float64),
+        "background": _bounded("background", np.stack([eng.background(s) for s in range(S)]), np.float64),
+        "mask_frames": np.asarray([(i // S, i % S) for i in picks], np.float64),
+        "masks": _bounded("masks", np.stack([eng.mask(i // S, i % S) for i in picks]), np.float32),
+    }
+    sfx = "" if world == 1 else f".rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{sfx}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--gpus", type=int, default=1)
@@ -637,12 +704,18 @@ def main() -> None:
     ap.add_argument("--ring", type=int, default=256, help="device-resident frames per stream")
     ap.add_argument("--ring-period", type=int, default=64,
                     help="synthetic frames in the ring's cycle: ring slot t holds frame t %% period")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (1-GPU run): device copy peak, host-fed and "
+                         "MJPEG-fed pipelines, the side configurations (child processes) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (counts, contours, background, a "
+                         "seeded choice of masks) as DIR/<name>.npy; the inputs are the same on every run")
     ap.add_argument("--cpu-frames", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--host-fed", action="store_true", help="also time PCIe-fed submits (stderr only)")
-    ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed decode-ahead pipeline figure")
+    ap.add_argument("--no-host-fed", action="store_true", help="--full: skip the host-fed decode-ahead pipeline figure")
     ap.add_argument("--no-ktimes", action="store_true", help="no HIP event timing at all (no roofline)")
-    ap.add_argument("--no-mjpeg", action="store_true", help="skip the MJPEG-fed (GPU decode) figure")
+    ap.add_argument("--no-mjpeg", action="store_true", help="--full: skip the MJPEG-fed (GPU decode) figure")
     ap.add_argument("--masks", action="store_true",
                     help="configs[4]'s polygon masks on every stream: a rectangle and a triangle in 3840x2160 frame "
                          "coordinates, given in the MASK_SCHEMA form (find_motion.py:86-100), the polygons of the "
@@ -651,7 +724,7 @@ def main() -> None:
                     help="configs[4]: run the reference's frontalface_default cascade on every 15th written frame "
                          "of each stream (find_objects, fm.py:549-575, 703-731) inside the timed steps")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the mode D and configs[2] figures the default (1-GPU, configs[1]) line carries")
+                    help="--full: skip the mode D, configs[2] and configs[4] figures of the 1-GPU configs[1] line")
     ap.add_argument("--side-leg", choices=sorted(SIDE_LEGS), default=None,
                     help="(internal) run one side leg of the default line and print its JSON object")
     ap.add_argument("--all-ktimes", action="store_true",
@@ -689,25 +762,16 @@ def main() -> None:
     value, roof, kernels, haar, det = leg["value"], leg["roofline"], leg["kernels"], leg["haar"], leg["det"]
     footprint, ccl, depth = leg["footprint"], leg["ccl"], eng.max_inflight
 
-    # measured device copy peak (for reference beside the spec)
-    try:
-        a = torch.empty(1 << 28, dtype=torch.uint8, device=f"cuda:{local}")
-        b = torch.empty_like(a)
-        for _ in range(3):
-            b.copy_(a)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            b.copy_(a)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbs = 10 * 2 * a.numel() / (e0.elapsed_time(e1) / 1e3) / 1e9
-        if roof is not None:
-            roof["copy_peak_measured"] = round(copy_gbs, 1)
-        del a, b
-    except Exception:
-        pass
+    dumped = None
+    if args.dump_outputs:  # the last timed step's results, before anything else is submitted to the engine
+        dumped = dump_outputs(eng, args.dump_outputs, rank, world)
+
+    # measured device copy peak (for reference beside the spec): a run of its own, so --full only
+    if args.full and roof is not None:
+        try:
+            roof["copy_peak_measured"] = round(copy_peak_gbs(local), 1)
+        except Exception:
+            pass
 
     if args.host_fed:
         # PCIe-inclusive rates (never `value`): pageable numpy batches, then page-locked
@@ -749,7 +813,7 @@ def main() -> None:
     host_fed = None
     # per-GPU figure, measured in the 1-GPU run only: every rank would page-lock (depth + 2) batches of
     # T frames (≈21 GB at 10 slots x 256 frames of 1080p), ≈170 GB of pinned host memory on an 8-GPU node
-    if not args.no_host_fed and world == 1:
+    if args.full and not args.no_host_fed and world == 1:
         from find_motion_amd import videoio
         from find_motion_amd.feeder import BatchFeeder
 
@@ -781,7 +845,7 @@ def main() -> None:
     # the host, copied to the GPU, decoded there (fm_submit_jpeg) in front of the hot path.  Beside
     # `value`, never as it; libjpeg-turbo (Pillow) on one host core is the CPU decode rate it replaces.
     mjpeg = None
-    if not args.no_mjpeg and world == 1:  # a per-GPU figure: measured in the 1-GPU run only
+    if args.full and not args.no_mjpeg and world == 1:  # a per-GPU figure: measured in the 1-GPU run only
         mjpeg = mjpeg_fed(eng, host, T, S)
 
     eng.close()
@@ -796,11 +860,11 @@ def main() -> None:
     # 67 k in a fresh process (round 6, profiles/r06/r06c*_default_bench.log)
     side = None
     default_shape = args.mode == "F" and S == 1 and (W, H) == (1920, 1080) and not args.haar
-    if world == 1 and default_shape and not args.no_side:
+    if args.full and world == 1 and default_shape and not args.no_side:
         side = {name: side_child(name, args) for name in SIDE_LEGS}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, host.reshape(P * S, H, W, 3), min(args.cpu_frames, P * S))
 
     if rank == 0:
@@ -823,7 +887,9 @@ def main() -> None:
                "contour_pass": {"heavy_tiles_per_batch": round(ccl["heavy_tiles"] / max(ccl["batches"], 1), 2),
                                 "shared_nodes_max": ccl["shared_nodes_max"],
                                 "fallback_frames": ccl["fallback_frames"]},
-               "host_us_per_step": leg["host_us_per_step"]}
+               "host_us_per_step": leg["host_us_per_step"], "full": bool(args.full)}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(out), flush=True)
     dist.finalize(active)
 

@@ -38,6 +38,16 @@ def contour_cases():
             for n in names}
 
 
+def cascade_xml(name):
+    """The XML text of tests/golden/haarcascades/haarcascade_<name>.xml.gz: the cascade data files the
+    reference loads (CASCADE_LOOKUP, find_motion.py:104-122) and its one haartraining-format file, gzipped
+    as they are (OpenCV's files, licence text included)."""
+    import gzip
+
+    with gzip.open(os.path.join(GOLDEN, "haarcascades", f"haarcascade_{name}.xml.gz"), "rt", encoding="utf-8") as fh:
+        return fh.read()
+
+
 def load_frontalface():
     """(Cascade, fixture dict) of tests/golden/cascade_frontalface_default.npz (make_golden_cascade.py)."""
     from find_motion_amd.cascade import Cascade

@@ -115,6 +115,51 @@ def test_default_line_legs_have_committed_pmc_traffic(bench):
         assert os.path.exists(os.path.join(ROOT, src)), src
 
 
+@pytest.fixture(scope="module")
+def waited_engine(oracle_lib):
+    """The oracle-backed engine (tests/fake_engine.py) after one waited batch of 5 frames x 2 streams."""
+    from fake_engine import OracleEngine
+    from find_motion_amd import make_gaussian
+    from find_motion_amd.synthetic import batch
+    eng = OracleEngine(n_streams=2, src_w=64, src_h=48, box_size=64, ksize=make_gaussian(64, 13), threshold=12,
+                       avg=0.1, max_batch=5)
+    eng.submit(batch(64, 48, 2, 0, 5))
+    eng.wait()
+    return eng
+
+
+def test_dump_outputs_writes_the_last_steps_results(bench, waited_engine, tmp_path):
+    """--dump-outputs: counts, contour rows, backgrounds and a seeded choice of masks as float .npy files, the
+    same files on every call."""
+    import numpy as np
+    eng = waited_engine
+    shapes = bench.dump_outputs(eng, str(tmp_path / "a"))
+    bench.dump_outputs(eng, str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{n}.npy" for n in shapes) and len(shapes) == 5
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    for n, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and list(a.shape) == shapes[n]
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert np.array_equal(got["counts"], eng.counts()) and eng.counts().sum() > 0
+    assert np.array_equal(got["background"], np.stack([eng.background(0), eng.background(1)]))
+    want = [(t, s, c.x, c.y, c.w, c.h, *c.origin) for t in range(5) for s in range(2) for c in eng.contours(t, s)]
+    assert got["contours"].tolist() == [list(map(float, r)) for r in want]
+    assert len(got["mask_frames"]) == bench.DUMP_MASKS == len({tuple(r) for r in got["mask_frames"]})
+    for k, (t, s) in enumerate(got["mask_frames"].astype(int)):
+        assert np.array_equal(got["masks"][k], eng.mask(t, s))
+
+
+def test_dump_outputs_samples_an_array_over_its_budget(bench, waited_engine, tmp_path, monkeypatch):
+    import numpy as np
+    assert sum(bench.DUMP_BUDGET.values()) <= 64_000_000
+    monkeypatch.setitem(bench.DUMP_BUDGET, "background", 8 * 100)
+    shapes = bench.dump_outputs(waited_engine, str(tmp_path))
+    bg = np.load(tmp_path / "background.npy")
+    assert shapes["background"] == [100] and np.isin(bg, waited_engine.background(0)).sum() >= 50
+    bench.dump_outputs(waited_engine, str(tmp_path / "again"))
+    assert np.array_equal(bg, np.load(tmp_path / "again" / "background.npy"))
+
+
 def test_side_legs_run_in_child_processes(bench, monkeypatch):
     """bench.py runs each side leg as `bench.py --side-leg NAME` in a process of its own and takes its last JSON
     line; a failed child gives an error entry, not a crash of the default line."""

@@ -15,34 +15,30 @@ import pytest
 
 from find_motion_amd import _native
 from find_motion_amd.cascade import CASCADE_LOOKUP, THRESHOLD_EPS, parse, to_xml
+from golden_cases import cascade_xml
 from haar_cases import make_cascade, make_image
 from oracle import haar
 
-REF_CASCADES = "/root/reference/find_motion/haarcascades"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_CASCADES), reason="reference cascades not present")
 def test_reference_cascades_parse():
-    # every cascade the reference can load (CASCADE_LOOKUP, find_motion.py:104-122) reads into
-    # consistent arrays
+    # every cascade the reference can load (CASCADE_LOOKUP, find_motion.py:104-122; the files are
+    # fixtures, tests/golden/haarcascades) reads into consistent arrays
     for name in CASCADE_LOOKUP:
-        cs = parse(os.path.join(REF_CASCADES, f"haarcascade_{name}.xml"))
+        cs = parse(cascade_xml(name))
         assert cs.n_stages > 0 and cs.stage_ntrees.sum() == len(cs.tree_nodes)
         assert cs.tree_nodes.sum() == len(cs.node_left) == len(cs.node_threshold)
         assert len(cs.leaves) == len(cs.tree_nodes) + len(cs.node_left)
         assert cs.node_feature.max() < len(cs.feat_tilted)
         assert cs.has_tilted == (name in ("frontalcatface_extended", "fullbody", "lowerbody")), name
-    d = parse(os.path.join(REF_CASCADES, "haarcascade_frontalface_default.xml"))
+    d = parse(cascade_xml("frontalface_default"))
     assert (d.win_w, d.win_h, d.n_stages) == (24, 24, 25)
     assert d.stage_threshold[0] == np.float32(np.float32(-5.0425500869750977) - THRESHOLD_EPS)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CASCADES), reason="reference cascades not present")
 def test_reference_old_format_cascade():
     # haarcascade_licence_plate_rus_16stages.xml (haartraining's format, commented out of
     # CASCADE_LOOKUP): 64x16 window, 16 stages of stumps, values as CascadeClassifier::convert
     # writes them; its first stage and first tree as the file states them
-    cs = parse(os.path.join(REF_CASCADES, "haarcascade_licence_plate_rus_16stages.xml"))
+    cs = parse(cascade_xml("licence_plate_rus_16stages"))
     assert (cs.win_w, cs.win_h, cs.n_stages, len(cs.tree_nodes)) == (64, 16, 16, 91)
     assert (cs.tree_nodes == 1).all() and len(cs.leaves) == 2 * 91 and not cs.has_tilted
     assert (cs.node_left == 0).all() and (cs.node_right == -1).all()
@@ -56,12 +52,11 @@ def test_reference_old_format_cascade():
     assert rc in (_native.FM_OK, _native.FM_EHIP), msg
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CASCADES), reason="reference cascades not present")
 def test_reference_cascades_pass_the_abi_validation():
-    # fm_haar_create validates before touching the device: on this CPU-only host a valid
+    # fm_haar_create validates before touching the device: on a CPU-only host a valid
     # description fails only at the first HIP call (FM_EHIP), never with FM_EINVAL
     for name in CASCADE_LOOKUP:
-        cs = parse(os.path.join(REF_CASCADES, f"haarcascade_{name}.xml"))
+        cs = parse(cascade_xml(name))
         rc, msg = _create(cs)
         assert rc in (_native.FM_OK, _native.FM_EHIP), (name, msg)
 
@@ -117,17 +112,15 @@ def test_xml_round_trip(kw):
 
 
 def test_old_format_fixture():
-    # the committed arrays are the reference file's (when it is here) and the restatement's
-    # candidates on the plate images are the fixture's
+    # the committed arrays are the reference file's and the restatement's candidates on the
+    # plate images are the fixture's
     from golden_cases import load_licence_plate_old
     from haar_cases import plate_image
 
     cs, cases = load_licence_plate_old()
-    path = os.path.join(REF_CASCADES, "haarcascade_licence_plate_rus_16stages.xml")
-    if os.path.isfile(path):
-        ref = parse(path)
-        for f in cs.__dataclass_fields__:
-            assert np.array_equal(getattr(cs, f), getattr(ref, f)), f
+    ref = parse(cascade_xml("licence_plate_rus_16stages"))
+    for f in cs.__dataclass_fields__:
+        assert np.array_equal(getattr(cs, f), getattr(ref, f)), f
     for seed, cand, dets in cases[:2]:
         got = haar.detect_candidates(cs, plate_image(seed), 1.1)
         assert [tuple(r) for r in got] == cand and haar.group_rectangles(got, 5) == dets
@@ -361,16 +354,12 @@ def test_golden_fixtures_present():
 
 # --- the reference's own cascade (tests/golden/cascade_frontalface_default.npz) --------------
 
-REF_XML = "/root/reference/find_motion/haarcascades/haarcascade_frontalface_default.xml"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason="reference tree not mounted (GPU box)")
 def test_frontalface_fixture_is_the_reference_cascade():
     """The fixture's arrays are find_motion_amd.cascade.parse of the reference's XML (config 5's cascade)."""
     from golden_cases import load_frontalface
 
     cs, _ = load_frontalface()
-    ref = parse(REF_XML)
+    ref = parse(cascade_xml("frontalface_default"))
     assert (cs.win_w, cs.win_h) == (ref.win_w, ref.win_h) == (24, 24) and cs.n_stages == 25
     for f in ("stage_ntrees", "stage_threshold", "tree_nodes", "node_left", "node_right", "node_feature",
               "node_threshold", "leaves", "feat_rects", "feat_weights", "feat_tilted"):

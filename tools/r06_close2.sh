@@ -21,9 +21,11 @@ for w in "$@"; do
     c4h) run c4h $C4 --haar ;;
     c4m) run c4m $C4 --masks ;;
     default)
-      timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_${TAG}_default.log 2>&1 || { tail -20 gpurun_out/bench_${TAG}_default.log; exit 1; }
-      python3 - "$TAG" <<'PY'
-import json, sys; d=json.loads(open(f'gpurun_out/bench_{sys.argv[1]}_default.log').read().strip().splitlines()[-1]); r=d['roofline']
+      OUT=${OUT:-bench_logs}  # where the --full line is kept
+      mkdir -p "$OUT"
+      timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_${TAG}_default.log" 2>&1 || { tail -20 "$OUT/bench_${TAG}_default.log"; exit 1; }
+      python3 - "$TAG" "$OUT" <<'PY'
+import json, sys; d=json.loads(open(f'{sys.argv[2]}/bench_{sys.argv[1]}_default.log').read().strip().splitlines()[-1]); r=d['roofline']
 print('F', round(d['value']), d['ms_per_step'], r['avg_launch_us'], r.get('launch_std_us'), r['frac'], r['traffic'])
 for k, v in d['side_configs'].items(): print(k, round(v['value']), v['ms_per_step'], v['roofline']['avg_launch_us'], v['roofline'].get('launch_std_us'), v['roofline']['frac'], v['roofline'].get('traffic'), (v.get('haar_stage') or {}).get('share_of_step_time'))
 PY
