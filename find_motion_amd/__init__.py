@@ -34,6 +34,7 @@ from ._native import (  # noqa: F401
     Contour,
     FMError,
     MJpegDecoder,
+    MJpegEncoder,
     MotionEngine,
     NativeLibraryMissing,
     rasterize_masks,

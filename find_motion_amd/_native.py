@@ -33,6 +33,8 @@ EXPORTED = (
     "fm_submit_jpeg", "fm_read_frame", "fm_mjpeg_tune", "fm_frame_device", "fm_mjpeg_geometry",
     "fm_submit_streams", "fm_footprint", "fm_haar_detect_frame_list", "fm_haar_detect_frame_list_async",
     "fm_haar_collect",
+    "fm_jpeg_header", "fm_mjpeg_enc_create", "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_encode",
+    "fm_mjpeg_encode_frame_list", "fm_mjpeg_enc_get", "fm_mjpeg_enc_coefficients", "fm_mjpeg_enc_last_ms",
 )
 
 
@@ -139,9 +141,22 @@ def load() -> C.CDLL:
     L.fm_mjpeg_tune.argtypes = [vp, i32, i32]
     L.fm_mjpeg_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.fm_submit_streams.argtypes = [vp, vp, i32, i32]
+    L.fm_jpeg_header.argtypes = [i32, i32, i32, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.fm_mjpeg_enc_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.fm_mjpeg_enc_destroy.argtypes = [vp]
+    L.fm_mjpeg_enc_destroy.restype = None
+    L.fm_mjpeg_enc_last_error.argtypes = [vp]
+    L.fm_mjpeg_enc_last_error.restype = C.c_char_p
+    L.fm_mjpeg_encode.argtypes = [vp, vp, i32, i32]
+    L.fm_mjpeg_encode_frame_list.argtypes = [vp, vp, i32]
+    L.fm_mjpeg_enc_get.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.fm_mjpeg_enc_coefficients.argtypes = [vp, i32, vp, C.c_size_t]
+    L.fm_mjpeg_enc_last_ms.argtypes = [vp]
+    L.fm_mjpeg_enc_last_ms.restype = C.c_double
     for name in EXPORTED:
         if name not in ("fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
-                        "fm_haar_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms"):
+                        "fm_haar_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
+                        "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_enc_last_ms"):
             getattr(L, name).restype = i32
     _lib = L
     return L
@@ -675,6 +690,121 @@ class MJpegDecoder:
     def close(self):
         if self._h:
             load().fm_mjpeg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def jpeg_header(width: int, height: int, quality: int = 95, subsampling: int = 2, restart_interval: int = 0) -> bytes:
+    """The bytes from SOI through the SOS segment of the JPEGs MJpegEncoder writes (fm_jpeg_header; host only)."""
+    L = load()
+    n = C.c_size_t()
+    args = (int(width), int(height), int(quality), int(subsampling), int(restart_interval))
+    L.fm_jpeg_header(*args, None, 0, C.byref(n))
+    buf = np.empty(max(n.value, 1), np.uint8)
+    rc = L.fm_jpeg_header(*args, _ptr(buf), buf.size, C.byref(n))
+    if rc != FM_OK:
+        raise FMError(rc, f"fm_jpeg_header: bad settings {args}")
+    return buf[:n.value].tobytes()
+
+
+class MJpegEncoder:
+    """The write side on the GPU: BGR u8 frames -> baseline JPEGs, byte for byte what Pillow's libjpeg-turbo
+    writes for Image.save(..., "JPEG", quality=quality, subsampling=subsampling[, restart_marker_blocks=
+    restart_interval]) -- the bytes videoio.MjpegAviWriter writes on the host (fm.py:447-546 with codec 'MJPG').
+    subsampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0; restart_interval in MCUs, 0 = none."""
+
+    def __init__(self, width: int, height: int, max_frames: int = 64, device: int = 0, quality: int = 95,
+                 subsampling: int = 2, restart_interval: int = 0):
+        L = load()
+        h = C.c_void_p()
+        rc = L.fm_mjpeg_enc_create(int(device), int(width), int(height), int(max_frames), int(quality),
+                                   int(subsampling), int(restart_interval), C.byref(h))
+        self._h = h
+        if rc != FM_OK:
+            msg = L.fm_mjpeg_enc_last_error(h).decode() if h else ""
+            L.fm_mjpeg_enc_destroy(h)
+            self._h = None
+            raise FMError(rc, f"fm_mjpeg_enc_create: {msg}")
+        self.width, self.height, self.max_frames, self.device = int(width), int(height), int(max_frames), int(device)
+        self.quality, self.subsampling, self.restart_interval = int(quality), int(subsampling), int(restart_interval)
+        hs, vs = (1, 1) if subsampling == 0 else (2, 1) if subsampling == 1 else (2, 2)
+        self.blocks = -(-self.width // (8 * hs)) * -(-self.height // (8 * vs)) * (hs * vs + 2)
+
+    def _fail(self, rc: int, what: str):
+        raise FMError(rc, f"{what}: {load().fm_mjpeg_enc_last_error(self._h).decode()}")
+
+    def _collect(self, n: int) -> list:
+        L = load()
+        out = []
+        ln = C.c_size_t()
+        for i in range(n):
+            L.fm_mjpeg_enc_get(self._h, i, None, 0, C.byref(ln))  # the size
+            buf = np.empty(max(ln.value, 1), np.uint8)
+            rc = L.fm_mjpeg_enc_get(self._h, i, _ptr(buf), buf.size, C.byref(ln))
+            if rc != FM_OK:
+                self._fail(rc, "fm_mjpeg_enc_get")
+            out.append(buf[:ln.value].tobytes())
+        return out
+
+    def encode(self, frames) -> list:
+        """Host frames [n, H, W, 3] (or one [H, W, 3]) BGR u8 -> list of JPEG byte strings."""
+        f = np.ascontiguousarray(frames, dtype=np.uint8)
+        if f.ndim == 3:
+            f = f[None]
+        if f.ndim != 4 or f.shape[1:] != (self.height, self.width, 3):
+            raise FMError(FM_EINVAL, f"frames of shape {f.shape}, the encoder takes [n, {self.height}, {self.width}, 3]")
+        rc = load().fm_mjpeg_encode(self._h, _ptr(f), f.shape[0], 0)
+        if rc != FM_OK:
+            self._fail(rc, "fm_mjpeg_encode")
+        return self._collect(f.shape[0])
+
+    def encode_device(self, ptrs_or_ptr, n: int | None = None) -> list:
+        """Frames already in device memory: one address of n contiguous frames [n, H, W, 3] (an int, or a
+        contiguous uint8 torch tensor on the encoder's GPU), or a sequence of addresses of single frames
+        (e.g. MotionEngine.frame_device_ptr).  The frames must be complete on the device."""
+        L = load()
+        src = ptrs_or_ptr
+        if getattr(src, "is_cuda", False):
+            import torch
+            if src.dtype != torch.uint8 or not src.is_contiguous() or tuple(src.shape[-3:]) != (self.height, self.width, 3):
+                raise FMError(FM_EINVAL, f"device frames must be a contiguous uint8 tensor [n, {self.height}, {self.width}, 3]")
+            torch.cuda.current_stream(src.device).synchronize()
+            n = 1 if src.dim() == 3 else int(src.shape[0])
+            rc = L.fm_mjpeg_encode(self._h, C.c_void_p(src.data_ptr()), n, 1)
+        elif isinstance(src, (int, np.integer)):
+            if n is None:
+                raise ValueError("n is required with a single device address")
+            rc = L.fm_mjpeg_encode(self._h, C.c_void_p(int(src)), int(n), 1)
+        else:
+            ptrs = [int(p) for p in src]
+            n = len(ptrs) if n is None else int(n)
+            if n > len(ptrs):
+                raise ValueError(f"{len(ptrs)} addresses for n = {n}")
+            arr = (C.c_void_p * max(n, 1))(*ptrs[:n])
+            rc = L.fm_mjpeg_encode_frame_list(self._h, C.cast(arr, C.c_void_p), n)
+        if rc != FM_OK:
+            self._fail(rc, "fm_mjpeg_encode")
+        return self._collect(int(n))
+
+    def coefficients(self, i: int) -> np.ndarray:
+        """Quantized coefficients of frame i of the last call: int16 [blocks, 64], scan order, zigzag."""
+        out = np.empty((self.blocks, 64), np.int16)
+        rc = load().fm_mjpeg_enc_coefficients(self._h, int(i), _ptr(out), out.size)
+        if rc < 0:
+            self._fail(rc, "fm_mjpeg_enc_coefficients")
+        return out
+
+    def last_ms(self) -> float:
+        return float(load().fm_mjpeg_enc_last_ms(self._h))
+
+    def close(self):
+        if self._h:
+            load().fm_mjpeg_enc_destroy(self._h)
             self._h = None
 
     def __del__(self):

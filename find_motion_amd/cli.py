@@ -2,6 +2,7 @@
 
     python -m find_motion_amd [files] -i DIR -o DIR -c cfg.ini -B 100 -b 20 -t 12 -a 0.1 ...
                               [--gpus N] [--device D] [--batch T] [--group] [--gpu-decode]
+                              [--gpu-encode]
 
 Everything the reference's `run` does around the hot path is kept in its
 shape (INI overriding the CLI, masks from literals and a JSON file, mtime
@@ -78,6 +79,9 @@ def get_args(parser: ArgumentParser) -> None:
                         help="Batch same-sized videos of a GPU's shard into one launch (StreamGroup)")
     parser.add_argument("--gpu-decode", action="store_true", default=None,
                         help="Decode MJPEG AVIs on the GPU (libjpeg-turbo-exact) even when OpenCV is present")
+    parser.add_argument("--gpu-encode", action="store_true", default=None,
+                        help="Encode MJPG output on the GPU (libjpeg-turbo-exact baseline JPEG, quality 95, 4:2:0) "
+                             "instead of cv2.VideoWriter / the host writer")
 
 
 def process_config(config_file: str, args: Namespace) -> Namespace:
@@ -92,7 +96,7 @@ def process_config(config_file: str, args: Namespace) -> Namespace:
         if setting in ("mintime", "cachetime", "avg"):
             use_value = float(value)
         if setting in ("mem", "progress", "debug", "show", "ignore_progress", "ignore_drive", "yolo_tiny", "group",
-                       "gpu_decode"):
+                       "gpu_decode", "gpu_encode"):
             if value not in ("True", "False"):
                 raise ValueError("{} must be True or False".format(setting))
             use_value = value == "True"
@@ -204,7 +208,8 @@ def _job_kwargs(args) -> dict:
                 blur_scale=args.blur_scale, box_size=args.box_size, min_box_scale=args.min_box_scale,
                 threshold=args.threshold, avg=args.avg, fps=args.fps, min_time=args.mintime,
                 cache_time=args.cachetime, multiprocess=args.processes > 1, cascades=args.cascade_object,
-                yolo_tiny=args.yolo_tiny, gpu_decode=getattr(args, "gpu_decode", None))
+                yolo_tiny=args.yolo_tiny, gpu_decode=getattr(args, "gpu_decode", None),
+                gpu_encode=getattr(args, "gpu_encode", None))
 
 
 def run_shard(files: list, kwargs: dict, device: int, batch: int, group: bool) -> list:

@@ -34,11 +34,19 @@ cascade on), and an MJPG output receives the source's JPEG bytes unchanged
 instead of a re-encode.  That decode equals libjpeg-turbo's (cv2.imdecode),
 not FFmpeg's (cv2.VideoCapture's default backend): see videoio.
 
+Writer: cv2.VideoWriter whenever OpenCV imports (fm.py:447-475).  With
+gpu_encode=True and codec 'MJPG' the motion frames of any other source are
+encoded to baseline JPEG on the GPU (videoio.MjpegAviWriter with an
+MJpegEncoder): a frame whose batch is still the engine's current one is
+encoded where it lies in HBM, a frame flushed from the pre-motion cache from
+its host copy; the bytes are the ones Pillow's libjpeg-turbo writes, so the
+file equals the one the host writer produces.
+
 Extra keyword arguments (not in the reference): device (HIP ordinal),
 batch (frames decoded ahead and processed per kernel launch; the per-frame
 results and the decisions are identical for any batch -- only ref_frame is
 then observed at batch boundaries), capture (a ready capture object),
-gpu_decode (see above).
+gpu_decode, gpu_encode (see above).
 
 There is no CPU fallback: without the HIP library this module raises
 NativeLibraryMissing at VideoMotion construction.
@@ -213,7 +221,7 @@ class VideoMotion:
                  yolo_tiny: bool = False, *,
                  device: int = 0, batch: int = 1, capture=None, engine: MotionEngine = None,
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
-                 pipeline_depth: int = None, gpu_decode: bool = None) -> None:
+                 pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -274,6 +282,7 @@ class VideoMotion:
         self._stream = int(stream)
         self._capture = capture
         self.gpu_decode = gpu_decode
+        self.gpu_encode = gpu_encode
         self._ahead: typing.Deque[VideoFrame] = deque()
         self.frames_read = 0
         self._jpeg_dec = None  # one-frame GPU decoder for raw frames of batches already overwritten
@@ -435,7 +444,8 @@ class VideoMotion:
             self.outfile_name = os.path.join(self.outdir, os.path.basename(outname)) + "_motion.avi"
         self.outfile = videoio.open_writer(self.outfile_name, self.codec, self.fps,
                                            (self.frame_width, self.frame_height),
-                                           jpeg=hasattr(self.cap, "read_jpeg"))
+                                           jpeg=hasattr(self.cap, "read_jpeg"), gpu_encode=self.gpu_encode,
+                                           device=self.device)
 
     def output_frame(self, frame: VideoFrame = None) -> None:
         """fm.py:509-530"""
@@ -449,24 +459,30 @@ class VideoMotion:
         self._write(frame, index)
 
     def _write_frame(self, frame: VideoFrame) -> None:
-        self._write(lambda: frame.raw, getattr(frame, "index", -1), getattr(frame, "jpeg", None))
+        self._write(lambda: frame.raw, getattr(frame, "index", -1), getattr(frame, "jpeg", None),
+                    getattr(frame, "_bound", None))
 
-    def _put(self, raw, jpeg) -> None:
-        if jpeg is not None and hasattr(self.outfile, "write_jpeg"):
-            self.outfile.write_jpeg(jpeg)  # MJPEG in, MJPG out: the source's bytes, no re-encode
-        else:
-            self.outfile.write(raw() if callable(raw) else raw)
+    def _put(self, raw, jpeg, bound=None) -> None:
+        out = self.outfile
+        if jpeg is not None and hasattr(out, "write_jpeg"):
+            out.write_jpeg(jpeg)  # MJPEG in, MJPG out: the source's bytes, no re-encode
+        elif (bound is not None and getattr(out, "encoder", None) is not None
+              and bound.engine.generation == bound.gen):
+            # GPU writer, the frame's batch still current: encoded where it lies in HBM (fm_frame_device)
+            out.write_device(bound.engine.frame_device_ptr(bound.t, bound.s), raw)
+        else:  # any other writer, or a frame of an older batch (the pre-motion cache): the host copy
+            out.write(raw() if callable(raw) else raw)
 
-    def _write(self, raw, index, jpeg=None):
+    def _write(self, raw, index, jpeg=None, bound=None):
         if not self.wrote_frames:
             self._make_outfile()
             self.wrote_frames = True
         try:
-            self._put(raw, jpeg)
+            self._put(raw, jpeg, bound)
         except Exception as e:  # noqa: BLE001 (fm.py:527-530)
             self.log.warning("Having to create output file due to exception: {}".format(e))
             self._make_outfile()
-            self._put(raw, jpeg)
+            self._put(raw, jpeg, bound)
         self.written_indices.append(index)
 
     # -- the hot path (fm.py:487-494, 619-636, 638-662) ------------------------

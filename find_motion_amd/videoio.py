@@ -25,7 +25,10 @@ available:
   instead (cv2.imdecode, else Pillow: libjpeg-turbo either way).
   MjpegAviWriter writes such files: the 'MJPG' output of an MJPEG input keeps
   the source's JPEG bytes (write_jpeg); write() encodes a BGR frame with
-  Pillow;
+  Pillow, or -- on opt-in (open_writer(gpu_encode=True), CLI --gpu-encode) --
+  on the GPU (find_motion_amd.MJpegEncoder), write_device() a frame already in
+  HBM: the same bytes either way (libjpeg-turbo's, as Pillow writes them; not
+  those of cv2.VideoWriter's own MJPG encoder, whose parity is unpinned);
 * in-memory sources for tests, benchmarks and embedding: ArrayCapture over a
   [N][H][W][3] uint8 array and SyntheticCapture over the deterministic
   synthetic video of find_motion_amd.synthetic.
@@ -495,11 +498,25 @@ class MjpegAviCapture(RawAviCapture):
 
 class MjpegAviWriter(RawAviWriter):
     """MJPEG AVI writer: frames encoded by Pillow (libjpeg-turbo) at `quality` (default 95, OpenCV's MJPG
-    default), one '00dc' chunk per frame."""
+    default), one '00dc' chunk per frame.
 
-    def __init__(self, path: str, fps: float, size, quality: int = 95, **jpeg_kw):
+    encoder (find_motion_amd.MJpegEncoder, or anything with its encode / encode_device): write() encodes on
+    the GPU instead, and write_device() takes a frame already in HBM; the bytes are the ones Pillow would
+    write for the encoder's settings (which replace quality / jpeg_kw), so the file is the same either way.
+    A frame the encoder refuses (FMError) is encoded by Pillow and logged.  device_frames / host_frames /
+    fallback_frames count the frames that went each way."""
+
+    def __init__(self, path: str, fps: float, size, quality: int = 95, encoder=None, **jpeg_kw):
         self.quality = int(quality)
         self.jpeg_kw = jpeg_kw
+        self.encoder = encoder
+        self.own_encoder = False  # open_writer made the encoder: release() closes it
+        self.device_frames = self.host_frames = self.fallback_frames = 0
+        if encoder is not None:
+            self.quality = int(getattr(encoder, "quality", quality))
+            self.jpeg_kw = dict(jpeg_kw, subsampling=int(getattr(encoder, "subsampling", 2)))
+            if getattr(encoder, "restart_interval", 0):
+                self.jpeg_kw["restart_marker_blocks"] = int(encoder.restart_interval)
         self.sizes = []
         super().__init__(path, fps, size)
 
@@ -528,18 +545,52 @@ class MjpegAviWriter(RawAviWriter):
         self.sizes.append(len(data))
         self.n += 1
 
-    def write(self, frame: np.ndarray) -> None:
+    def _host_encode(self, frame: np.ndarray) -> bytes:
         import io
 
         from PIL import Image
+        b = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(frame[..., ::-1])).save(b, "JPEG", quality=self.quality, **self.jpeg_kw)
+        return b.getvalue()
+
+    def write(self, frame: np.ndarray) -> None:
         frame = np.asarray(frame, dtype=np.uint8)
         if frame.shape != (self.h, self.w, 3):
             raise ValueError(f"frame shape {frame.shape} != ({self.h}, {self.w}, 3)")
-        b = io.BytesIO()
-        Image.fromarray(np.ascontiguousarray(frame[..., ::-1])).save(b, "JPEG", quality=self.quality, **self.jpeg_kw)
-        self.write_jpeg(b.getvalue())
+        if self.encoder is None:
+            self.write_jpeg(self._host_encode(frame))
+            return
+        from ._native import FMError
+        try:
+            data = self.encoder.encode(frame[None])[0]
+            self.host_frames += 1
+        except FMError as e:
+            log.info("frame refused by the GPU encoder (%s); encoding it on the host", e)
+            data = self._host_encode(frame)
+            self.fallback_frames += 1
+        self.write_jpeg(data)
+
+    def write_device(self, ptr: int, raw=None) -> None:
+        """A BGR frame [h][w][3] already in device memory at address ptr, encoded where it lies.  raw: the same
+        frame on the host (an array, or a callable that fetches it), used only if the encoder refuses."""
+        from ._native import FMError
+        if self.encoder is None:
+            raise ValueError("write_device needs a writer made with an encoder")
+        try:
+            data = self.encoder.encode_device([int(ptr)])[0]
+            self.device_frames += 1
+        except FMError as e:
+            if raw is None:
+                raise
+            log.info("device frame refused by the GPU encoder (%s); encoding it on the host", e)
+            data = self._host_encode(np.asarray(raw() if callable(raw) else raw, dtype=np.uint8))
+            self.fallback_frames += 1
+        self.write_jpeg(data)
 
     def release(self) -> None:
+        if self.own_encoder and self.encoder is not None:
+            self.encoder.close()
+            self.encoder = None
         if self.f is None:
             return
         f = self.f
@@ -603,12 +654,24 @@ def open_capture(source, device: int = 0, gpu_decode: bool | None = None):
     return RawAviCapture(str(source))
 
 
-def open_writer(path: str, codec: str, fps: float, size, jpeg: bool = False):
+def open_writer(path: str, codec: str, fps: float, size, jpeg: bool = False, gpu_encode=None, device: int = 0):
     """cv2.VideoWriter(path, fourcc(codec), fps, size) (fm.py:468-470), else an uncompressed AVI.
     jpeg: the frames come from an MJPEG source -- an 'MJPG' output is then an MjpegAviWriter that
-    stores the source's JPEG bytes as they are (write_jpeg), with or without cv2."""
+    stores the source's JPEG bytes as they are (write_jpeg), with or without cv2.
+    gpu_encode: True (or an encoder object) with codec 'MJPG' -- an MjpegAviWriter whose frames are encoded
+    on the GPU (MJpegEncoder on `device`: quality 95, 4:2:0, the bytes Pillow's libjpeg-turbo writes), with
+    or without cv2 and for any source but an MJPEG one, whose bytes are still copied.  None / False: as
+    without it."""
     if jpeg and codec == "MJPG":
         return MjpegAviWriter(path, fps, size)
+    if gpu_encode and codec == "MJPG":
+        if gpu_encode is True:
+            from ._native import MJpegEncoder
+            w = MjpegAviWriter(path, fps, size, encoder=MJpegEncoder(int(size[0]), int(size[1]), max_frames=1,
+                                                                    device=device))
+            w.own_encoder = True
+            return w
+        return MjpegAviWriter(path, fps, size, encoder=gpu_encode)
     if cv2 is not None:
         return cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*codec), fps, size)
     if codec not in ("DIB ", "RGB ", "raw ", None):

@@ -334,6 +334,53 @@ int fm_read_frame(fm_ctx* ctx, int frame, int stream, uint8_t* out);
  * cascade without a round trip through host memory.  Valid until the next fm_wait. */
 int fm_frame_device(fm_ctx* ctx, int frame, int stream, const uint8_t** out);
 
+/* ---- Write side: BGR frames encoded to baseline JPEG on the GPU for the MJPG writer ------------
+ * Stands in for cv2.VideoWriter.write (find_motion.py:447-546, constructor default codec 'MJPG',
+ * :303) when the caller opts in: the frames are encoded where they lie in HBM and only compressed
+ * bytes cross PCIe.  The output is libjpeg-turbo's, byte for byte, as Pillow calls it --
+ * Image.save(..., "JPEG", quality=q, subsampling=s[, restart_marker_blocks=n]): jpeg_set_quality(q,
+ * force_baseline) tables, JDCT_ISLOW, the T.81 Annex K Huffman tables (not optimized), JFIF 1.01
+ * APP0 -- i.e. the bytes videoio.MjpegAviWriter writes on the host.  cv2.VideoWriter's built-in
+ * MJPG encoder is OpenCV's own code, not libjpeg: parity with its bytes is unpinned here, as the
+ * FFmpeg decode parity is on the read side.
+ * Supported: BGR u8 [H][W][3] frames (each frame contiguous) up to 65535 x 65535 and 2^20 blocks,
+ * three components, subsampling in Pillow's values 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0, quality 1..100,
+ * restart_interval in MCUs (0 = none, at most 65535).  Not supported: grayscale output, optimized
+ * Huffman tables, progressive, 12-bit. */
+typedef struct fm_mjpeg_enc fm_mjpeg_enc;
+/* The bytes from SOI through the SOS segment of such a file (the same for every frame of one
+ * size and setting): *len = their number, copied to out when cap suffices.  Pure host code, no
+ * HIP call.  FM_EINVAL for settings outside the ranges above (*len = 0) or a buffer too small. */
+int fm_jpeg_header(int width, int height, int quality, int subsampling, int restart_interval, uint8_t* out, size_t cap,
+                   size_t* len);
+/* An encoder for width x height frames, up to max_frames per call.  Settings outside the ranges
+ * above: FM_EINVAL before any HIP call.  *out is set even on failure (fm_mjpeg_enc_last_error says
+ * why); release with fm_mjpeg_enc_destroy. */
+int fm_mjpeg_enc_create(int device, int width, int height, int max_frames, int quality, int subsampling,
+                        int restart_interval, fm_mjpeg_enc** out);
+void fm_mjpeg_enc_destroy(fm_mjpeg_enc* enc);
+const char* fm_mjpeg_enc_last_error(const fm_mjpeg_enc* enc);
+/* Encode n frames [n][H][W][3]: host memory (copied to the device first), or device memory when
+ * on_device (read in place).  Synchronous, on the encoder's own stream: device frames must be
+ * complete (the caller synchronises the streams that wrote them).  The results stay on the device
+ * until the next call; fm_mjpeg_enc_get fetches them. */
+int fm_mjpeg_encode(fm_mjpeg_enc* enc, const uint8_t* frames, int n, int on_device);
+/* fm_mjpeg_encode over n frames in device memory at n separate addresses (frames[i]: [H][W][3]
+ * BGR), as fm_haar_detect_frame_list takes them: a frame from fm_frame_device is encoded where it
+ * lies. */
+int fm_mjpeg_encode_frame_list(fm_mjpeg_enc* enc, const uint8_t* const* frames, int n);
+/* The complete JPEG (SOI .. EOI) of frame `frame` of the last call: *len = its size, copied to out
+ * when cap suffices (FM_EINVAL otherwise; call again with *len bytes).  Only the entropy-coded
+ * bytes are copied from the device. */
+int fm_mjpeg_enc_get(fm_mjpeg_enc* enc, int frame, uint8_t* out, size_t cap, size_t* len);
+/* The quantized coefficients of that frame (parity tests: what tells a DCT fault from a Huffman
+ * fault): int16, blocks in scan (MCU-interleaved) order with dummy blocks included, 64 per block in
+ * zigzag order.  Returns their number (cap counts coefficients; FM_EINVAL when it is smaller). */
+int fm_mjpeg_enc_coefficients(fm_mjpeg_enc* enc, int frame, int16_t* out, size_t cap);
+/* Device time of the last call, from its first kernel to its last (HIP events; the two host
+ * round trips that size the buffers lie inside it), ms. */
+double fm_mjpeg_enc_last_ms(const fm_mjpeg_enc* enc);
+
 #ifdef __cplusplus
 }
 #endif
