@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("FM_HIP_LIB") or LIB_PATH  # unset or empty: the in-tr
 
 FM_OK, FM_EINVAL, FM_EHIP, FM_ENOMEM, FM_ESTATE, FM_ENOTSUP = 0, -1, -2, -3, -4, -5
 FM_FLAG_KEEP_PLANES, FM_FLAG_PROFILE, FM_FLAG_PROFILE_PIX, FM_FLAG_CONTOUR_AREA = 0x1, 0x2, 0x4, 0x8
+FM_FLAG_CONTOUR_POINTS = 0x10
 PLANE_GRAY, PLANE_BLUR, PLANE_DELTA, PLANE_SMALL = 0, 1, 2, 3
 
 EXPORTED = (
@@ -35,6 +36,7 @@ EXPORTED = (
     "fm_haar_collect",
     "fm_jpeg_header", "fm_mjpeg_enc_create", "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_encode",
     "fm_mjpeg_encode_frame_list", "fm_mjpeg_enc_get", "fm_mjpeg_enc_coefficients", "fm_mjpeg_enc_last_ms",
+    "fm_get_contour_points", "fm_last_trace_stats",
 )
 
 
@@ -66,7 +68,7 @@ class FMHaarDesc(C.Structure):
 class FMContour(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
                 ("origin_x", C.c_int32), ("origin_y", C.c_int32), ("area2", C.c_int32),
-                ("reserved1", C.c_int32)]
+                ("npts", C.c_int32)]
 
 
 _lib = None
@@ -112,6 +114,8 @@ def load() -> C.CDLL:
     L.fm_max_inflight.argtypes = [vp]
     L.fm_last_fallbacks.argtypes = [vp]
     L.fm_last_ccl_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.fm_get_contour_points.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.fm_last_trace_stats.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.fm_footprint.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.fm_haar_create.argtypes = [i32, C.POINTER(FMHaarDesc), C.POINTER(vp)]
     L.fm_haar_destroy.argtypes = [vp]
@@ -185,13 +189,24 @@ class Contour:
 
     bbox is cv2.boundingRect's (x, y, w, h) (fm.py:792); origin is the border
     start (the component's raster-first pixel); area is cv2.contourArea of the
-    CHAIN_APPROX_SIMPLE contour (fm.py:679), None unless the engine traces it."""
+    CHAIN_APPROX_SIMPLE contour (fm.py:679), None unless the engine traces it; points is
+    that contour as cv2.findContours returns it, an (n, 1, 2) int32 array of (x, y) in trace
+    order from the start pixel, None unless the engine has contour_points=True.
+    np.asarray(contour) is points, so cv2.drawContours / contourArea / boundingRect /
+    convexHull / pointPolygonTest take a Contour where the reference had the array."""
     x: int
     y: int
     w: int
     h: int
     origin: tuple
     area: float | None = None
+    points: np.ndarray | None = None
+
+    def __array__(self, dtype=None, copy=None):
+        if self.points is None:
+            raise TypeError("this Contour carries no points: create the engine with contour_points=True")
+        a = self.points if dtype is None else self.points.astype(dtype, copy=False)
+        return a.copy() if copy else a
 
     @property
     def bbox(self):
@@ -204,12 +219,13 @@ class MotionEngine:
     def __init__(self, *, n_streams: int, src_w: int, src_h: int, box_size: int, ksize: int,
                  threshold: int, avg: float, max_batch: int = 1, max_contours: int = 4096,
                  keep_planes: bool = False, profile: bool | str = False, device: int = 0,
-                 contour_area: bool = False):
+                 contour_area: bool = False, contour_points: bool = False):
         # profile: True = every kernel timed with HIP events, "pix" = pixel-stream kernels only
         self._L = load()
         p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg),
                      max_batch, max_contours,
                      (FM_FLAG_KEEP_PLANES if keep_planes else 0) | (FM_FLAG_CONTOUR_AREA if contour_area else 0) |
+                     (FM_FLAG_CONTOUR_POINTS if contour_points else 0) |
                      (FM_FLAG_PROFILE_PIX if profile == "pix" else FM_FLAG_PROFILE if profile else 0))
         h = C.c_void_p()
         rc = self._L.fm_create(C.byref(h), C.byref(p))
@@ -228,6 +244,7 @@ class MotionEngine:
         self.max_contours = max_contours
         self.last_batch = 0
         self.keep_planes = bool(keep_planes)
+        self.contour_points = bool(contour_points)
         self.generation = 0    # bumped at every wait(): results of older batches are gone
         self._init = [False] * n_streams
         self._inflight = []    # (n_frames, host frames kept alive) per submitted, not yet waited batch
@@ -404,9 +421,37 @@ class MotionEngine:
             buf = (FMContour * cap)()
             n = self._check(self._L.fm_get_contours(self._h, frame, stream, C.cast(buf, C.c_void_p), cap))
             if n <= cap:
-                return [Contour(c.x, c.y, c.w, c.h, (c.origin_x, c.origin_y), c.area2 / 2 if c.area2 >= 0 else None)
-                        for c in buf[:n]]
+                out = [Contour(c.x, c.y, c.w, c.h, (c.origin_x, c.origin_y), c.area2 / 2 if c.area2 >= 0 else None)
+                       for c in buf[:n]]
+                if self.contour_points:
+                    xy = self.contour_points_xy(frame, stream)
+                    ends = np.cumsum([c.npts for c in buf[:n]])
+                    if n and int(ends[-1]) != len(xy):
+                        raise FMError(FM_ESTATE, f"{len(xy)} points for records that count {int(ends[-1])}")
+                    for c, e, k in zip(out, ends, [c.npts for c in buf[:n]]):
+                        c.points = xy[e - k:e].reshape(k, 1, 2)
+                return out
             cap = n
+
+    def contour_points_xy(self, frame: int, stream: int) -> np.ndarray:
+        """Every contour point of (frame, stream) as one (total, 2) int32 array of (x, y), the contours
+        back to back in contours() order (fm_get_contour_points: one host copy)."""
+        total = C.c_size_t(0)
+        rc = self._L.fm_get_contour_points(self._h, frame, stream, None, 0, C.byref(total))
+        if rc != FM_OK and not (rc == FM_EINVAL and total.value > 0):
+            self._check(rc)
+        xy = np.empty((total.value, 2), np.int32)
+        if total.value:
+            self._check(self._L.fm_get_contour_points(self._h, frame, stream, _ptr(xy), total.value, C.byref(total)))
+        return xy
+
+    def trace_stats(self) -> dict:
+        """Contour trace of the last waited batch (contour_points=True): contours walked on a staged
+        window (registers or LDS), contours walked unstaged (larger boxes: global memory behind a
+        sliding window), border steps walked."""
+        a, b, st = C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self._L.fm_last_trace_stats(self._h, C.byref(a), C.byref(b), C.byref(st)))
+        return {"staged": a.value, "unstaged": b.value, "steps": st.value}
 
     def mask(self, frame: int, stream: int) -> np.ndarray:
         out = np.empty(self.work_shape, np.uint8)

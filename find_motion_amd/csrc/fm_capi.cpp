@@ -114,6 +114,16 @@ struct fm_ctx {
     size_t rec_one_cap = 0;
     int32_t* d_area = nullptr;     // FM_FLAG_CONTOUR_AREA: jobs [area_cap][3] + areas [area_cap]
     size_t area_cap = 0;
+    // FM_FLAG_CONTOUR_POINTS (contour_points): all grown on demand, from counts known beforehand
+    int32_t* d_trace = nullptr;    // jobs [trace_cap][8] + path lists [trace_cap] + results [trace_cap][3] + error word
+    size_t trace_cap = 0;
+    int32_t* d_cpts = nullptr;     // the batch's points [cpts_cap][2]
+    size_t cpts_cap = 0;
+    int32_t* h_pts = nullptr;      // page-locked copy of them: one device-to-host copy per batch
+    size_t h_pts_cap = 0;
+    std::vector<size_t> pts_off;   // [ready * S + 1] first point of each (t*S+s); empty before the first traced batch
+    int32_t trace_n[2] = {0, 0};   // contours of the last waited batch traced staged (registers, LDS) / unstaged
+    int64_t trace_steps = 0;       // border steps their count pass walked
     int32_t* d_rec_all = nullptr;  // k_emit_all records of one frame [rec_all_cap][5] + counter
     size_t rec_all_cap = 0;
     int rec_cap = 0;          // records per frame in each slot's mapped buffer (the first fetch; more -> k_emit_all)
@@ -397,6 +407,100 @@ int contour_areas(fm_ctx* c, BatchSlot& B, size_t F) {
                                        o.origin_y);
             o.area2 = a2[k++];
         }
+    return FM_OK;
+}
+
+// FM_FLAG_CONTOUR_POINTS: the CHAIN_APPROX_SIMPLE points of every contour of the finished batch in slot B
+// (fm.py:269-272), traced on the GPU on the same masks as contour_areas: a count pass (npts, area2), the
+// exclusive scan here, the buffers grown from the known total, an emit pass, one copy to the host.
+int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
+    c->trace_n[0] = c->trace_n[1] = 0;
+    c->trace_steps = 0;
+    c->pts_off.assign(F + 1, 0);
+    size_t n = 0;
+    for (size_t f = 0; f < F; f++) n += c->contours[f].size();
+    if (n == 0) return FM_OK;
+    if (n > 0x7fffffffull / 12) return fail(c, FM_ENOMEM, "%zu contours in one batch: too many to trace", n);
+    std::vector<int32_t> up(n * 9);  // jobs, then the three paths' lists
+    std::vector<int32_t> path[kTracePaths];
+    size_t k = 0;
+    for (size_t f = 0; f < F; f++)
+        for (const fm_contour& o : c->contours[f]) {
+            int32_t* j = &up[k * 8];
+            j[0] = (int32_t)f, j[1] = o.origin_x, j[2] = o.origin_y, j[3] = o.x, j[4] = o.y, j[5] = o.w, j[6] = o.h, j[7] = 0;
+            path[trace_box_path(o.w, o.h)].push_back((int32_t)k);
+            k++;
+        }
+    int32_t* lists = &up[n * 8];
+    for (auto& v : path) lists = std::copy(v.begin(), v.end(), lists);
+    if (n > c->trace_cap) {
+        dfree(c, c->d_trace);
+        c->trace_cap = 0;
+        if (int rc = dalloc(c, &c->d_trace, n * 12 + 1)) return rc;
+        c->trace_cap = n;
+    }
+    int32_t* d_jobs = c->d_trace;
+    int32_t* d_res = c->d_trace + n * 9;
+    int32_t* d_err = c->d_trace + n * 12;
+    hipStream_t st = c->aux_stream;
+    TraceArgs ta{c->use_fused ? B.d_dbits : nullptr, c->use_fused ? B.d_candf : nullptr, c->use_fused ? nullptr : c->d_mask,
+                 c->ntiles, c->ntx, c->h, c->w, d_jobs, d_jobs + n * 8,
+                 {(int)path[0].size(), (int)path[1].size(), (int)path[2].size(), (int)path[3].size()}, d_res, nullptr, d_err};
+    std::vector<int32_t> res(n * 3);
+    HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    HIP_TRY(c, launch_trace(st, ta, false, &c->timer));
+    HIP_TRY(c, hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    size_t total = 0;
+    k = 0;
+    for (size_t f = 0; f < F; f++) {
+        c->pts_off[f] = total;
+        for (fm_contour& o : c->contours[f]) {
+            const int32_t* r = &res[k * 3];
+            if (r[0] < 1) return fail(c, FM_EHIP, "contour of frame %zu at (%d, %d) has no closed border", f, o.origin_x,
+                                      o.origin_y);
+            o.npts = r[0];
+            o.area2 = r[1];
+            c->trace_steps += r[2];
+            up[k * 8 + 7] = (int32_t)total;
+            total += (size_t)r[0];
+            if (total > 0x7fffffffull) return fail(c, FM_ENOMEM, "more than 2^31 contour points in one batch");
+            k++;
+        }
+    }
+    c->pts_off[F] = total;
+    c->trace_n[0] = (int32_t)(path[0].size() + path[1].size() + path[2].size());
+    c->trace_n[1] = (int32_t)path[3].size();
+    // the total is known: size both point buffers before the emit pass touches them
+    if (total > c->cpts_cap) {
+        dfree(c, c->d_cpts);
+        c->cpts_cap = 0;
+        if (int rc = dalloc(c, &c->d_cpts, total * 2)) return rc;
+        c->cpts_cap = total;
+    }
+    if (total > c->h_pts_cap) {
+        if (c->h_pts) {
+            (void)hipHostFree(c->h_pts);
+            c->pinned_bytes -= c->h_pts_cap * 2 * sizeof(int32_t);
+        }
+        c->h_pts = nullptr;
+        c->h_pts_cap = 0;
+        const size_t want = std::max(total, (size_t)4096);
+        hipError_t e = halloc(c, &c->h_pts, want * 2 * sizeof(int32_t), hipHostMallocDefault);
+        if (e != hipSuccess) return fail(c, FM_ENOMEM, "hipHostMalloc(%zu bytes): %s", want * 2 * sizeof(int32_t),
+                                         hipGetErrorString(e));
+        c->h_pts_cap = want;
+    }
+    ta.pts = c->d_cpts;
+    int32_t err = 0;
+    HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), n * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, launch_trace(st, ta, true, &c->timer));
+    HIP_TRY(c, hipMemcpyAsync(c->h_pts, c->d_cpts, total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&err, d_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->timer.collect();
+    if (err) return fail(c, FM_EHIP, "the emit pass of the contour trace disagreed with its count pass (code %d)", err);
     return FM_OK;
 }
 
@@ -822,6 +926,8 @@ void fm_destroy(fm_ctx* c) {
     }
     dfree(c->d_bg[0]); dfree(c->d_bg[1]); dfree(c->d_keep); dfree(c->d_has_keep); dfree(c->d_init); dfree(c->d_mask);
     dfree(c->d_label); dfree(c->d_cid); dfree(c->d_outer); dfree(c->d_rec_dev); dfree(c->d_rec_one); dfree(c->d_rec_all); dfree(c->d_area);
+    dfree(c->d_trace); dfree(c->d_cpts);
+    if (c->h_pts) (void)hipHostFree(c->h_pts);
     dfree(c->d_xofs); dfree(c->d_xcnt); dfree(c->d_xwt); dfree(c->d_yofs); dfree(c->d_ycnt); dfree(c->d_ywt);
     for (hipStream_t st : {c->own_stream, c->aux_stream, c->rs_stream, c->rs_stream2})
         if (st) (void)hipStreamDestroy(st);
@@ -1277,7 +1383,7 @@ int fm_wait(fm_ctx* c) {
             o.origin_x = q[0] % c->w;
             o.origin_y = q[0] / c->w;
             o.area2 = -1;
-            o.reserved1 = 0;
+            o.npts = 0;
         }
     }
 #ifdef FM_DEV_SWITCHES
@@ -1293,8 +1399,15 @@ int fm_wait(fm_ctx* c) {
         add("host:wait_records", hw3 - hw2);
     }
 #endif
-    if (c->p.flags & FM_FLAG_CONTOUR_AREA)
+    if (c->p.flags & FM_FLAG_CONTOUR_POINTS) {  // (area2 comes with the points: no second trace)
+        c->pts_off.clear();
+        if (int rc = contour_points(c, B, F)) {
+            c->pts_off.clear();
+            return rc;
+        }
+    } else if (c->p.flags & FM_FLAG_CONTOUR_AREA) {
         if (int rc = contour_areas(c, B, F)) return rc;
+    }
     c->ready = n;
     c->ready_slot = si;
     c->ready_gen = B.gen;
@@ -1308,6 +1421,30 @@ int fm_last_ccl_stats(const fm_ctx* c, int32_t* shared_nodes, int32_t* heavy_til
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     if (shared_nodes) *shared_nodes = c->stats[0];
     if (heavy_tiles) *heavy_tiles = c->stats[1];
+    return FM_OK;
+}
+
+int fm_last_trace_stats(const fm_ctx* c, int32_t* staged, int32_t* unstaged, int64_t* steps) {
+    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (staged) *staged = c->trace_n[0];
+    if (unstaged) *unstaged = c->trace_n[1];
+    if (steps) *steps = c->trace_steps;
+    return FM_OK;
+}
+
+int fm_get_contour_points(fm_ctx* c, int frame, int stream, int32_t* xy, size_t cap, size_t* total) {
+    if (total) *total = 0;
+    if (!c || !total) return fail(c, FM_EINVAL, "null argument");
+    if (!(c->p.flags & FM_FLAG_CONTOUR_POINTS))
+        return fail(c, FM_ESTATE, "points not traced: create with FM_FLAG_CONTOUR_POINTS");
+    if (c->pts_off.empty()) return fail(c, FM_ESTATE, "no traced batch: call fm_wait first");
+    if (int rc = check_frame(c, frame, stream, false)) return rc;
+    const size_t f = (size_t)frame * c->p.n_streams + stream;
+    const size_t first = c->pts_off[f], n = c->pts_off[f + 1] - first;
+    *total = n;
+    if (cap < n) return fail(c, FM_EINVAL, "%zu points, room for %zu: call again with *total", n, cap);
+    if (n && !xy) return fail(c, FM_EINVAL, "null point buffer");
+    if (n) std::memcpy(xy, c->h_pts + first * 2, n * 2 * sizeof(int32_t));
     return FM_OK;
 }
 

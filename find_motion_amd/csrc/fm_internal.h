@@ -226,6 +226,29 @@ hipError_t launch_emit_all(hipStream_t st, const FusedArgs& a, int f, int32_t* r
 // origin y); the dilated mask of frame f is dbits/candf (fused path, [F][ntiles]...) or mask [F][h*w] bytes
 hipError_t launch_contour_area(hipStream_t st, const uint64_t* dbits, const uint8_t* candf, const uint8_t* mask, int ntiles,
                                int ntx, int h, int w, const int32_t* jobs, int n, int32_t* area2);
+// CHAIN_APPROX_SIMPLE points of external contours by border following (fm_trace.hip).  jobs [n][8] =
+// (frame, origin x, origin y, box x, box y, box w, box h, point offset); list: the contour indices of
+// the register path, the LDS path, the big-window LDS path, then the unstaged path (n_path of each; the
+// host sorts a box with trace_box_path); res [n][3] = (npts or -1, area2, steps), written by
+// the count pass (emit = false) and read by the emit pass, which writes contour i's points at
+// pts + 2 * offset_i and sets bits of *err when a walk disagrees with the count pass.
+constexpr int kTracePaths = 4;
+struct TraceArgs {
+    const uint64_t* dbits;
+    const uint8_t* candf;
+    const uint8_t* mask;
+    int ntiles, ntx, h, w;
+    const int32_t* jobs;
+    const int32_t* list;
+    int n_path[kTracePaths];
+    int32_t* res;
+    int32_t* pts;
+    int32_t* err;
+};
+int trace_box_path(int bw, int bh);  // 0 registers, 1 LDS, 2 big LDS window, 3 unstaged
+struct KernelTimer;
+// (timer: each path's launch timed under trace_count_<path> / trace_emit_<path>, FM_FLAG_PROFILE)
+hipError_t launch_trace(hipStream_t st, const TraceArgs& t, bool emit, KernelTimer* timer);
 // dilated bit rows of one frame -> mask bytes (VideoFrame.thresh) [h][w]; non-candidate tiles are 0
 hipError_t launch_expand_bits(hipStream_t st, const uint64_t* dbits, const uint8_t* candf, uint8_t* out, int h, int w,
                               int ntx);

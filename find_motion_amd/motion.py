@@ -46,7 +46,9 @@ Extra keyword arguments (not in the reference): device (HIP ordinal),
 batch (frames decoded ahead and processed per kernel launch; the per-frame
 results and the decisions are identical for any batch -- only ref_frame is
 then observed at batch boundaries), capture (a ready capture object),
-gpu_decode, gpu_encode (see above).
+gpu_decode, gpu_encode (see above), contour_points (every frame.contours[i]
+then carries its CHAIN_APPROX_SIMPLE points, traced on the GPU: np.asarray(c)
+is the (n, 1, 2) int32 array cv2.findContours returns at fm.py:269-272).
 
 There is no CPU fallback: without the HIP library this module raises
 NativeLibraryMissing at VideoMotion construction.
@@ -221,7 +223,8 @@ class VideoMotion:
                  yolo_tiny: bool = False, *,
                  device: int = 0, batch: int = 1, capture=None, engine: MotionEngine = None,
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
-                 pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None) -> None:
+                 pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None,
+                 contour_points: bool = False) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -283,6 +286,7 @@ class VideoMotion:
         self._capture = capture
         self.gpu_decode = gpu_decode
         self.gpu_encode = gpu_encode
+        self.contour_points = bool(contour_points)
         self._ahead: typing.Deque[VideoFrame] = deque()
         self.frames_read = 0
         self._jpeg_dec = None  # one-frame GPU decoder for raw frames of batches already overwritten
@@ -347,7 +351,8 @@ class VideoMotion:
             self._engine = MotionEngine(n_streams=1, src_w=self.frame_width, src_h=self.frame_height,
                                         box_size=self.box_size, ksize=self.gaussian[0], threshold=self.delta_thresh,
                                         avg=self.avg, max_batch=self.batch, keep_planes=self.keep_planes,
-                                        device=self.device, contour_area=self.area_filter)
+                                        device=self.device, contour_area=self.area_filter,
+                                        **({"contour_points": True} if self.contour_points else {}))
         if self.mask_areas:
             h, w = self._engine.work_shape
             self._engine.set_mask(self._stream, rasterize_masks(h, w, self.scale, self.mask_areas))
@@ -747,7 +752,8 @@ class StreamGroup:
         area_filter = int(W * H / 2 * (box / W)) < int(math.pow(box / mbs, 2))  # as _load_video decides
         self.engine = make(n_streams=S, src_w=W, src_h=H, box_size=box, ksize=make_gaussian_size(box, blur_scale),
                            threshold=kwargs.get("threshold", 7), avg=kwargs.get("avg", 0.1), max_batch=self.batch,
-                           keep_planes=show or dbg, device=device, contour_area=area_filter)
+                           keep_planes=show or dbg, device=device, contour_area=area_filter,
+                           **({"contour_points": True} if kwargs.get("contour_points") else {}))
         self.videos = [VideoMotion(filename=f, capture=c, engine=self.engine, stream=s, batch=self.batch, **kwargs)
                        for s, (f, c) in enumerate(zip(self.filenames, caps))]
 

@@ -46,6 +46,11 @@ extern "C" {
 #define FM_FLAG_CONTOUR_AREA 0x8u /* trace every external contour's border on the GPU at fm_wait and return
                                      2 x cv2.contourArea (fm.py:679) in fm_contour.area2: needed only where
                                      the area filter of fm.py:684 is live (max_area < min_area) */
+#define FM_FLAG_CONTOUR_POINTS 0x10u /* trace every external contour's border on the GPU at fm_wait and keep its
+                                        CHAIN_APPROX_SIMPLE points, the arrays cv2.findContours returns
+                                        (fm.py:269-272): fm_contour.npts, fm_get_contour_points.  area2 is filled
+                                        too (the count pass has it; FM_FLAG_CONTOUR_AREA need not be set and
+                                        starts no second trace).  Off: no kernel, buffer or result differs */
 
 /* planes for fm_read_plane */
 #define FM_PLANE_GRAY 0  /* VideoFrame.gray        (fm.py:493) */
@@ -77,8 +82,10 @@ typedef struct fm_contour {
     int32_t x, y, w, h;          /* cv2.boundingRect (fm.py:792) */
     int32_t origin_x, origin_y;  /* border start = raster-first pixel of the component */
     int32_t area2;               /* 2 x cv2.contourArea of the CHAIN_APPROX_SIMPLE contour (an integer: the
-                                    shoelace sum); -1 unless the context has FM_FLAG_CONTOUR_AREA */
-    int32_t reserved1;
+                                    shoelace sum); -1 unless the context has FM_FLAG_CONTOUR_AREA or
+                                    FM_FLAG_CONTOUR_POINTS */
+    int32_t npts;                /* its number of CHAIN_APPROX_SIMPLE points (>= 1); 0 unless the context has
+                                    FM_FLAG_CONTOUR_POINTS */
 } fm_contour;
 
 /* Library version (FM_ABI_VERSION) */
@@ -146,6 +153,21 @@ int fm_get_counts(fm_ctx* ctx, int32_t* counts);
  * contour is kept whatever fm_params.max_contours is (a frame with more is
  * fetched whole by fm_wait), so a second call with cap = count gets them all. */
 int fm_get_contours(fm_ctx* ctx, int frame, int stream, fm_contour* out, int cap);
+
+/* FM_FLAG_CONTOUR_POINTS: the CHAIN_APPROX_SIMPLE points of every contour of one (frame, stream) of the last
+ * batch, xy = [*total][2] as (x, y).  Contours in the order of fm_get_contours: contour i's npts_i points
+ * follow those of contours 0 .. i-1; within a contour in trace order, the order cv2.findContours returns,
+ * first point the start pixel (origin_x, origin_y).  *total is always set; the points are copied when
+ * cap >= *total (cap counts points), FM_EINVAL otherwise: call again with *total, as fm_mjpeg_enc_get.
+ * FM_ESTATE without the flag or before the first fm_wait.  A host copy: fm_wait fetched the whole batch's
+ * points in one transfer.  Valid until the next fm_wait, like the records.
+ * Limits: fewer than 2^31 points and about 1.7e8 contours per batch (FM_ENOMEM from fm_wait beyond); a
+ * start pixel whose border does not close within 4 (w + 2)(h + 2) + 16 steps makes fm_wait return FM_EHIP. */
+int fm_get_contour_points(fm_ctx* ctx, int frame, int stream, int32_t* xy, size_t cap, size_t* total);
+/* Diagnostics of the last waited batch's contour trace: contours traced from a staged window (registers or
+ * LDS: padded box up to 63.5 KiB of bit rows, about 700 x 700), contours traced unstaged (larger
+ * boxes: global memory behind a sliding window), and the border steps walked by the count pass. */
+int fm_last_trace_stats(const fm_ctx* ctx, int32_t* staged, int32_t* unstaged, int64_t* steps);
 
 /* Diagnostics: frames of the last waited batch whose contours came from the
  * pixel-level fallback (the batch exhausted its contour-pass node pool). */
