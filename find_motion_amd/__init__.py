@@ -38,6 +38,7 @@ from ._native import (  # noqa: F401
     MotionEngine,
     NativeLibraryMissing,
     rasterize_masks,
+    yuv_frame_bytes,
 )
 from .motion import StreamGroup, VideoError, VideoFrame, VideoMotion, run_vid  # noqa: F401,E402
 

@@ -37,7 +37,12 @@ EXPORTED = (
     "fm_jpeg_header", "fm_mjpeg_enc_create", "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_encode",
     "fm_mjpeg_encode_frame_list", "fm_mjpeg_enc_get", "fm_mjpeg_enc_coefficients", "fm_mjpeg_enc_last_ms",
     "fm_get_contour_points", "fm_last_trace_stats",
+    "fm_yuv_frame_bytes", "fm_submit_yuv", "fm_submit_yuv_list",
 )
+# fm_yuv_layout.format (FM_YUV_*), by fourcc
+YUV_NV12, YUV_I420, YUV_YUY2, YUV_UYVY = 0, 1, 2, 3
+YUV_FORMATS = {"NV12": YUV_NV12, "I420": YUV_I420, "IYUV": YUV_I420, "YUY2": YUV_YUY2, "YUYV": YUV_YUY2,
+               "UYVY": YUV_UYVY}
 
 
 class NativeLibraryMissing(ImportError):
@@ -63,6 +68,10 @@ class FMHaarDesc(C.Structure):
                 ("node_left", C.c_void_p), ("node_right", C.c_void_p), ("node_feature", C.c_void_p),
                 ("node_threshold", C.c_void_p), ("leaves", C.c_void_p), ("feat_rects", C.c_void_p),
                 ("feat_weights", C.c_void_p), ("feat_tilted", C.c_void_p)]
+
+
+class FMYuvLayout(C.Structure):
+    _fields_ = [("format", C.c_int), ("pitch", C.c_int), ("chroma_offset", C.c_int), ("frame_stride", C.c_size_t)]
 
 
 class FMContour(C.Structure):
@@ -145,6 +154,9 @@ def load() -> C.CDLL:
     L.fm_mjpeg_tune.argtypes = [vp, i32, i32]
     L.fm_mjpeg_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.fm_submit_streams.argtypes = [vp, vp, i32, i32]
+    L.fm_yuv_frame_bytes.argtypes = [i32, i32, C.POINTER(FMYuvLayout), C.POINTER(C.c_size_t)]
+    L.fm_submit_yuv.argtypes = [vp, vp, i32, C.POINTER(FMYuvLayout), i32]
+    L.fm_submit_yuv_list.argtypes = [vp, vp, i32, C.POINTER(FMYuvLayout)]
     L.fm_jpeg_header.argtypes = [i32, i32, i32, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.fm_mjpeg_enc_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.fm_mjpeg_enc_destroy.argtypes = [vp]
@@ -181,6 +193,34 @@ def rasterize_masks(h: int, w: int, scale: float, polygons) -> np.ndarray:
     if rc != FM_OK:
         raise FMError(rc, "invalid mask polygons (each needs >= 2 points)")
     return keep
+
+
+def yuv_format(fmt) -> int:
+    """FM_YUV_* of a fourcc name ("NV12", "I420" / "IYUV", "YUY2" / "YUYV", "UYVY") or of the value itself."""
+    if isinstance(fmt, (bytes, bytearray)):
+        fmt = bytes(fmt).decode("ascii", "replace")
+    if isinstance(fmt, str):
+        try:
+            return YUV_FORMATS[fmt.strip().upper()]
+        except KeyError:
+            raise ValueError(f"unknown YUV format {fmt!r}") from None
+    return int(fmt)
+
+
+def yuv_layout(fmt, pitch: int = 0, chroma_offset: int = 0, frame_stride: int = 0) -> FMYuvLayout:
+    return FMYuvLayout(yuv_format(fmt), int(pitch), int(chroma_offset), int(frame_stride))
+
+
+def yuv_frame_bytes(width: int, height: int, fmt, pitch: int = 0, chroma_offset: int = 0, frame_stride: int = 0) -> int:
+    """Bytes one width x height frame occupies in this layout (fm_yuv_frame_bytes: host only); frames of a batch
+    lie frame_stride (0: this many) bytes apart.  FMError(FM_EINVAL) for a layout the engine refuses."""
+    L = load()
+    n = C.c_size_t()
+    lay = yuv_layout(fmt, pitch, chroma_offset, frame_stride)
+    rc = L.fm_yuv_frame_bytes(int(width), int(height), C.byref(lay), C.byref(n))
+    if rc != FM_OK:
+        raise FMError(rc, L.fm_last_error(None).decode())
+    return int(n.value)
 
 
 @dataclass
@@ -269,6 +309,21 @@ class MotionEngine:
         previous batches' kernels.  Freed by close(); keep it unchanged until wait() returns
         for a batch submitted from it."""
         shape = (n_frames, self.n_streams) + self.src_shape
+        nbytes = int(np.prod(shape))
+        p = C.c_void_p()
+        self._check(self._L.fm_host_alloc(self._h, nbytes, C.byref(p)))
+        if not hasattr(self, "_host_bufs"):
+            self._host_bufs = []
+        self._host_bufs.append(p)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nbytes,)).reshape(shape)
+
+    def host_buffer_yuv(self, n_frames: int, fmt, pitch: int = 0, chroma_offset: int = 0,
+                        frame_stride: int = 0) -> np.ndarray:
+        """host_buffer for YUV batches: page-locked uint8 [n_frames][n_streams][stride], stride = frame_stride or
+        the frame's bytes in this layout (yuv_frame_bytes); submit_yuv of it is an asynchronous DMA."""
+        H, W = self.src_shape[:2]
+        stride = int(frame_stride) or yuv_frame_bytes(W, H, fmt, pitch, chroma_offset)
+        shape = (int(n_frames), self.n_streams, stride)
         nbytes = int(np.prod(shape))
         p = C.c_void_p()
         self._check(self._L.fm_host_alloc(self._h, nbytes, C.byref(p)))
@@ -381,6 +436,46 @@ class MotionEngine:
         self._check(self._L.fm_submit_jpeg(self._h, decoder._h, _ptr(ptrs), _ptr(sizes), n // self.n_streams))
         del keep
         self._inflight.append((n // self.n_streams, None))
+
+    def submit_yuv(self, frames, fmt, pitch: int = 0, chroma_offset: int = 0, frame_stride: int = 0,
+                   n_frames: int | None = None) -> None:
+        """YUV frames in host memory (fm_submit_yuv): a uint8 array holding n x n_streams frames in [t][s] order,
+        frame_stride (0: the frame's bytes) apart, converted to BGR on the GPU in front of the hot path
+        (cv2.cvtColor COLOR_YUV2BGR_*).  fmt: "NV12", "I420", "YUY2", "UYVY" (or FM_YUV_*).  n_frames: taken
+        from the array when not given (its first axis, or its size for a flat one).  Keep the array unchanged
+        until wait() returns for the batch; read_frame() gives the converted BGR frame."""
+        f = np.ascontiguousarray(frames, dtype=np.uint8)
+        H, W = self.src_shape[:2]
+        extent = yuv_frame_bytes(W, H, fmt, pitch, chroma_offset, frame_stride)
+        stride = int(frame_stride) or extent
+        if n_frames is None:
+            n_frames = f.shape[0] if f.ndim >= 3 else (f.size + stride - extent) // (stride * self.n_streams)
+        n = int(n_frames)
+        if n >= 1 and f.size < (n * self.n_streams - 1) * stride + extent:
+            raise ValueError(f"{f.size} bytes for {n} x {self.n_streams} frames of {extent} bytes, {stride} apart")
+        lay = yuv_layout(fmt, pitch, chroma_offset, frame_stride)
+        self._check(self._L.fm_submit_yuv(self._h, _ptr(f), n, C.byref(lay), 0))
+        self._inflight.append((n, f))
+
+    def submit_yuv_device(self, ptr: int, n_frames: int, fmt, pitch: int = 0, chroma_offset: int = 0,
+                          frame_stride: int = 0) -> None:
+        """YUV frames already in device memory at ptr, [n_frames][n_streams] frames frame_stride apart, read in
+        place (keep them until wait() returns for the batch)."""
+        lay = yuv_layout(fmt, pitch, chroma_offset, frame_stride)
+        self._check(self._L.fm_submit_yuv(self._h, C.c_void_p(int(ptr)), int(n_frames), C.byref(lay), 1))
+        self._inflight.append((int(n_frames), None))
+
+    def submit_yuv_list(self, ptrs, fmt, pitch: int = 0, chroma_offset: int = 0) -> None:
+        """n x n_streams YUV frames in device memory at separate addresses, ptrs[t * n_streams + s] (a decoder's
+        surfaces: fm_submit_yuv_list), converted where they lie."""
+        ptrs = [int(p) for p in ptrs]
+        if not ptrs or len(ptrs) % self.n_streams:
+            raise ValueError(f"{len(ptrs)} frame addresses is not a multiple of n_streams={self.n_streams}")
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        lay = yuv_layout(fmt, pitch, chroma_offset, 0)
+        n = len(ptrs) // self.n_streams
+        self._check(self._L.fm_submit_yuv_list(self._h, C.cast(arr, C.c_void_p), n, C.byref(lay)))
+        self._inflight.append((n, None))
 
     def wait(self) -> None:
         """Complete the oldest batch in flight; its results become readable."""

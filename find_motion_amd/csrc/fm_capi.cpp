@@ -48,6 +48,10 @@ enum class ResizeMode { Identity, Fast, General };
 constexpr int kSlots = FM_SLOTS;
 struct BatchSlot {
     uint8_t* d_in = nullptr;        // host-fed staging [T][S][H][W][3]
+    uint8_t* d_yuv = nullptr;       // host-fed YUV staging of fm_submit_yuv (first use; grown on demand)
+    size_t yuv_cap = 0;             // its bytes
+    const uint8_t** d_ytab = nullptr;  // fm_submit_yuv_list: the batch's frame addresses [max_batch * S] on the device
+    const uint8_t** h_ytab = nullptr;  // and their page-locked staging
     uint8_t* d_work = nullptr;      // resized BGR [T][S][h][w][3] (mode D)
     uint8_t* d_planes = nullptr;    // [3][T][S][h*w] gray, blur, frame_delta (FM_FLAG_KEEP_PLANES)
     uint64_t* d_bits = nullptr;     // threshold bit rows (k_pix output)
@@ -914,10 +918,10 @@ void fm_destroy(fm_ctx* c) {
             st = nullptr;
         }
     for (auto& b : c->slots) {
-        dfree(b.d_in); dfree(b.d_work); dfree(b.d_planes); dfree(b.d_bits); dfree(b.d_dbits); dfree(b.d_tiles); dfree(b.d_sblur);
+        dfree(b.d_in); dfree(b.d_yuv); dfree(b.d_ytab); dfree(b.d_work); dfree(b.d_planes); dfree(b.d_bits); dfree(b.d_dbits); dfree(b.d_tiles); dfree(b.d_sblur);
         dfree(b.d_nodes); dfree(b.d_heavy); dfree(b.d_count); dfree(b.d_tflag); dfree(b.d_candf);
         dfree(b.d_clist); dfree(b.d_rlist); dfree(b.d_regrep); dfree(b.d_ncr);
-        for (auto* hp : {(void*)b.h_count, (void*)b.h_overflow, (void*)b.h_rec, (void*)b.h_init, (void*)b.h_stats})
+        for (auto* hp : {(void*)b.h_count, (void*)b.h_overflow, (void*)b.h_rec, (void*)b.h_init, (void*)b.h_stats, (void*)b.h_ytab})
             if (hp) (void)hipHostFree(hp);
         if (b.ev_pix) (void)hipEventDestroy(b.ev_pix);
         if (b.ev_done) (void)hipEventDestroy(b.ev_done);
@@ -991,8 +995,17 @@ int fm_set_hip_stream(fm_ctx* c, void* s) {
 
 // fm_submit / fm_submit_jpeg: frames from host memory (copied), device memory, or JPEGs decoded
 // on the input stream into the batch's device buffer (dec != nullptr)
+// (yuv: a validated fm_submit_yuv / fm_submit_yuv_list batch, converted into the slot's input buffer)
+namespace {
+struct YuvSrc {
+    int format, pitch;
+    size_t chroma_offset, extent, stride;  // stride: bytes between frames (contiguous source)
+    const uint8_t* const* list;            // F device addresses (host array), or nullptr
+};
+}  // namespace
 static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, fm_mjpeg* dec,
-                       const uint8_t* const* jpegs, const size_t* sizes, const uint8_t* const* per_stream = nullptr) {
+                       const uint8_t* const* jpegs, const size_t* sizes, const uint8_t* const* per_stream = nullptr,
+                       const YuvSrc* yuv = nullptr) {
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     if ((int)c->inflight.size() >= c->nslots)
         return fail(c, FM_ESTATE, "%d batch(es) already in flight: call fm_wait first", (int)c->inflight.size());
@@ -1004,7 +1017,7 @@ static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, f
             per_stream = nullptr;
         }
     }
-    if ((!frames && !dec && !per_stream) || n < 1 || n > c->p.max_batch)
+    if ((!frames && !dec && !per_stream && !(yuv && yuv->list)) || n < 1 || n > c->p.max_batch)
         return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d] or null frames", n, c->p.max_batch);
     HIP_TRY(c, hipSetDevice(c->p.device));
     const int si = c->next_slot;
@@ -1039,6 +1052,44 @@ static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, f
         const int rc = fm_mjpeg_enqueue(dec, jpegs, sizes, (int)F, B.d_in, rs);
         HIP_TRY(c, hipSetDevice(c->p.device));
         if (rc) return fail(c, rc, "JPEG decode: %s", fm_mjpeg_last_error(dec));
+        src = B.d_in;
+        on_device = 0;  // (the input stream ran: the pixel stream waits for it below)
+    } else if (yuv) {  // YUV frames -> BGR frames in the batch's device buffer, on the input stream
+        int rc;
+        if (!B.d_in && (rc = dalloc(c, &B.d_in, (size_t)c->p.max_batch * S * c->src_frame_bytes))) return rc;
+        YuvArgs ya{};
+        ya.src = frames;
+        if (yuv->list) {
+            const size_t cap = (size_t)c->p.max_batch * S;
+            if (!B.d_ytab && (rc = dalloc(c, &B.d_ytab, cap))) return rc;
+            if (!B.h_ytab) HIP_TRY(c, halloc(c, &B.h_ytab, cap * sizeof(uint8_t*), hipHostMallocDefault));
+            std::copy(yuv->list, yuv->list + F, B.h_ytab);  // (the slot is idle: its last batch was waited for)
+            HIP_TRY(c, hipMemcpyAsync(B.d_ytab, B.h_ytab, F * sizeof(uint8_t*), hipMemcpyHostToDevice, rs));
+            ya.srcs = B.d_ytab;
+        } else if (!on_device) {
+            const size_t bytes = (F - 1) * yuv->stride + yuv->extent;
+            if (bytes > B.yuv_cap) {  // first use, or a larger layout than the slot has seen
+                const size_t want = std::max(bytes, ((size_t)c->p.max_batch * S - 1) * yuv->stride + yuv->extent);
+                dfree(c, B.d_yuv);
+                B.yuv_cap = 0;
+                if ((rc = dalloc(c, &B.d_yuv, want))) return rc;
+                B.yuv_cap = want;
+            }
+            HIP_TRY(c, hipMemcpyAsync(B.d_yuv, frames, bytes, hipMemcpyHostToDevice, rs));
+            ya.src = B.d_yuv;
+        }
+        ya.frame_stride = yuv->stride;
+        ya.chroma_offset = yuv->chroma_offset;
+        ya.dst = B.d_in;
+        ya.format = yuv->format;
+        ya.pitch = yuv->pitch;
+        ya.W = c->p.src_w;
+        ya.H = c->p.src_h;
+        ya.F = (int)F;
+        ya.kstamp = c->timer.stamp("yuv2bgr");
+        const int tok = ya.kstamp ? -1 : c->timer.begin("yuv2bgr", rs);
+        HIP_TRY(c, launch_yuv2bgr(rs, ya));
+        c->timer.end(tok);
         src = B.d_in;
         on_device = 0;  // (the input stream ran: the pixel stream waits for it below)
     } else if (per_stream) {  // stream s's frames -> rows s, S + s, 2S + s, ... of the [t][s] batch layout
@@ -1289,6 +1340,66 @@ int fm_submit_jpeg(fm_ctx* c, fm_mjpeg* dec, const uint8_t* const* jpegs, const 
         return fail(c, FM_EINVAL, "decoder takes %d frames per call, the batch has %lld", dmax,
                     (long long)n * c->p.n_streams);
     return submit_impl(c, nullptr, n, 0, dec, jpegs, sizes);
+}
+
+// fm_yuv_layout resolved for width x height frames (pitch, chroma offset, extent, frame stride), or why not
+static const char* yuv_resolve(int W, int H, const fm_yuv_layout* L, YuvSrc& y) {
+    if (!L) return "null layout";
+    if (L->format < FM_YUV_NV12 || L->format > FM_YUV_UYVY) return "unknown YUV format";
+    const bool planar = L->format == FM_YUV_NV12 || L->format == FM_YUV_I420;
+    if (W < 1 || H < 1) return "frame size below 1";
+    if (W & 1) return "YUV frames need an even width";
+    if (planar && (H & 1)) return "NV12 / I420 frames need an even height";
+    const long long tight = planar ? (long long)W : 2ll * W;
+    if (tight > INT32_MAX) return "frame too wide";
+    if (L->pitch < 0 || (L->pitch != 0 && L->pitch < tight)) return "pitch below the tight row";
+    const size_t pitch = L->pitch ? (size_t)L->pitch : (size_t)tight;
+    if (L->format == FM_YUV_I420 && (pitch & 1)) return "I420 needs an even pitch (chroma rows are pitch / 2 bytes)";
+    size_t coff = 0, extent = pitch * (size_t)H;
+    if (planar) {
+        if (L->chroma_offset < 0 || (L->chroma_offset != 0 && (size_t)L->chroma_offset < pitch * (size_t)H))
+            return "chroma_offset inside the luma plane";
+        coff = L->chroma_offset ? (size_t)L->chroma_offset : pitch * (size_t)H;
+        // NV12: H/2 rows of pitch bytes; I420: two planes of H/2 rows of pitch/2 bytes
+        extent = coff + (L->format == FM_YUV_NV12 ? pitch * (size_t)(H / 2) : (pitch / 2) * (size_t)H);
+    }
+    if (L->frame_stride != 0 && L->frame_stride < extent) return "frame_stride below the frame's extent";
+    y.format = L->format;
+    y.pitch = (int)pitch;
+    y.chroma_offset = coff;
+    y.extent = extent;
+    y.stride = L->frame_stride ? L->frame_stride : extent;
+    y.list = nullptr;
+    return nullptr;
+}
+
+int fm_yuv_frame_bytes(int width, int height, const fm_yuv_layout* layout, size_t* bytes) {
+    if (bytes) *bytes = 0;
+    if (!bytes) return fail(nullptr, FM_EINVAL, "null argument");
+    YuvSrc y{};
+    if (const char* why = yuv_resolve(width, height, layout, y)) return fail(nullptr, FM_EINVAL, "%s", why);
+    *bytes = y.extent;
+    return FM_OK;
+}
+
+int fm_submit_yuv(fm_ctx* c, const uint8_t* frames, int n, const fm_yuv_layout* layout, int on_device) {
+    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!frames) return fail(c, FM_EINVAL, "null frames");
+    YuvSrc y{};
+    if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return fail(c, FM_EINVAL, "%s", why);
+    return submit_impl(c, frames, n, on_device, nullptr, nullptr, nullptr, nullptr, &y);
+}
+
+int fm_submit_yuv_list(fm_ctx* c, const uint8_t* const* frames, int n, const fm_yuv_layout* layout) {
+    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!frames) return fail(c, FM_EINVAL, "null frame address array");
+    YuvSrc y{};
+    if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return fail(c, FM_EINVAL, "%s", why);
+    if (n < 1 || n > c->p.max_batch) return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d]", n, c->p.max_batch);
+    for (size_t i = 0; i < (size_t)n * c->p.n_streams; i++)
+        if (!frames[i]) return fail(c, FM_EINVAL, "null address for frame %zu", i);
+    y.list = frames;
+    return submit_impl(c, nullptr, n, 1, nullptr, nullptr, nullptr, nullptr, &y);
 }
 
 int fm_wait(fm_ctx* c) {

@@ -196,6 +196,20 @@ hipError_t launch_resize_area(hipStream_t st, const uint8_t* src, uint8_t* dst, 
 hipError_t launch_resize_area_fast(hipStream_t st, const uint8_t* src, uint8_t* dst, int F, int H, int W,
                                    int h, int w, int sx, int sy, uint64_t* kstamp = nullptr);
 hipError_t launch_pixel(hipStream_t st, const PixelArgs& a);
+// YUV frames -> packed BGR [F][H][W][3] (fm_yuv.hip).  Frame f is at srcs[f] (a device table of F
+// addresses) when srcs is set, at src + f * frame_stride otherwise; pitch / chroma_offset as resolved
+// from fm_yuv_layout (never 0).  runs, groups and total are filled in by the launcher.
+struct YuvArgs {
+    const uint8_t* src;
+    const uint8_t* const* srcs;
+    size_t frame_stride, chroma_offset;
+    uint8_t* dst;
+    int format, pitch, W, H, F;
+    int runs, groups;     // lane runs per row, row groups (row pairs for 4:2:0) per frame
+    long long total;      // F * groups * runs
+    uint64_t* kstamp;
+};
+hipError_t launch_yuv2bgr(hipStream_t st, const YuvArgs& a);
 struct KernelTimer;
 hipError_t launch_ccl(hipStream_t st, const CclArgs& a, KernelTimer* timer);
 hipError_t launch_fused(hipStream_t st, const FusedArgs& a, KernelTimer* timer);

@@ -24,6 +24,13 @@ JPEG mode (every capture has read_jpeg(), i.e. MJPEG sources, SURVEY.md
 decodes them on the GPU (fm_submit_jpeg) in front of the hot path, so only
 compressed bytes cross PCIe.  Batch.frames then holds JPEG byte strings and
 Batch.buf is None.
+
+YUV mode (every capture has read_yuv() and they share one yuv_format, i.e. raw
+NV12 / I420 / YUY2 / UYVY sources): the decoder thread copies each frame's
+stored bytes into page-locked YUV batch buffers (host_buffer_yuv) and the
+engine converts them to BGR on the GPU (fm_submit_yuv), so 1.5 or 2 bytes per
+pixel cross PCIe instead of 3 and no host core converts.  Batch.frames then
+holds the frames' YUV bytes and Batch.yuv their format.
 """
 from __future__ import annotations
 
@@ -46,6 +53,7 @@ class Batch:
     frames: list
     T: int
     jpegs: list = None  # JPEG mode: the T x S compressed frames in [t][s] order, ended streams padded
+    yuv: str = None     # YUV mode: the format of frames[s][t] (bytes) and of buf [T][S][frame bytes]
 
 
 class BatchFeeder:
@@ -57,7 +65,7 @@ class BatchFeeder:
     """
 
     def __init__(self, engine, caps: list, batch: int, depth: int | None = None, buffers: list | None = None,
-                 jpeg: bool | None = None):
+                 jpeg: bool | None = None, yuv: bool | None = None):
         self.engine = engine
         self.caps = list(caps)
         self.T = int(batch)
@@ -70,6 +78,16 @@ class BatchFeeder:
         self.jpeg = can if jpeg is None else bool(jpeg)
         if self.jpeg and not can:
             raise ValueError("JPEG mode needs captures with read_jpeg() and one JPEG layout")
+        # YUV mode: every capture hands out its frames' YUV bytes in one format, and the engine converts them
+        fmts = {getattr(c, "yuv_format", None) if hasattr(c, "read_yuv") else None for c in self.caps}
+        can_yuv = (not self.jpeg and len(fmts) == 1 and None not in fmts and hasattr(engine, "submit_yuv")
+                   and hasattr(engine, "host_buffer_yuv"))
+        if yuv and not can_yuv:
+            raise ValueError("YUV mode needs captures with read_yuv() of one format and an engine with submit_yuv()")
+        self.yuv = fmts.pop() if (can_yuv if yuv is None else bool(yuv)) else None
+        if self.yuv and (buffers is None or any(b.ndim != 3 for b in buffers)):
+            # (buffers made for BGR batches do not fit: [T][S][frame bytes] ones from host_buffer_yuv do)
+            buffers = [engine.host_buffer_yuv(self.T, self.yuv) for _ in range(self.depth + 2)]
         self.decoder = None
         if self.jpeg:
             from ._native import MJpegDecoder
@@ -120,7 +138,7 @@ class BatchFeeder:
                 got = [[] for _ in range(S)]
                 for s, cap in enumerate(self.caps):
                     while live[s] and len(got[s]) < self.T:
-                        ok, fr = cap.read_jpeg() if self.jpeg else cap.read()
+                        ok, fr = cap.read_jpeg() if self.jpeg else cap.read_yuv() if self.yuv else cap.read()
                         if not ok:
                             live[s] = False
                             break
@@ -152,10 +170,14 @@ class BatchFeeder:
                             jobs.append((t, s, last[s]))  # ended stream: padding
 
                 def put(j, buf=buf):
-                    np.copyto(buf[j[0], j[1]], j[2])
+                    if self.yuv:  # the frame's bytes into the head of its [stride] slot
+                        fr = np.frombuffer(j[2], np.uint8)
+                        np.copyto(buf[j[0], j[1], :fr.size], fr)
+                    else:
+                        np.copyto(buf[j[0], j[1]], j[2])
 
                 list(self._copiers.map(put, jobs))
-                self._full.put(Batch(buf, got, T))
+                self._full.put(Batch(buf, got, T, None, self.yuv))
         except BaseException as e:  # noqa: BLE001 - re-raised in the consumer
             self._error = e
         finally:
@@ -191,6 +213,8 @@ class BatchFeeder:
                         break
                     if b.jpegs is not None:
                         self._submit_jpeg(b)
+                    elif b.yuv is not None:
+                        eng.submit_yuv(b.buf[:b.T], b.yuv)
                     else:
                         eng.submit(b.buf[:b.T])
                     inflight.append(b)

@@ -33,6 +33,11 @@ the device on first access (a frame the state machine writes, shows or runs a
 cascade on), and an MJPG output receives the source's JPEG bytes unchanged
 instead of a re-encode.  That decode equals libjpeg-turbo's (cv2.imdecode),
 not FFmpeg's (cv2.VideoCapture's default backend): see videoio.
+Uncompressed YUV AVIs (NV12, I420, YUY2, UYVY; read without OpenCV by
+videoio.RawAviCapture) take the same shape: the stored bytes are converted
+to BGR on the GPU (fm_submit_yuv, cv2.cvtColor's COLOR_YUV2BGR_* arithmetic)
+and frame.raw is fetched from the device on first access, or converted on
+the host once its batch is gone.  The file's fourcc selects the path.
 
 Writer: cv2.VideoWriter whenever OpenCV imports (fm.py:447-475).  With
 gpu_encode=True and codec 'MJPG' the motion frames of any other source are
@@ -126,10 +131,11 @@ class VideoFrame:
 
     _LAZY = ("gray", "blur", "frame_delta", "thresh")
 
-    def __init__(self, frame, show: bool = False, jpeg: bytes = None) -> None:
+    def __init__(self, frame, show: bool = False, jpeg: bytes = None, yuv=None) -> None:
         self._raw = frame
         self.jpeg = jpeg  # MJPEG input: the compressed source frame (raw is decoded on the GPU)
-        self._load = None  # MJPEG input: fetches raw on first access (VideoMotion.bind_results)
+        self.yuv = yuv    # YUV input: (the frame's YUV bytes, their format) (raw is converted on the GPU)
+        self._load = None  # MJPEG / YUV input: fetches raw on first access (VideoMotion.bind_results)
         self._show = show
         # fm.py:236 always copies raw; the copy is only drawn on (show), so it is made only then
         if frame is not None:
@@ -203,7 +209,7 @@ class VideoFrame:
         self._bound = None
         if self.in_cache:
             return
-        self._raw = self._load = self.jpeg = None
+        self._raw = self._load = self.jpeg = self.yuv = None
 
 
 class VideoMotion:
@@ -416,12 +422,16 @@ class VideoMotion:
         """VideoFrames of stream `stream` of a waited feeder batch (JPEG batches: raw fetched lazily)."""
         if b.jpegs is not None:
             return [VideoFrame(None, self.show, jpeg=j) for j in b.frames[stream]]
+        if getattr(b, "yuv", None) is not None:
+            return [VideoFrame(None, self.show, yuv=(y, b.yuv)) for y in b.frames[stream]]
         return [VideoFrame(r, self.show) for r in b.frames[stream]]
 
-    def _raw_loader(self, eng, gen: int, t: int, s: int, jpeg: bytes):
+    def _raw_loader(self, eng, gen: int, t: int, s: int, jpeg: bytes, yuv=None):
         def load():
             if eng.generation == gen:  # the batch's decoded frame is still in the engine's input slot
                 return eng.read_frame(t, s)
+            if yuv is not None:  # a YUV frame of an older batch: the same conversion on the host
+                return videoio.yuv_to_bgr(yuv[0], self.frame_width, self.frame_height, yuv[1])
             if self._jpeg_dec is None:
                 self._jpeg_dec = MJpegDecoder(self.frame_width, self.frame_height, 1, device=self.device)
             return videoio.decode_one(self._jpeg_dec, jpeg)
@@ -429,8 +439,8 @@ class VideoMotion:
 
     def bind_results(self, vfs, eng, stream: int) -> None:
         for t, vf in enumerate(vfs):
-            if vf.jpeg is not None and vf._raw is None:
-                vf._load = self._raw_loader(eng, eng.generation, t, stream, vf.jpeg)
+            if (vf.jpeg is not None or vf.yuv is not None) and vf._raw is None:
+                vf._load = self._raw_loader(eng, eng.generation, t, stream, vf.jpeg, vf.yuv)
             vf._bound = _Bound(eng, eng.generation, t, stream)
             vf.contours = eng.contours(t, stream)
             vf.processed = True

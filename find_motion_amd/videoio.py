@@ -269,6 +269,57 @@ class SyntheticCapture(ArrayCapture):
 
 
 # ---------------------------------------------------------------------------
+# YUV frames (what cameras and decoders hand out): the conversion the engine runs on the GPU
+# (fm_submit_yuv), vectorised on the host for read() and for frames whose batch is gone
+
+YUV_FOURCCS = {b"NV12": "NV12", b"I420": "I420", b"IYUV": "I420", b"YUY2": "YUY2", b"YUYV": "YUY2", b"UYVY": "UYVY"}
+YUV_BITS = {"NV12": 12, "I420": 12, "YUY2": 16, "UYVY": 16}
+
+
+def yuv_frame_size(w: int, h: int, fmt: str) -> int:
+    """Bytes of one tight w x h frame."""
+    return w * h * YUV_BITS[fmt] // 8
+
+
+def yuv_to_bgr(buf, w: int, h: int, fmt: str) -> np.ndarray:
+    """One tight YUV frame (bytes-like or uint8 array) -> BGR u8 (h, w, 3): cv2.cvtColor(yuv,
+    COLOR_YUV2BGR_{NV12,I420,YUY2,UYVY}) as OpenCV 4.x computes it -- BT.601 limited range in 20-bit fixed
+    point, the chroma pair of each 2x1 / 2x2 group replicated (restated from OpenCV's source; the engine's
+    GPU conversion is the same arithmetic)."""
+    fmt = YUV_FOURCCS.get(fmt, fmt) if isinstance(fmt, bytes) else {"IYUV": "I420", "YUYV": "YUY2"}.get(fmt, fmt)
+    if fmt not in YUV_BITS:
+        raise ValueError(f"unknown YUV format {fmt!r}")
+    if w < 2 or h < 1 or w & 1 or (fmt in ("NV12", "I420") and h & 1):
+        raise ValueError(f"{fmt} frames need an even width{' and height' if fmt in ('NV12', 'I420') else ''}")
+    a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, np.uint8).ravel()
+    n = yuv_frame_size(w, h, fmt)
+    if a.size < n:
+        raise ValueError(f"{a.size} bytes for a {w}x{h} {fmt} frame of {n}")
+    a = a[:n]
+    if fmt == "NV12":
+        Y = a[:w * h].reshape(h, w)
+        uv = a[w * h:].reshape(h // 2, w // 2, 2)
+        U, V = uv[..., 0].repeat(2, 0).repeat(2, 1), uv[..., 1].repeat(2, 0).repeat(2, 1)
+    elif fmt == "I420":
+        Y = a[:w * h].reshape(h, w)
+        q = (w // 2) * (h // 2)
+        U = a[w * h:w * h + q].reshape(h // 2, w // 2).repeat(2, 0).repeat(2, 1)
+        V = a[w * h + q:].reshape(h // 2, w // 2).repeat(2, 0).repeat(2, 1)
+    else:
+        p = a.reshape(h, w // 2, 4)
+        yi = 0 if fmt == "YUY2" else 1
+        Y = p[..., [yi, 2 + yi]].reshape(h, w)
+        U, V = p[..., 1 - yi].repeat(2, 1), p[..., 3 - yi].repeat(2, 1)
+    y = np.maximum(Y.astype(np.int32) - 16, 0) * 1220542 + (1 << 19)
+    uu, vv = U.astype(np.int32) - 128, V.astype(np.int32) - 128
+    out = np.empty((h, w, 3), np.uint8)
+    out[..., 0] = np.clip((y + 2116026 * uu) >> 20, 0, 255)
+    out[..., 1] = np.clip((y - 852492 * vv - 409993 * uu) >> 20, 0, 255)
+    out[..., 2] = np.clip((y + 1673527 * vv) >> 20, 0, 255)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # uncompressed AVI
 
 def _fourcc(s: str) -> bytes:
@@ -276,14 +327,23 @@ def _fourcc(s: str) -> bytes:
 
 
 class RawAviWriter:
-    """Uncompressed 24-bit BGR AVI (RIFF, one video stream, idx1 index)."""
+    """Uncompressed 24-bit BGR AVI (RIFF, one video stream, idx1 index).
 
-    def __init__(self, path: str, fps: float, size):
+    fourcc ("NV12", "I420", "YUY2", "UYVY"): an uncompressed YUV AVI instead -- write() then takes each frame's
+    bytes in that layout (tight, rows top-down) and stores them as they are."""
+
+    def __init__(self, path: str, fps: float, size, fourcc: str | None = None):
         self.path = path
         self.w, self.h = int(size[0]), int(size[1])
         self.fps = max(1, int(round(fps)))
         self.row = (self.w * 3 + 3) & ~3
         self.frame_bytes = self.row * self.h
+        self.fourcc = None
+        if fourcc is not None:
+            self.fourcc = YUV_FOURCCS.get(_fourcc(fourcc))
+            if self.fourcc is None:
+                raise ValueError(f"RawAviWriter stores BGR or NV12 / I420 / YUY2 / UYVY frames, not {fourcc!r}")
+            self.frame_bytes = yuv_frame_size(self.w, self.h, self.fourcc)
         self.n = 0
         self.index = []
         self.f = open(path, "wb")
@@ -296,9 +356,13 @@ class RawAviWriter:
         avih = struct.pack("<IIIIIIIIII16x", 1000000 // self.fps, self.frame_bytes * self.fps, 0, 0x10, 0, 0, 1,
                            self.frame_bytes, self.w, self.h)
         hdrl += b"avih" + struct.pack("<I", len(avih)) + avih
-        strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"DIB ", 0, 0, 0, 0, 1, self.fps, 0, 0, self.frame_bytes,
-                           0xFFFFFFFF, 0, 0, 0, self.w, self.h)
-        strf = struct.pack("<IiiHHIIiiII", 40, self.w, self.h, 1, 24, 0, self.frame_bytes, 0, 0, 0, 0)
+        strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", _fourcc(self.fourcc) if self.fourcc else b"DIB ", 0, 0, 0, 0,
+                           1, self.fps, 0, 0, self.frame_bytes, 0xFFFFFFFF, 0, 0, 0, self.w, self.h)
+        if self.fourcc:
+            strf = struct.pack("<IiiHH4sIiiII", 40, self.w, self.h, 1, YUV_BITS[self.fourcc], _fourcc(self.fourcc),
+                               self.frame_bytes, 0, 0, 0, 0)
+        else:
+            strf = struct.pack("<IiiHHIIiiII", 40, self.w, self.h, 1, 24, 0, self.frame_bytes, 0, 0, 0, 0)
         strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
         hdrl += b"LIST" + struct.pack("<I", len(strl)) + strl
         f.write(b"LIST" + struct.pack("<I", len(hdrl) + 4) + b"hdrl" + hdrl)
@@ -311,6 +375,15 @@ class RawAviWriter:
         return self.f is not None
 
     def write(self, frame: np.ndarray) -> None:
+        if self.fourcc:
+            data = frame.tobytes() if isinstance(frame, np.ndarray) else bytes(frame)
+            if len(data) != self.frame_bytes:
+                raise ValueError(f"{len(data)} bytes for a {self.w}x{self.h} {self.fourcc} frame of {self.frame_bytes}")
+            off = self.f.tell() - (self._movi_at + 8)
+            self.f.write(b"00db" + struct.pack("<I", self.frame_bytes) + data + (b"\0" if len(data) & 1 else b""))
+            self.index.append(off)
+            self.n += 1
+            return
         frame = np.asarray(frame, dtype=np.uint8)
         if frame.shape != (self.h, self.w, 3):
             raise ValueError(f"frame shape {frame.shape} != ({self.h}, {self.w}, 3)")
@@ -344,7 +417,13 @@ class RawAviWriter:
 
 
 class RawAviCapture:
-    """Reader for uncompressed 24-bit AVI (what RawAviWriter and OpenCV's 'DIB ' writer produce)."""
+    """Reader for uncompressed 24-bit AVI (what RawAviWriter and OpenCV's 'DIB ' writer produce), and for
+    uncompressed YUV AVI: strf compression NV12, I420 / IYUV, YUY2 / YUYV or UYVY (rows top-down, tight).
+
+    A YUV file sets yuv_format ("NV12", "I420", "YUY2", "UYVY"; None for 24-bit files) and gains read_yuv() ->
+    (ok, the frame's stored bytes) and peek() (the next frame's bytes, None at the end): BatchFeeder hands the
+    bytes to the engine, which converts them on the GPU (fm_submit_yuv).  read() converts on the host
+    (yuv_to_bgr) and returns BGR like any capture."""
 
     def __init__(self, path: str):
         self.path = path
@@ -353,11 +432,14 @@ class RawAviCapture:
         self.fps = 30.0
         self._i = 0
         self._open = False
+        self.yuv_format = None
         try:
             self._parse()
             self._open = self.w > 0 and self.h > 0
         except (OSError, ValueError, struct.error) as e:
             log.error("cannot read %s as uncompressed AVI: %s", path, e)
+        if self._open and self.yuv_format:
+            self.read_yuv, self.peek = self._read_yuv, self._peek_yuv
 
     def _parse(self):
         with open(self.path, "rb") as f:
@@ -384,10 +466,20 @@ class RawAviCapture:
                 if vals[0]:
                     self.fps = 1e6 / vals[0]
             elif ck == b"strf" and not self.w:
-                bi = struct.unpack("<IiiHHI", f.read(20))
+                raw = f.read(20)
+                bi = struct.unpack("<IiiHHI", raw)
+                yuv = YUV_FOURCCS.get(raw[16:20])
+                if yuv is not None and bi[4] == YUV_BITS[yuv]:
+                    self.w, self.h = bi[1], abs(bi[2])  # (YUV rows are top-down whatever the sign)
+                    if self.w & 1 or (yuv in ("NV12", "I420") and self.h & 1):
+                        raise ValueError(f"{yuv} AVI of odd size {self.w}x{self.h}")
+                    self.yuv_format = yuv
+                    self.frame_bytes = yuv_frame_size(self.w, self.h, yuv)
+                    pos = body + ln + (ln & 1)
+                    continue
                 if bi[4] != 24 or bi[5] != 0:
-                    raise ValueError(f"only uncompressed 24-bit BGR AVI is readable without OpenCV "
-                                     f"(bitcount {bi[4]}, compression {bi[5]})")
+                    raise ValueError(f"only uncompressed 24-bit BGR or NV12 / I420 / YUY2 / UYVY AVI is readable "
+                                     f"without OpenCV (bitcount {bi[4]}, compression {bi[5]})")
                 self.w, self.h = bi[1], bi[2]
                 self._bottom_up = self.h > 0
                 self.h = abs(self.h)
@@ -399,7 +491,23 @@ class RawAviCapture:
     def isOpened(self) -> bool:  # noqa: N802
         return self._open
 
+    def _peek_yuv(self):
+        if not self._open or self._i >= len(self._offsets):
+            return None
+        off, ln = self._offsets[self._i]
+        return self._mm[off: off + self.frame_bytes] if ln >= self.frame_bytes else None
+
+    def _read_yuv(self):
+        fr = self._peek_yuv()
+        if fr is None:
+            return False, None
+        self._i += 1
+        return True, fr
+
     def read(self):
+        if self.yuv_format:
+            ok, fr = self._read_yuv()
+            return (True, yuv_to_bgr(fr, self.w, self.h, self.yuv_format)) if ok else (False, None)
         if not self._open or self._i >= len(self._offsets):
             return False, None
         off, ln = self._offsets[self._i]

@@ -356,6 +356,56 @@ int fm_read_frame(fm_ctx* ctx, int frame, int stream, uint8_t* out);
  * cascade without a round trip through host memory.  Valid until the next fm_wait. */
 int fm_frame_device(fm_ctx* ctx, int frame, int stream, const uint8_t** out);
 
+/* ---- YUV input: NV12 / I420 / YUY2 / UYVY frames converted to BGR on the GPU ------------------
+ * What produces video hands out YUV, not BGR: a hardware decoder leaves NV12 surfaces (pitch, chroma
+ * offset) in device memory, a V4L2 camera gives YUY2 or UYVY, raw captures are I420 / NV12 / YUY2.
+ * fm_submit_yuv is fm_submit for such frames: they are converted into the batch slot's BGR input
+ * buffer on the context's input stream (as fm_submit_jpeg decodes into it) and the batch proceeds
+ * unchanged, so 1.5 or 2 bytes per pixel cross PCIe instead of 3, and a decoder's surface needs no
+ * round trip through the host.  The conversion is cv2.cvtColor(yuv, COLOR_YUV2BGR_{NV12,I420,YUY2,
+ * UYVY}) as OpenCV 4.x computes it -- BT.601 limited range in 20-bit fixed point, the chroma pair of
+ * a 2x1 / 2x2 group replicated:
+ *   uu = U - 128, vv = V - 128, y = max(0, Y - 16) * 1220542
+ *   R = sat_u8((y + 524288 + 1673527 vv) >> 20),  B = sat_u8((y + 524288 + 2116026 uu) >> 20)
+ *   G = sat_u8((y + 524288 - 852492 vv - 409993 uu) >> 20)            (>> floors negative sums)
+ * restated from OpenCV's source; OpenCV is not in the build image, so that parity is unpinned.
+ * Layouts of one W x H frame (W even; H even for NV12 / I420):
+ *   NV12  Y plane (H rows of `pitch` bytes), at chroma_offset H/2 rows of `pitch` bytes of U,V pairs
+ *   I420  Y plane, at chroma_offset the U plane (H/2 rows of pitch/2 bytes), then the V plane
+ *   YUY2  rows of Y0 U Y1 V per pixel pair;  UYVY  rows of U Y0 V Y1 */
+#define FM_YUV_NV12 0
+#define FM_YUV_I420 1
+#define FM_YUV_YUY2 2
+#define FM_YUV_UYVY 3
+typedef struct fm_yuv_layout {
+    int format;           /* FM_YUV_* */
+    int pitch;            /* bytes per luma row (packed formats: per row); 0 = tight (W, or 2W) */
+    int chroma_offset;    /* planar: bytes from frame start to the UV (NV12) / U (I420) plane;
+                             0 = pitch*H.  I420: chroma rows are pitch/2 bytes, V follows U's H/2 rows */
+    size_t frame_stride;  /* bytes between consecutive frames of the batch; 0 = tight */
+} fm_yuv_layout;
+/* *bytes = the extent of one width x height frame in this layout, from its first byte to the end of
+ * its last chroma row (tight NV12 / I420: W*H*3/2, packed: 2*W*H): consecutive frames of a batch lie
+ * frame_stride (0: this many) bytes apart.  Pure host code, no HIP call.  FM_EINVAL (*bytes = 0) for a
+ * null argument, an unknown format, width or height < 1, odd width, odd height for NV12 / I420, pitch
+ * below tight, odd pitch for I420, a nonzero chroma_offset below pitch*H, or a nonzero frame_stride
+ * below the extent. */
+int fm_yuv_frame_bytes(int width, int height, const fm_yuv_layout* layout, size_t* bytes);
+/* fm_submit with YUV frames in [n_frames][n_streams] order, frame_stride apart.  Host memory
+ * (on_device = 0): copied with hipMemcpyAsync on the input stream into the batch slot's YUV staging
+ * (allocated on first use, one per slot, counted by fm_footprint); the buffer must stay valid until
+ * fm_wait returns for the batch.  Device memory (on_device = 1): read in place, under fm_submit's
+ * rules.  fm_read_frame / fm_frame_device give the converted BGR frame.  FM_EINVAL, with nothing
+ * enqueued, for every case fm_yuv_frame_bytes refuses (the context's src_w x src_h is the frame
+ * size: a context created with an odd width takes no YUV) and for n_frames outside [1, max_batch].
+ * Under FM_FLAG_PROFILE the conversion is the kernel `yuv2bgr`. */
+int fm_submit_yuv(fm_ctx* ctx, const uint8_t* frames, int n_frames, const fm_yuv_layout* layout, int on_device);
+/* The same for n_frames x n_streams frames in device memory at separate addresses, frames[t * n_streams
+ * + s] (host array of device pointers, as fm_haar_detect_frame_list takes them): a decoder's surfaces
+ * are converted where they lie.  frame_stride is ignored.  The array may be reused when the call
+ * returns; the frames stay until fm_wait. */
+int fm_submit_yuv_list(fm_ctx* ctx, const uint8_t* const* frames, int n_frames, const fm_yuv_layout* layout);
+
 /* ---- Write side: BGR frames encoded to baseline JPEG on the GPU for the MJPG writer ------------
  * Stands in for cv2.VideoWriter.write (find_motion.py:447-546, constructor default codec 'MJPG',
  * :303) when the caller opts in: the frames are encoded where they lie in HBM and only compressed
