@@ -1,9 +1,9 @@
 // fm_capi.cpp — C ABI of the MI355X motion-detection hot path (include/find_motion_amd.h).
 //
 // Owns the per-context device state (background models, masks, batch
-// buffers), builds the host-side tables OpenCV builds per call (INTER_AREA
-// taps, fixed-point Gaussian taps) once at fm_create, and sequences the
-// kernels of fm_kernels.hip on one HIP stream per context.
+// buffers), has the host-side tables OpenCV builds per call (fm_tables.cpp)
+// built once at fm_create, and sequences the kernels of the fm_*.hip files
+// on the context's streams (submit: one short function, one stage each).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -132,8 +132,8 @@ struct fm_ctx {
     size_t rec_all_cap = 0;
     int rec_cap = 0;          // records per frame in each slot's mapped buffer (the first fetch; more -> k_emit_all)
     size_t dev_bytes = 0;     // device bytes the context holds now (fm_footprint)
-    std::unordered_map<const void*, size_t> dev_sizes;  // (so that a freed buffer leaves dev_bytes)
     size_t pinned_bytes = 0;  // and its page-locked host allocations
+    std::unordered_map<const void*, size_t> dev_sizes, pin_sizes;  // every buffer of either kind it owns -> its bytes
     bool use_fused = false;
     bool use_pix = false;          // k_pix + dilating tile CCL (else k_fused dilates itself)
     bool use_small = false;        // the pixel stage as k_small_blur + k_small_scan (small work images)
@@ -168,6 +168,20 @@ struct fm_ctx {
     std::vector<int64_t> ts_n;
     bool serial = false;  // FM_SERIAL: contour pass on the pixel stream (profiling: no overlap)
     int dbg_skip = 0;  // FM_DEBUG_SKIP: profiling-only stage ablation of k_fused (results invalid)
+
+    // Releases everything the context took, also when fm_create gave up half way (nothing was enqueued
+    // on its streams then; fm_destroy synchronises them first).
+    ~fm_ctx() {
+        for (hipStream_t st : ccl_streams)
+            if (st) (void)hipStreamDestroy(st);
+        for (hipStream_t st : {own_stream, aux_stream, rs_stream, rs_stream2})
+            if (st) (void)hipStreamDestroy(st);
+        for (BatchSlot& b : slots)
+            for (hipEvent_t ev : {b.ev_pix, b.ev_done, b.ev_rs, b.ev_lab})
+                if (ev) (void)hipEventDestroy(ev);
+        for (const auto& kv : dev_sizes) (void)hipFree(const_cast<void*>(kv.first));
+        for (const auto& kv : pin_sizes) (void)hipHostFree(const_cast<void*>(kv.first));
+    }
 };
 
 namespace {
@@ -189,123 +203,60 @@ int fail(fm_ctx* c, int code, const char* fmt, ...) {
         if (_e != hipSuccess) return fail(ctx, FM_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-// computeResizeAreaTab (OpenCV imgproc resize.cpp) restated on the product
-// side: for each destination index the weights over consecutive source
-// indices, in the order OpenCV accumulates them.
-}  // namespace
-namespace fm {
-bool build_area_axis(int ssize, int dsize, double scale, AreaAxis& A) {
-    A.n_dst = dsize;
-    std::vector<std::vector<std::pair<int, float>>> taps(dsize);
-    for (int dx = 0; dx < dsize; dx++) {
-        const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-        const double cell = std::min(scale, ssize - fsx1);
-        int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
-        sx2 = std::min(sx2, ssize - 1);
-        sx1 = std::min(sx1, sx2);
-        auto& t = taps[dx];
-        if (sx1 - fsx1 > 1e-3) t.emplace_back(sx1 - 1, (float)((sx1 - fsx1) / cell));
-        for (int sx = sx1; sx < sx2; sx++) t.emplace_back(sx, (float)(1.0 / cell));
-        if (fsx2 - sx2 > 1e-3) t.emplace_back(sx2, (float)(std::min(std::min(fsx2 - sx2, 1.), cell) / cell));
-    }
-    A.max_taps = 1;
-    for (auto& t : taps) A.max_taps = std::max<int>(A.max_taps, (int)t.size());
-    A.ofs.assign(dsize, 0);
-    A.cnt.assign(dsize, 0);
-    A.wt.assign((size_t)dsize * A.max_taps, 0.f);
-    for (int d = 0; d < dsize; d++) {
-        auto& t = taps[d];
-        if (t.empty()) return false;
-        A.ofs[d] = t[0].first;
-        A.cnt[d] = (int)t.size();
-        for (size_t j = 0; j < t.size(); j++) {
-            if (t[j].first != t[0].first + (int)j) return false;  // taps must be consecutive
-            A.wt[(size_t)d * A.max_taps + j] = t[j].second;
-        }
-    }
-    return true;
-}
-}  // namespace fm
-namespace {
-
-// getGaussianKernelBitExact + getGaussianKernelFixedPoint_ED (OpenCV imgproc
-// smooth.dispatch.cpp) restated: the 8-bit fixed-point taps GaussianBlur
-// uses for CV_8U with sigma = 0.
-bool gaussian_taps(int n, std::vector<int32_t>& out) {
-    if (n < 1 || (n & 1) == 0 || n > kMaxK) return false;
-    std::vector<double> kd(n);
-    switch (n) {
-        case 1: kd = {1.0}; break;
-        case 3: kd = {0.25, 0.5, 0.25}; break;
-        case 5: kd = {0.0625, 0.25, 0.375, 0.25, 0.0625}; break;
-        case 7: kd = {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125}; break;
-        case 9: kd = {4 / 256., 13 / 256., 30 / 256., 51 / 256., 60 / 256., 51 / 256., 30 / 256., 13 / 256., 4 / 256.}; break;
-        default: {
-            const double sigma = std::fma((double)n, 0.15, 0.35);
-            const double scale2 = -0.125 / (sigma * sigma);
-            const int half = (n - 1) / 2;
-            std::vector<double> v(half);
-            double sum = 0;
-            for (int i = 0, x = 1 - n; i < half; i++, x += 2) {
-                v[i] = std::exp((double)(x * x) * scale2);
-                sum += v[i];
-            }
-            sum = sum * 2 + 1;
-            for (int i = 0; i < half; i++) kd[i] = kd[n - 1 - i] = v[i] / sum;
-            kd[half] = 1 / sum;
-        }
-    }
-    out.assign(n, 0);
-    const int half = n / 2;
-    double err = 0;
-    int64_t s = 0;
-    for (int i = 0; i < half; i++) {
-        const double adj = kd[i] * 256 + err;
-        const int64_t v0 = (int64_t)std::nearbyint(adj);
-        err = adj - (double)v0;
-        out[i] = out[n - 1 - i] = (int32_t)v0;
-        s += v0;
-    }
-    out[half] = (int32_t)(256 - 2 * s);
-    return true;
-}
-
+// Device and page-locked memory of the context: every allocation is entered in c->dev_sizes /
+// c->pin_sizes (fm_footprint's totals), and ~fm_ctx frees whatever the two still hold.
 template <class T>
 int dalloc(fm_ctx* c, T** p, size_t count) {
     if (count == 0) count = 1;
     hipError_t e = hipMalloc((void**)p, count * sizeof(T));
     if (e != hipSuccess) return fail(c, FM_ENOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
-    if (c) {
-        c->dev_bytes += count * sizeof(T);
-        c->dev_sizes[*p] = count * sizeof(T);
-    }
+    c->dev_bytes += count * sizeof(T);
+    c->dev_sizes[*p] = count * sizeof(T);
     return FM_OK;
 }
 
-// page-locked host memory of the context (counted for fm_footprint)
 template <class T>
 hipError_t halloc(fm_ctx* c, T** p, size_t bytes, unsigned flags) {
     hipError_t e = hipHostMalloc((void**)p, bytes, flags);
-    if (e == hipSuccess) c->pinned_bytes += bytes;
+    if (e == hipSuccess) {
+        c->pinned_bytes += bytes;
+        c->pin_sizes[*p] = bytes;
+    }
     return e;
 }
 
+// At least `want` units in *p, whose capacity *cap counts the same units: a smaller buffer is replaced
+// by one of `count` elements (contents not preserved) and leaves the footprint.
 template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-// a buffer freed while the context lives on (re-grown): its bytes leave the footprint
-template <class T>
-void dfree(fm_ctx* c, T*& p) {
-    if (p) {
-        auto it = c->dev_sizes.find(p);
-        if (it != c->dev_sizes.end()) {
-            c->dev_bytes -= it->second;
-            c->dev_sizes.erase(it);
-        }
+int grow(fm_ctx* c, T** p, size_t* cap, size_t want, size_t count) {
+    if (want <= *cap) return FM_OK;
+    if (auto it = c->dev_sizes.find(*p); it != c->dev_sizes.end()) {
+        (void)hipFree(*p);
+        c->dev_bytes -= it->second;
+        c->dev_sizes.erase(it);
     }
-    dfree(p);
+    *p = nullptr;
+    *cap = 0;
+    if (int rc = dalloc(c, p, count)) return rc;
+    *cap = want;
+    return FM_OK;
+}
+
+// the page-locked counterpart
+template <class T>
+int grow_pinned(fm_ctx* c, T** p, size_t* cap, size_t want, size_t count) {
+    if (want <= *cap) return FM_OK;
+    if (auto it = c->pin_sizes.find(*p); it != c->pin_sizes.end()) {
+        (void)hipHostFree(*p);
+        c->pinned_bytes -= it->second;
+        c->pin_sizes.erase(it);
+    }
+    *p = nullptr;
+    *cap = 0;
+    hipError_t e = halloc(c, p, count * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) return fail(c, FM_ENOMEM, "hipHostMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+    *cap = want;
+    return FM_OK;
 }
 
 int check_idle(fm_ctx* c) {
@@ -313,9 +264,14 @@ int check_idle(fm_ctx* c) {
     return FM_OK;
 }
 
+int check_stream(fm_ctx* c, int stream) {
+    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    return FM_OK;
+}
+
 // results of the last waited batch (device-side ones live until its slot is resubmitted)
 int check_frame(fm_ctx* c, int frame, int stream, bool device_data) {
-    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    if (int rc = check_stream(c, stream)) return rc;
     if (frame < 0 || frame >= c->ready) return fail(c, FM_EINVAL, "frame %d not in the last batch (%d frames)", frame, c->ready);
     if (device_data && (c->ready_slot < 0 || c->slots[c->ready_slot].gen != c->ready_gen))
         return fail(c, FM_ESTATE, "the batch's device results were overwritten by a later submit");
@@ -324,12 +280,7 @@ int check_frame(fm_ctx* c, int frame, int stream, bool device_data) {
 
 // every record of frame f of a finished fused-path batch (count known from k_emit)
 int emit_all(fm_ctx* c, BatchSlot& B, size_t f, int count, std::vector<int32_t>& out) {
-    if ((size_t)count > c->rec_all_cap) {
-        dfree(c, c->d_rec_all);
-        c->rec_all_cap = 0;
-        if (int rc = dalloc(c, &c->d_rec_all, (size_t)count * 5 + 1)) return rc;
-        c->rec_all_cap = (size_t)count;
-    }
+    if (int rc = grow(c, &c->d_rec_all, &c->rec_all_cap, (size_t)count, (size_t)count * 5 + 1)) return rc;
     hipStream_t st = c->aux_stream;
     int32_t* cnt = c->d_rec_all + (size_t)count * 5;
     HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(int32_t), st));
@@ -370,10 +321,7 @@ int relabel_frame(fm_ctx* c, BatchSlot& B, size_t f, std::vector<int32_t>& out, 
             HIP_TRY(c, hipStreamSynchronize(st));
             return FM_OK;
         }
-        dfree(c, c->d_rec_one);
-        c->rec_one_cap = 0;
-        if (int rc = dalloc(c, &c->d_rec_one, (size_t)n * 5)) return rc;
-        c->rec_one_cap = (size_t)n;
+        if (int rc = grow(c, &c->d_rec_one, &c->rec_one_cap, (size_t)n, (size_t)n * 5)) return rc;
     }
     return fail(c, FM_EHIP, "pixel-level relabel of frame %zu did not converge", f);
 }
@@ -390,12 +338,7 @@ int contour_areas(fm_ctx* c, BatchSlot& B, size_t F) {
         }
     const size_t n = jobs.size() / 3;
     if (n == 0) return FM_OK;
-    if (n > c->area_cap) {
-        dfree(c, c->d_area);
-        c->area_cap = 0;
-        if (int rc = dalloc(c, &c->d_area, n * 4)) return rc;
-        c->area_cap = n;
-    }
+    if (int rc = grow(c, &c->d_area, &c->area_cap, n, n * 4)) return rc;
     hipStream_t st = c->aux_stream;
     std::vector<int32_t> a2(n);
     HIP_TRY(c, hipMemcpyAsync(c->d_area, jobs.data(), n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -437,12 +380,7 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
         }
     int32_t* lists = &up[n * 8];
     for (auto& v : path) lists = std::copy(v.begin(), v.end(), lists);
-    if (n > c->trace_cap) {
-        dfree(c, c->d_trace);
-        c->trace_cap = 0;
-        if (int rc = dalloc(c, &c->d_trace, n * 12 + 1)) return rc;
-        c->trace_cap = n;
-    }
+    if (int rc = grow(c, &c->d_trace, &c->trace_cap, n, n * 12 + 1)) return rc;
     int32_t* d_jobs = c->d_trace;
     int32_t* d_res = c->d_trace + n * 9;
     int32_t* d_err = c->d_trace + n * 12;
@@ -477,25 +415,9 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
     c->trace_n[0] = (int32_t)(path[0].size() + path[1].size() + path[2].size());
     c->trace_n[1] = (int32_t)path[3].size();
     // the total is known: size both point buffers before the emit pass touches them
-    if (total > c->cpts_cap) {
-        dfree(c, c->d_cpts);
-        c->cpts_cap = 0;
-        if (int rc = dalloc(c, &c->d_cpts, total * 2)) return rc;
-        c->cpts_cap = total;
-    }
-    if (total > c->h_pts_cap) {
-        if (c->h_pts) {
-            (void)hipHostFree(c->h_pts);
-            c->pinned_bytes -= c->h_pts_cap * 2 * sizeof(int32_t);
-        }
-        c->h_pts = nullptr;
-        c->h_pts_cap = 0;
-        const size_t want = std::max(total, (size_t)4096);
-        hipError_t e = halloc(c, &c->h_pts, want * 2 * sizeof(int32_t), hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, FM_ENOMEM, "hipHostMalloc(%zu bytes): %s", want * 2 * sizeof(int32_t),
-                                         hipGetErrorString(e));
-        c->h_pts_cap = want;
-    }
+    const size_t host_pts = std::max(total, (size_t)4096);
+    if (int rc = grow(c, &c->d_cpts, &c->cpts_cap, total, total * 2)) return rc;
+    if (int rc = grow_pinned(c, &c->h_pts, &c->h_pts_cap, host_pts, host_pts * 2)) return rc;
     ta.pts = c->d_cpts;
     int32_t err = 0;
     HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), n * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -509,152 +431,6 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------------------
-// KernelTimer
-namespace fm {
-int KernelTimer::id_of(const char* name) {
-    for (size_t i = 0; i < names.size(); i++)
-        if (names[i] == name || std::strcmp(names[i], name) == 0) return (int)i;
-    names.push_back(name);
-    ms.push_back(0);
-    ms_sq.push_back(0);
-    stamped.push_back(0);
-    stamped_ms.push_back(0);
-    busy.push_back(Busy{});
-    launches.push_back(0);
-    calls.push_back(0);
-    return (int)names.size() - 1;
-}
-int KernelTimer::begin(const char* name, hipStream_t st) {
-    if (!enabled) return -1;
-    if (!st) st = stream;
-    if (pixel_only && st != stream && st != stream2) return -1;
-    const int id = id_of(name);
-    // events on every launch cost the pipeline ~7% (each record is a barrier packet):
-    // the pixel-only mode times a sample of the launches of the kernels it cannot stamp
-    if (pixel_only && calls[id]++ % kSample != 0) return -1;
-    hipEvent_t a, b;
-    if (pool.size() >= 2) {
-        a = pool.back(); pool.pop_back();
-        b = pool.back(); pool.pop_back();
-    } else {
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -1;
-    }
-    (void)hipEventRecord(a, st);
-    pending.push_back({id, a, b, st});
-    return (int)pending.size() - 1;
-}
-void KernelTimer::end(int token) {
-    if (token < 0 || token >= (int)pending.size()) return;
-    (void)hipEventRecord(pending[token].b, pending[token].st);
-}
-void KernelTimer::collect() {
-    std::vector<Rec> keep;
-    for (auto& r : pending) {
-        if (hipEventQuery(r.b) == hipErrorNotReady) {  // a later batch still running
-            keep.push_back(r);
-            continue;
-        }
-        float t = 0;
-        if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) {
-            ms[r.id] += t;
-            launches[r.id] += 1;
-        }
-        pool.push_back(r.a);
-        pool.push_back(r.b);
-    }
-    pending.swap(keep);
-}
-// Stamped launches (pixel-only mode): the round-4 sampled events opened their window at the marker
-// ahead of the kernel, so it took in the queue's waits, and one launch in four was a biased sample
-// (a sampled mean of 709 us against a 655.5 us step).  Stamps time every launch from its first
-// workgroup's start to its last wave's end.
-uint64_t* KernelTimer::stamp(const char* name) {
-    if (!enabled || !pixel_only) return nullptr;
-    if (!d_stamps) {
-        if (hipMalloc(&d_stamps, sizeof(uint64_t) * 2 * kStampRing) != hipSuccess) {
-            d_stamps = nullptr;
-            enabled = false;
-            return nullptr;
-        }
-        std::vector<uint64_t> init(2 * kStampRing);
-        for (int i = 0; i < kStampRing; i++) init[2 * i] = ~0ull, init[2 * i + 1] = 0;
-        if (hipMemcpy(d_stamps, init.data(), init.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
-            enabled = false;
-            return nullptr;
-        }
-    }
-    const int id = id_of(name);
-    if ((int)stamp_ids.size() >= kStampRing) {
-        unstamped++;
-        return nullptr;
-    }
-    stamp_ids.push_back(id);
-    return d_stamps + 2 * (stamp_ids.size() - 1);
-}
-int KernelTimer::fold_stamps() {
-    if (stamp_ids.empty()) return 0;
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (stream2) (void)hipStreamSynchronize(stream2);
-    if (stream3) (void)hipStreamSynchronize(stream3);
-    for (hipStream_t st : extra) (void)hipStreamSynchronize(st);  // (an entry read while its kernel runs is lost)
-    const size_t n = stamp_ids.size();
-    std::vector<uint64_t> v(2 * n);
-    if (hipMemcpy(v.data(), d_stamps, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    const bool dump = dev_env("FM_STAMP_DUMP") != nullptr;  // dev build: every launch's window to stderr
-    for (size_t i = 0; i < n; i++) {
-        if (dump) std::fprintf(stderr, "kstamp %s %llu %llu\n", names[stamp_ids[i]], (unsigned long long)v[2 * i],
-                               (unsigned long long)v[2 * i + 1]);
-        if (v[2 * i] == ~0ull || v[2 * i + 1] <= v[2 * i]) continue;  // (a kernel that does not stamp)
-        const double t = (double)(v[2 * i + 1] - v[2 * i]) * 1e-5;  // 100 MHz ticks -> ms
-        ms[stamp_ids[i]] += t;
-        ms_sq[stamp_ids[i]] += t * t;
-        stamped[stamp_ids[i]] += 1;
-        stamped_ms[stamp_ids[i]] += t;
-        launches[stamp_ids[i]] += 1;
-    }
-    // the union of each kernel's launch windows (launches of one kernel may overlap: two input streams)
-    std::vector<std::pair<uint64_t, uint64_t>> iv;
-    for (size_t id = 0; id < names.size(); id++) {
-        iv.clear();
-        for (size_t i = 0; i < n; i++)
-            if (stamp_ids[i] == (int)id && v[2 * i] != ~0ull && v[2 * i + 1] > v[2 * i]) iv.emplace_back(v[2 * i], v[2 * i + 1]);
-        std::sort(iv.begin(), iv.end());
-        Busy& b = busy[id];
-        for (const auto& [s0, e0] : iv) {
-            if (b.open && s0 <= b.e) {
-                b.e = std::max(b.e, e0);
-                continue;
-            }
-            if (b.open) b.ms += (double)(b.e - b.s) * 1e-5;
-            b.s = s0, b.e = e0, b.open = true;
-        }
-    }
-    for (size_t i = 0; i < n; i++) v[2 * i] = ~0ull, v[2 * i + 1] = 0;
-    stamp_ids.clear();
-    return hipMemcpy(d_stamps, v.data(), v.size() * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-}
-void KernelTimer::reset() {
-    fold_stamps();  // (launches stamped before the reset are dropped with the sums below)
-    std::fill(ms.begin(), ms.end(), 0.0);
-    std::fill(ms_sq.begin(), ms_sq.end(), 0.0);
-    std::fill(stamped.begin(), stamped.end(), 0);
-    std::fill(stamped_ms.begin(), stamped_ms.end(), 0.0);
-    std::fill(busy.begin(), busy.end(), Busy{});
-    std::fill(launches.begin(), launches.end(), 0);
-    std::fill(calls.begin(), calls.end(), 0);
-    unstamped = 0;
-}
-KernelTimer::~KernelTimer() {
-    if (d_stamps) (void)hipFree(d_stamps);
-    for (auto& r : pending) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    for (auto e : pool) (void)hipEventDestroy(e);
-}
-}  // namespace fm
 
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -832,10 +608,8 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         }
         b.ccl_stream = c->ccl_streams[i % c->nccl];
         if (i < c->nccl) c->timer.extra.push_back(b.ccl_stream);  // fold_stamps waits for it too
-        HIP_TRY(cp, hipEventCreateWithFlags(&b.ev_pix, hipEventDisableTiming));
-        HIP_TRY(cp, hipEventCreateWithFlags(&b.ev_done, hipEventDisableTiming));
-        HIP_TRY(cp, hipEventCreateWithFlags(&b.ev_rs, hipEventDisableTiming));
-        HIP_TRY(cp, hipEventCreateWithFlags(&b.ev_lab, hipEventDisableTiming));
+        for (hipEvent_t* ev : {&b.ev_pix, &b.ev_done, &b.ev_rs, &b.ev_lab})
+            HIP_TRY(cp, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     }
     // pixel-level CCL: the whole batch on the v1 path, one frame for the fused path's overflow fallback
     const size_t ccl_px = c->use_fused ? c->work_plane : px;
@@ -899,43 +673,18 @@ void fm_destroy(fm_ctx* c) {
                 std::fclose(fh);
             }
         }
-        dfree(c->d_pts);
     }
     if (c->d_ts) {
         std::fprintf(stderr, "[fm] contour-pass phase cycles (mean per labelled tile):");
         for (int k = 2; k < 16; k++)
             if (c->ts_n[k]) std::fprintf(stderr, " %d:%.0f(n=%lld)", k, c->ts_sum[k] / c->ts_n[k], (long long)c->ts_n[k]);
         std::fprintf(stderr, "\n");
-        dfree(c->d_ts);
     }
     (void)hipSetDevice(c->p.device);
     for (hipStream_t st : {c->own_stream, c->stream, c->aux_stream, c->rs_stream, c->rs_stream2})
         if (st) (void)hipStreamSynchronize(st);
-    for (hipStream_t& st : c->ccl_streams)
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-            st = nullptr;
-        }
-    for (auto& b : c->slots) {
-        dfree(b.d_in); dfree(b.d_yuv); dfree(b.d_ytab); dfree(b.d_work); dfree(b.d_planes); dfree(b.d_bits); dfree(b.d_dbits); dfree(b.d_tiles); dfree(b.d_sblur);
-        dfree(b.d_nodes); dfree(b.d_heavy); dfree(b.d_count); dfree(b.d_tflag); dfree(b.d_candf);
-        dfree(b.d_clist); dfree(b.d_rlist); dfree(b.d_regrep); dfree(b.d_ncr);
-        for (auto* hp : {(void*)b.h_count, (void*)b.h_overflow, (void*)b.h_rec, (void*)b.h_init, (void*)b.h_stats, (void*)b.h_ytab})
-            if (hp) (void)hipHostFree(hp);
-        if (b.ev_pix) (void)hipEventDestroy(b.ev_pix);
-        if (b.ev_done) (void)hipEventDestroy(b.ev_done);
-        if (b.ev_rs) (void)hipEventDestroy(b.ev_rs);
-        if (b.ev_lab) (void)hipEventDestroy(b.ev_lab);
-    }
-    dfree(c->d_bg[0]); dfree(c->d_bg[1]); dfree(c->d_keep); dfree(c->d_has_keep); dfree(c->d_init); dfree(c->d_mask);
-    dfree(c->d_label); dfree(c->d_cid); dfree(c->d_outer); dfree(c->d_rec_dev); dfree(c->d_rec_one); dfree(c->d_rec_all); dfree(c->d_area);
-    dfree(c->d_trace); dfree(c->d_cpts);
-    if (c->h_pts) (void)hipHostFree(c->h_pts);
-    dfree(c->d_xofs); dfree(c->d_xcnt); dfree(c->d_xwt); dfree(c->d_yofs); dfree(c->d_ycnt); dfree(c->d_ywt);
-    for (hipStream_t st : {c->own_stream, c->aux_stream, c->rs_stream, c->rs_stream2})
-        if (st) (void)hipStreamDestroy(st);
-    if (c->h_err) (void)hipHostFree(c->h_err);
+    for (hipStream_t st : c->ccl_streams)
+        if (st) (void)hipStreamSynchronize(st);
     delete c;
 }
 
@@ -965,7 +714,7 @@ int fm_work_size(const fm_ctx* c, int* h, int* w) {
 int fm_set_mask(fm_ctx* c, int stream, const uint8_t* keep) {
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     if (int rc = check_idle(c)) return rc;
-    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    if (int rc = check_stream(c, stream)) return rc;
     HIP_TRY(c, hipSetDevice(c->p.device));
     const uint8_t flag = keep ? 1 : 0;
     if (keep)
@@ -980,7 +729,7 @@ int fm_set_mask(fm_ctx* c, int stream, const uint8_t* keep) {
 int fm_reset_stream(fm_ctx* c, int stream) {
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     if (int rc = check_idle(c)) return rc;
-    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    if (int rc = check_stream(c, stream)) return rc;
     c->bg_init[stream] = 0;
     return FM_OK;
 }
@@ -993,42 +742,29 @@ int fm_set_hip_stream(fm_ctx* c, void* s) {
     return FM_OK;
 }
 
-// fm_submit / fm_submit_jpeg: frames from host memory (copied), device memory, or JPEGs decoded
-// on the input stream into the batch's device buffer (dec != nullptr)
-// (yuv: a validated fm_submit_yuv / fm_submit_yuv_list batch, converted into the slot's input buffer)
+// One batch's input as the five fm_submit* entry points describe it after their own validation.
 namespace {
 struct YuvSrc {
     int format, pitch;
     size_t chroma_offset, extent, stride;  // stride: bytes between frames (contiguous source)
-    const uint8_t* const* list;            // F device addresses (host array), or nullptr
 };
-}  // namespace
-static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, fm_mjpeg* dec,
-                       const uint8_t* const* jpegs, const size_t* sizes, const uint8_t* const* per_stream = nullptr,
-                       const YuvSrc* yuv = nullptr) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if ((int)c->inflight.size() >= c->nslots)
-        return fail(c, FM_ESTATE, "%d batch(es) already in flight: call fm_wait first", (int)c->inflight.size());
-    if (per_stream) {
-        for (int s = 0; s < c->p.n_streams; s++)
-            if (!per_stream[s]) return fail(c, FM_EINVAL, "null frames for stream %d", s);
-        if (on_device && c->p.n_streams == 1) {  // one stream: [n][1] is the contiguous layout, read in place
-            frames = per_stream[0];
-            per_stream = nullptr;
-        }
-    }
-    if ((!frames && !dec && !per_stream && !(yuv && yuv->list)) || n < 1 || n > c->p.max_batch)
-        return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d] or null frames", n, c->p.max_batch);
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int si = c->next_slot;
-    BatchSlot& B = c->slots[si];
-    const int S = c->p.n_streams;
-    const size_t F = (size_t)n * S;
-    hipStream_t ps = c->stream;  // pixel stream: pixel kernel (bg recurrence is ordered here)
-    // input copy and resize: on their own stream when there is a resize, so batch i+1's
-    // resize (many workgroups, HBM-bound) overlaps batch i's pixel kernel (few, when the
-    // work image is small); the pixel stream waits for it below
-    hipStream_t rs = c->rs_stream ? c->rs_stream : ps;
+enum class InputKind { Bgr, BgrStreams, Jpeg, Yuv, YuvList };
+struct BatchInput {
+    InputKind kind;
+    int n;                       // frames per stream
+    bool on_device;              // Bgr, BgrStreams, Yuv: the addresses are device memory (else host memory, copied)
+    const uint8_t* frames;       // Bgr, Yuv: the batch's frames [n][S], contiguous
+    const uint8_t* const* ptrs;  // BgrStreams: S streams' frames; Jpeg: n * S JPEGs; YuvList: n * S device addresses
+    fm_mjpeg* dec;               // Jpeg: the decoder
+    const size_t* sizes;         // and each JPEG's bytes
+    YuvSrc yuv;                  // Yuv, YuvList: the resolved layout
+};
+
+// The stream the batch's input copies, conversion and resize run on: their own stream when there is
+// a resize, so batch i+1's resize (many workgroups, HBM-bound) overlaps batch i's pixel kernel (few,
+// when the work image is small); the pixel stream waits for it (submit).
+int pick_input_stream(fm_ctx* c, const BatchInput& in, int si, hipStream_t* rs) {
+    *rs = c->rs_stream ? c->rs_stream : c->stream;
 #ifndef FM_RS_TWO
 #define FM_RS_TWO 1
 #endif
@@ -1036,98 +772,321 @@ static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, f
     // waited for the previous one's last wave and then its own dispatch (6-19 us a batch in mode D), on two the
     // next one's workgroups fill the previous one's tail.  Each batch's resize writes its own slot's buffer, and
     // the pixel stream waits for its batch's event, so the order of the batches is unchanged.
-    if (FM_RS_TWO && c->rs_stream && !dec && c->rmode != ResizeMode::Identity && (si & 1)) {
+    if (FM_RS_TWO && c->rs_stream && in.kind != InputKind::Jpeg && c->rmode != ResizeMode::Identity && (si & 1)) {
         if (!c->rs_stream2) {
             HIP_TRY(c, hipStreamCreateWithFlags(&c->rs_stream2, hipStreamNonBlocking));
             c->timer.stream3 = c->rs_stream2;
         }
-        rs = c->rs_stream2;
+        *rs = c->rs_stream2;
     }
-    const uint8_t* src = frames;
-    if (dec) {  // the decode side (§8(f)-3): JPEGs -> BGR frames in the batch's device buffer
-        if (!B.d_in) {
-            int rc = dalloc(c, &B.d_in, (size_t)c->p.max_batch * S * c->src_frame_bytes);
-            if (rc) return rc;
+    return FM_OK;
+}
+
+// the slot's BGR input buffer [max_batch][S][H][W][3], allocated by the first batch that is staged into it
+int ensure_input_buffer(fm_ctx* c, BatchSlot& B) {
+    if (B.d_in) return FM_OK;
+    return dalloc(c, &B.d_in, (size_t)c->p.max_batch * c->p.n_streams * c->src_frame_bytes);
+}
+
+// YUV frames -> BGR frames in B.d_in, on the input stream
+int stage_yuv(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, size_t F) {
+    const YuvSrc& y = in.yuv;
+    const size_t cap = (size_t)c->p.max_batch * c->p.n_streams;
+    YuvArgs ya{};
+    ya.src = in.frames;
+    if (in.kind == InputKind::YuvList) {
+        if (!B.d_ytab)
+            if (int rc = dalloc(c, &B.d_ytab, cap)) return rc;
+        if (!B.h_ytab) HIP_TRY(c, halloc(c, &B.h_ytab, cap * sizeof(uint8_t*), hipHostMallocDefault));
+        std::copy(in.ptrs, in.ptrs + F, B.h_ytab);  // (the slot is idle: its last batch was waited for)
+        HIP_TRY(c, hipMemcpyAsync(B.d_ytab, B.h_ytab, F * sizeof(uint8_t*), hipMemcpyHostToDevice, rs));
+        ya.srcs = B.d_ytab;
+    } else if (!in.on_device) {
+        const size_t bytes = (F - 1) * y.stride + y.extent;
+        if (bytes > B.yuv_cap) {  // first use, or a larger layout than the slot has seen: room for a full batch of it
+            const size_t want = std::max(bytes, (cap - 1) * y.stride + y.extent);
+            if (int rc = grow(c, &B.d_yuv, &B.yuv_cap, want, want)) return rc;
         }
-        const int rc = fm_mjpeg_enqueue(dec, jpegs, sizes, (int)F, B.d_in, rs);
-        HIP_TRY(c, hipSetDevice(c->p.device));
-        if (rc) return fail(c, rc, "JPEG decode: %s", fm_mjpeg_last_error(dec));
-        src = B.d_in;
-        on_device = 0;  // (the input stream ran: the pixel stream waits for it below)
-    } else if (yuv) {  // YUV frames -> BGR frames in the batch's device buffer, on the input stream
-        int rc;
-        if (!B.d_in && (rc = dalloc(c, &B.d_in, (size_t)c->p.max_batch * S * c->src_frame_bytes))) return rc;
-        YuvArgs ya{};
-        ya.src = frames;
-        if (yuv->list) {
-            const size_t cap = (size_t)c->p.max_batch * S;
-            if (!B.d_ytab && (rc = dalloc(c, &B.d_ytab, cap))) return rc;
-            if (!B.h_ytab) HIP_TRY(c, halloc(c, &B.h_ytab, cap * sizeof(uint8_t*), hipHostMallocDefault));
-            std::copy(yuv->list, yuv->list + F, B.h_ytab);  // (the slot is idle: its last batch was waited for)
-            HIP_TRY(c, hipMemcpyAsync(B.d_ytab, B.h_ytab, F * sizeof(uint8_t*), hipMemcpyHostToDevice, rs));
-            ya.srcs = B.d_ytab;
-        } else if (!on_device) {
-            const size_t bytes = (F - 1) * yuv->stride + yuv->extent;
-            if (bytes > B.yuv_cap) {  // first use, or a larger layout than the slot has seen
-                const size_t want = std::max(bytes, ((size_t)c->p.max_batch * S - 1) * yuv->stride + yuv->extent);
-                dfree(c, B.d_yuv);
-                B.yuv_cap = 0;
-                if ((rc = dalloc(c, &B.d_yuv, want))) return rc;
-                B.yuv_cap = want;
+        HIP_TRY(c, hipMemcpyAsync(B.d_yuv, in.frames, bytes, hipMemcpyHostToDevice, rs));
+        ya.src = B.d_yuv;
+    }
+    ya.frame_stride = y.stride;
+    ya.chroma_offset = y.chroma_offset;
+    ya.dst = B.d_in;
+    ya.format = y.format;
+    ya.pitch = y.pitch;
+    ya.W = c->p.src_w;
+    ya.H = c->p.src_h;
+    ya.F = (int)F;
+    HIP_TRY(c, c->timer.timed(rs, "yuv2bgr", [&](uint64_t* ks, uint64_t*) {
+        ya.kstamp = ks;
+        return launch_yuv2bgr(rs, ya);
+    }));
+    return FM_OK;
+}
+
+// The batch's BGR frames [n][S][H][W][3] on the device: *src is the caller's device memory, read in
+// place (*staged false: nothing was enqueued), or B.d_in, filled on the input stream rs (*staged true).
+int stage_input(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, const uint8_t** src, bool* staged) {
+    *staged = !(in.kind == InputKind::Bgr && in.on_device);
+    *src = in.frames;
+    if (!*staged) return FM_OK;
+    if (int rc = ensure_input_buffer(c, B)) return rc;
+    *src = B.d_in;
+    const int S = c->p.n_streams;
+    const size_t F = (size_t)in.n * S, fb = c->src_frame_bytes;
+    switch (in.kind) {
+        case InputKind::Bgr:
+            HIP_TRY(c, hipMemcpyAsync(B.d_in, in.frames, F * fb, hipMemcpyHostToDevice, rs));
+            break;
+        case InputKind::BgrStreams:  // stream s's frames -> rows s, S + s, 2S + s, ... of the [t][s] batch layout
+            for (int s = 0; s < S; s++)
+                HIP_TRY(c, hipMemcpy2DAsync(B.d_in + (size_t)s * fb, (size_t)S * fb, in.ptrs[s], fb, fb, (size_t)in.n,
+                                            in.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, rs));
+            break;
+        case InputKind::Jpeg: {  // the decode side (§8(f)-3): JPEGs -> BGR frames in the batch's device buffer
+            const int rc = fm_mjpeg_enqueue(in.dec, in.ptrs, in.sizes, (int)F, B.d_in, rs);
+            HIP_TRY(c, hipSetDevice(c->p.device));
+            if (rc) return fail(c, rc, "JPEG decode: %s", fm_mjpeg_last_error(in.dec));
+            break;
+        }
+        case InputKind::Yuv:
+        case InputKind::YuvList:
+            return stage_yuv(c, B, in, rs, F);
+    }
+    return FM_OK;
+}
+
+// INTER_AREA on the input stream: *work is the work-size batch [n][S][h][w][3] (src itself without a resize)
+int resize_input(fm_ctx* c, BatchSlot& B, hipStream_t rs, const uint8_t* src, size_t F, const uint8_t** work) {
+    *work = c->rmode == ResizeMode::Identity ? src : B.d_work;
+    if (c->rmode == ResizeMode::General)
+        HIP_TRY(c, c->timer.timed(rs, "resize_area", [&](uint64_t* ks, uint64_t*) {
+            return launch_resize_area(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->d_xofs, c->d_xcnt,
+                                      c->d_xwt, c->ax.max_taps, c->d_yofs, c->d_ycnt, c->d_ywt, c->ay.max_taps, nullptr, ks);
+        }));
+    else if (c->rmode == ResizeMode::Fast)
+        HIP_TRY(c, c->timer.timed(rs, "resize_area_fast", [&](uint64_t* ks, uint64_t*) {
+            return launch_resize_area_fast(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->fast_sx,
+                                           c->fast_sy, ks);
+        }));
+    return FM_OK;
+}
+
+// the fused paths' arguments for n frames per stream of the work-size batch `work` in slot B
+FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool any_init) {
+    const int S = c->p.n_streams;
+    const long long npx = (long long)c->work_plane;
+    FusedArgs fa{};
+    fa.src = work;
+    fa.bg_in = c->d_bg[c->bg_cur];
+    fa.bg_out = c->d_bg[c->bg_cur ^ 1];
+    fa.keep = c->d_keep;
+    fa.has_keep = c->d_has_keep;
+    fa.init = any_init ? c->d_init : nullptr;
+    fa.mask_out = nullptr;
+    fa.planes = B.d_planes;
+    fa.bits = B.d_bits;
+    fa.dbits = B.d_dbits;
+    fa.tiles = B.d_tiles;
+    fa.tflag = B.d_tflag;
+    fa.tflag_waves = c->use_pix ? 8 : 1;
+    fa.candf = B.d_candf;
+    fa.clist = B.d_clist;
+    fa.rlist = B.d_rlist;
+    fa.regrep = B.d_regrep;
+    fa.ncr = B.d_ncr;
+    fa.nodes = B.d_nodes;
+    fa.count = B.d_count;
+    fa.heavy = B.d_heavy;
+    fa.rec = B.d_rec;
+    fa.h_count = B.dh_count;
+    fa.h_overflow = B.dh_overflow;
+    fa.T = n;
+    fa.S = S;
+    fa.h = c->h;
+    fa.w = c->w;
+    fa.ksize = c->p.ksize;
+    fa.thresh = c->p.threshold;
+    fa.ntx = c->ntx;
+    fa.nty = c->nty;
+    fa.ntiles = c->ntiles;
+    fa.nnodes = c->nnodes;
+    fa.nquota = c->nquota;
+    fa.h_stats = B.dh_stats;
+    fa.cap = c->rec_cap;
+    fa.cvt_simd = npx >= 16;
+    fa.alpha = c->p.avg;
+    fa.beta = 1.0 - c->p.avg;
+    fa.acc_vec_end = npx - npx % 16;
+    fa.any_keep = std::any_of(c->has_keep.begin(), c->has_keep.end(), [](uint8_t k) { return k != 0; }) ? 1 : 0;
+    fa.dbg_skip = c->dbg_skip;
+    fa.dbg_ts = c->d_ts;
+    fa.dbg_pts = c->d_pts ? c->d_pts + (size_t)(c->pts_launches++ % c->pts_ring) * S * c->ntiles * 36 : nullptr;
+    fa.dbg_err = c->dh_err;
+    for (int i = 0; i < c->p.ksize; i++) fa.coef[i] = c->coef[i];
+    fa.t_begin = 0;
+    fa.t_end = n;
+    return fa;
+}
+
+// The batch's pixel kernels on the pixel stream (the background recurrence is ordered here).  The counters
+// are zeroed by k_pix (k_regions on the k_fused path), the tile flags cleared by k_counts.
+int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
+    hipStream_t ps = c->stream;
+    const int n = fa.T;
+    if (c->d_ts) HIP_TRY(c, hipMemsetAsync(c->d_ts, 0, (size_t)n * fa.S * c->ntiles * 16 * sizeof(uint64_t), ps));
+    if (!c->use_pix) {
+        HIP_TRY(c, launch_fused(ps, fa, &c->timer));
+        c->bg_cur ^= 1;
+        return FM_OK;
+    }
+    const bool planes = B.d_planes != nullptr;
+    // each launch reads d_bg[cur] and writes d_bg[cur ^ 1]
+    auto run = [&](int t0, int t1, bool init, const char* name) -> int {
+        FusedArgs fp = fa;
+        fp.t_begin = t0;
+        fp.t_end = t1;
+        fp.bg_in = c->d_bg[c->bg_cur];
+        fp.bg_out = c->d_bg[c->bg_cur ^ 1];
+        if (!init) fp.init = nullptr;
+        if (c->use_small)  // not stamping (FM_FLAG_PROFILE, or the stamp ring full): the pair timed by events
+            HIP_TRY(c, c->timer.timed(ps, init ? "small_blur_init" : "small_blur", [&](uint64_t* k1, uint64_t* k2) {
+                return launch_small(ps, fp, B.d_sblur, k1, k2);
+            }, true, init ? "small_scan_init" : "small_scan", init ? "small_init" : "small"));
+        else
+            HIP_TRY(c, c->timer.timed(ps, name, [&](uint64_t* ks, uint64_t*) {
+                fp.kstamp = ks;
+                return launch_pix(ps, fp, planes, init);
+            }));
+        c->bg_cur ^= 1;
+        return FM_OK;
+    };
+    if (any_init) {  // first frames in their own launch: the steady-state kernel has no init select
+        if (int rc = run(0, 1, true, "pix_init")) return rc;
+        return n > 1 ? run(1, n, false, "pix") : FM_OK;
+    }
+    return run(0, n, false, "pix");
+}
+
+// The batch's contour pass on its slot's stream, after its pixel kernels; counts land in the mapped
+// h_count / h_overflow.
+// Consecutive batches on different contour streams: with 4 slots on 3 streams a fixed
+// slot -> stream map put every fourth pair of consecutive chains on one stream, one after
+// the other (the last batch's chain waited ≈130 µs for its predecessor's)
+// (Batches taking the contour streams in turn instead of the fixed slot map: +2 % on one box,
+// equal on another with 8 % longer pixel launches, round 3.)
+int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
+    hipStream_t ps = c->stream, cs = c->serial ? ps : B.ccl_stream;
+    const size_t F = (size_t)fa.T * fa.S;
+    HIP_TRY(c, hipEventRecord(B.ev_pix, ps));
+    HIP_TRY(c, hipStreamWaitEvent(cs, B.ev_pix, 0));
+    if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
+        FusedArgs fc = fa;
+        // stamped by the dev build only; FM_FLAG_PROFILE: events around it (a contour stream: never in the pixel-only mode)
+        HIP_TRY(c, c->timer.timed(cs, "frame_contours", [&](uint64_t* ks, uint64_t*) {
+            fc.kstamp = ks;
+            // the slot-wide words (shared pool, heavy tally, frames done) sit at indices that depend on the batch's
+            // frame count; the last workgroup re-arms them for a batch of the same size, so a slot whose batch size
+            // changed (a stream's last, partial batch) zeroes them at the new indices first
+            if (B.ccl_F != F) {
+                hipError_t e = hipMemsetAsync(B.d_count + 2 * F, 0, 2 * sizeof(int32_t), cs);
+                if (e == hipSuccess) e = hipMemsetAsync(B.d_count + 3 * F + 2, 0, sizeof(int32_t), cs);
+                if (e != hipSuccess) return e;
+                B.ccl_F = F;
             }
-            HIP_TRY(c, hipMemcpyAsync(B.d_yuv, frames, bytes, hipMemcpyHostToDevice, rs));
-            ya.src = B.d_yuv;
+            return launch_frame_contours(cs, fc, c->use_pix);
+        }, kDevSwitches));
+    } else {
+        // the labelling gate: one batch's labelling kernel at a time (the previous batch's, on another contour
+        // stream, is waited for), so the labelling of consecutive chains never bunches beside a pixel launch
+        // (+1.5 %, 388.1 vs 382.3 k, 4 alternating rounds, round 3)
+        hipEvent_t gate_wait = nullptr;
+        if (!c->serial && c->lab_prev >= 0 && c->lab_prev != si) gate_wait = c->slots[c->lab_prev].ev_lab;
+        HIP_TRY(c, launch_tile_ccl(cs, fa, c->use_pix, &c->timer, gate_wait, B.ev_lab));
+        c->lab_prev = si;
+    }
+    B.fa = fa;
+    HIP_TRY(c, hipEventRecord(B.ev_done, cs));
+    return FM_OK;
+}
+
+// the per-frame (v1) path: one pixel launch per batch step and the pixel-level CCL, all on the pixel stream
+int run_per_frame(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool any_init) {
+    hipStream_t ps = c->stream;
+    const int S = c->p.n_streams;
+    const size_t F = (size_t)n * S;
+    const long long npx = (long long)c->work_plane;
+    HIP_TRY(c, hipMemsetAsync(B.d_count, 0, (2 * F + 1) * sizeof(int32_t), ps));
+    PixelArgs a{};
+    a.bg = nullptr;
+    a.keep = c->d_keep;
+    a.has_keep = c->d_has_keep;
+    a.S = S;
+    a.h = c->h;
+    a.w = c->w;
+    a.ksize = c->p.ksize;
+    a.thresh = c->p.threshold;
+    a.alpha = c->p.avg;
+    a.beta = 1.0 - c->p.avg;
+    a.acc_vec_end = npx - npx % 16;
+    a.cvt_simd = npx >= 16;
+    for (int i = 0; i < c->p.ksize; i++) a.coef[i] = c->coef[i];
+    const size_t step_px = (size_t)S * c->work_plane;
+    for (int t = 0; t < n; t++) {
+        a.src = work + (size_t)t * step_px * 3;  // work image is [T][S][h][w][3] in every resize mode
+        a.init = (t == 0 && any_init) ? c->d_init : nullptr;
+        a.mask_out = c->d_mask + (size_t)t * step_px;
+        if (B.d_planes) {
+            a.gray_out = B.d_planes + (size_t)t * step_px;
+            a.blur_out = B.d_planes + F * c->work_plane + (size_t)t * step_px;
+            a.delta_out = B.d_planes + 2 * F * c->work_plane + (size_t)t * step_px;
         }
-        ya.frame_stride = yuv->stride;
-        ya.chroma_offset = yuv->chroma_offset;
-        ya.dst = B.d_in;
-        ya.format = yuv->format;
-        ya.pitch = yuv->pitch;
-        ya.W = c->p.src_w;
-        ya.H = c->p.src_h;
-        ya.F = (int)F;
-        ya.kstamp = c->timer.stamp("yuv2bgr");
-        const int tok = ya.kstamp ? -1 : c->timer.begin("yuv2bgr", rs);
-        HIP_TRY(c, launch_yuv2bgr(rs, ya));
-        c->timer.end(tok);
-        src = B.d_in;
-        on_device = 0;  // (the input stream ran: the pixel stream waits for it below)
-    } else if (per_stream) {  // stream s's frames -> rows s, S + s, 2S + s, ... of the [t][s] batch layout
-        if (!B.d_in) {
-            int rc = dalloc(c, &B.d_in, (size_t)c->p.max_batch * S * c->src_frame_bytes);
-            if (rc) return rc;
-        }
-        const size_t fb = c->src_frame_bytes;
+        HIP_TRY(c, c->timer.timed(ps, "pixel", [&](uint64_t*, uint64_t*) {
+            return launch_pixel_pp(ps, a, c->d_bg[c->bg_cur], c->d_bg[c->bg_cur ^ 1]);
+        }, false));
+        c->bg_cur ^= 1;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->d_outer, 0, F * c->work_plane, ps));
+    CclArgs ca{c->d_mask, c->d_label, c->d_outer, c->d_cid, B.d_count, c->d_rec_dev, (int)F, c->h, c->w, c->p.max_contours};
+    HIP_TRY(c, launch_ccl(ps, ca, &c->timer));
+    HIP_TRY(c, hipMemcpyAsync(B.h_rec, c->d_rec_dev, F * c->p.max_contours * 5 * sizeof(int32_t), hipMemcpyDeviceToHost,
+                              ps));
+    HIP_TRY(c, hipMemsetAsync(B.d_count + F, 0, F * sizeof(int32_t), ps));
+    HIP_TRY(c, hipMemcpyAsync(B.h_overflow, B.d_count + F, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
+    HIP_TRY(c, hipMemcpyAsync(B.h_count, B.d_count, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
+    HIP_TRY(c, hipEventRecord(B.ev_done, ps));
+    return FM_OK;
+}
+
+// One batch into the next slot: its input staged and resized on an input stream, the pixel kernels on the
+// pixel stream, the contour pass on the slot's stream.  fm_wait takes the slots in submission order.
+int submit(fm_ctx* c, BatchInput in) {
+    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if ((int)c->inflight.size() >= c->nslots)
+        return fail(c, FM_ESTATE, "%d batch(es) already in flight: call fm_wait first", (int)c->inflight.size());
+    const int S = c->p.n_streams, n = in.n;
+    if (in.kind == InputKind::BgrStreams) {
         for (int s = 0; s < S; s++)
-            HIP_TRY(c, hipMemcpy2DAsync(B.d_in + (size_t)s * fb, (size_t)S * fb, per_stream[s], fb, fb, (size_t)n,
-                                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, rs));
-        src = B.d_in;
-        on_device = 0;
-    } else if (!on_device) {
-        if (!B.d_in) {
-            int rc = dalloc(c, &B.d_in, (size_t)c->p.max_batch * S * c->src_frame_bytes);
-            if (rc) return rc;
+            if (!in.ptrs[s]) return fail(c, FM_EINVAL, "null frames for stream %d", s);
+        if (in.on_device && S == 1) {  // one stream: [n][1] is the contiguous layout, read in place
+            in.kind = InputKind::Bgr;
+            in.frames = in.ptrs[0];
         }
-        HIP_TRY(c, hipMemcpyAsync(B.d_in, frames, F * c->src_frame_bytes, hipMemcpyHostToDevice, rs));
-        src = B.d_in;
     }
-    const uint8_t* work = src;
-    if (c->rmode == ResizeMode::General) {
-        uint64_t* ks = c->timer.stamp("resize_area");
-        int tok = ks ? -1 : c->timer.begin("resize_area", rs);
-        HIP_TRY(c, launch_resize_area(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->d_xofs, c->d_xcnt,
-                                      c->d_xwt, c->ax.max_taps, c->d_yofs, c->d_ycnt, c->d_ywt, c->ay.max_taps, nullptr, ks));
-        c->timer.end(tok);
-        work = B.d_work;
-    } else if (c->rmode == ResizeMode::Fast) {
-        uint64_t* ks = c->timer.stamp("resize_area_fast");
-        int tok = ks ? -1 : c->timer.begin("resize_area_fast", rs);
-        HIP_TRY(c, launch_resize_area_fast(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->fast_sx,
-                                           c->fast_sy, ks));
-        c->timer.end(tok);
-        work = B.d_work;
-    }
-    if (rs != ps && (!on_device || c->rmode != ResizeMode::Identity)) {  // something ran on the input stream
+    if ((in.kind == InputKind::Bgr && !in.frames) || n < 1 || n > c->p.max_batch)
+        return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d] or null frames", n, c->p.max_batch);
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const int si = c->next_slot;
+    BatchSlot& B = c->slots[si];
+    hipStream_t ps = c->stream, rs = nullptr;
+    const uint8_t *src = nullptr, *work = nullptr;
+    bool staged = false;
+    int rc;
+    if ((rc = pick_input_stream(c, in, si, &rs)) || (rc = stage_input(c, B, in, rs, &src, &staged)) ||
+        (rc = resize_input(c, B, rs, src, (size_t)n * S, &work)))
+        return rc;
+    if (rs != ps && (staged || c->rmode != ResizeMode::Identity)) {  // something ran on the input stream
         HIP_TRY(c, hipEventRecord(B.ev_rs, rs));
         HIP_TRY(c, hipStreamWaitEvent(ps, B.ev_rs, 0));
     }
@@ -1137,175 +1096,11 @@ static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, f
         any_init |= B.h_init[s] != 0;
     }
     if (any_init) HIP_TRY(c, hipMemcpyAsync(c->d_init, B.h_init, S, hipMemcpyHostToDevice, ps));
-
-    const long long npx = (long long)c->work_plane;
-    // fused path: counters zeroed by k_pix (k_regions on the k_fused path), tile flags cleared by k_counts
-    if (!c->use_fused) HIP_TRY(c, hipMemsetAsync(B.d_count, 0, (2 * F + 1) * sizeof(int32_t), ps));
     if (c->use_fused) {
-        FusedArgs fa{};
-        fa.src = work;
-        fa.bg_in = c->d_bg[c->bg_cur];
-        fa.bg_out = c->d_bg[c->bg_cur ^ 1];
-        fa.keep = c->d_keep;
-        fa.has_keep = c->d_has_keep;
-        fa.init = any_init ? c->d_init : nullptr;
-        fa.mask_out = nullptr;
-        fa.planes = B.d_planes;
-        fa.bits = B.d_bits;
-        fa.dbits = B.d_dbits;
-        fa.tiles = B.d_tiles;
-        fa.tflag = B.d_tflag;
-        fa.tflag_waves = c->use_pix ? 8 : 1;
-        fa.candf = B.d_candf;
-        fa.clist = B.d_clist;
-        fa.rlist = B.d_rlist;
-        fa.regrep = B.d_regrep;
-        fa.ncr = B.d_ncr;
-        fa.nodes = B.d_nodes;
-        fa.count = B.d_count;
-        fa.heavy = B.d_heavy;
-        fa.rec = B.d_rec;
-        fa.h_count = B.dh_count;
-        fa.h_overflow = B.dh_overflow;
-        fa.T = n;
-        fa.S = S;
-        fa.h = c->h;
-        fa.w = c->w;
-        fa.ksize = c->p.ksize;
-        fa.thresh = c->p.threshold;
-        fa.ntx = c->ntx;
-        fa.nty = c->nty;
-        fa.ntiles = c->ntiles;
-        fa.nnodes = c->nnodes;
-        fa.nquota = c->nquota;
-        fa.h_stats = B.dh_stats;
-        fa.cap = c->rec_cap;
-        fa.cvt_simd = npx >= 16;
-        fa.alpha = c->p.avg;
-        fa.beta = 1.0 - c->p.avg;
-        fa.acc_vec_end = npx - npx % 16;
-        fa.any_keep = std::any_of(c->has_keep.begin(), c->has_keep.end(), [](uint8_t k) { return k != 0; }) ? 1 : 0;
-        fa.dbg_skip = c->dbg_skip;
-        fa.dbg_ts = c->d_ts;
-        fa.dbg_pts = c->d_pts ? c->d_pts + (size_t)(c->pts_launches++ % c->pts_ring) * S * c->ntiles * 36 : nullptr;
-        fa.dbg_err = c->dh_err;
-        if (c->d_ts) HIP_TRY(c, hipMemsetAsync(c->d_ts, 0, F * c->ntiles * 16 * sizeof(uint64_t), ps));
-        for (int i = 0; i < c->p.ksize; i++) fa.coef[i] = c->coef[i];
-        fa.t_begin = 0;
-        fa.t_end = n;
-        if (c->use_pix) {
-            const bool planes = B.d_planes != nullptr;
-            // each launch reads d_bg[cur] and writes d_bg[cur ^ 1]
-            auto run = [&](int t0, int t1, bool init, const char* name) -> int {
-                FusedArgs fp = fa;
-                fp.t_begin = t0;
-                fp.t_end = t1;
-                fp.bg_in = c->d_bg[c->bg_cur];
-                fp.bg_out = c->d_bg[c->bg_cur ^ 1];
-                if (!init) fp.init = nullptr;
-                if (c->use_small) {
-                    uint64_t* k1 = c->timer.stamp(init ? "small_blur_init" : "small_blur");
-                    uint64_t* k2 = c->timer.stamp(init ? "small_scan_init" : "small_scan");
-                    // not stamping (FM_FLAG_PROFILE, or the stamp ring full): the pair timed by events
-                    int tok = (k1 && k2) ? -1 : c->timer.begin(init ? "small_init" : "small", ps);
-                    HIP_TRY(c, launch_small(ps, fp, B.d_sblur, k1, k2));
-                    c->timer.end(tok);
-                } else {
-                    fp.kstamp = c->timer.stamp(name);
-                    int tok = fp.kstamp ? -1 : c->timer.begin(name, ps);
-                    HIP_TRY(c, launch_pix(ps, fp, planes, init));
-                    c->timer.end(tok);
-                }
-                c->bg_cur ^= 1;
-                return FM_OK;
-            };
-            int rc;
-            if (any_init) {  // first frames in their own launch: the steady-state kernel has no init select
-                if ((rc = run(0, 1, true, "pix_init"))) return rc;
-                if (n > 1 && (rc = run(1, n, false, "pix"))) return rc;
-            } else if ((rc = run(0, n, false, "pix"))) {
-                return rc;
-            }
-        } else {
-            HIP_TRY(c, launch_fused(ps, fa, &c->timer));
-            c->bg_cur ^= 1;
-        }
-        // contour pass on its own stream, after this batch's pixel kernel
-        // consecutive batches on different contour streams: with 4 slots on 3 streams a fixed
-        // slot -> stream map put every fourth pair of consecutive chains on one stream, one after
-        // the other (the last batch's chain waited ≈130 µs for its predecessor's)
-        // (Batches taking the contour streams in turn instead of the fixed slot map: +2 % on one box,
-        // equal on another with 8 % longer pixel launches, round 3.)
-        hipStream_t cs = c->serial ? ps : B.ccl_stream;
-        HIP_TRY(c, hipEventRecord(B.ev_pix, ps));
-        HIP_TRY(c, hipStreamWaitEvent(cs, B.ev_pix, 0));
-        // the labelling gate: one batch's labelling kernel at a time (the previous batch's, on another contour
-        // stream, is waited for), so the labelling of consecutive chains never bunches beside a pixel launch
-        // (+1.5 %, 388.1 vs 382.3 k, 4 alternating rounds, round 3)
-        if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
-            FusedArgs fc = fa;
-#ifdef FM_DEV_SWITCHES
-            fc.kstamp = c->timer.stamp("frame_contours");
-#endif
-            // FM_FLAG_PROFILE: events around it (a contour stream: never in the pixel-only mode)
-            const int tok_fc = fc.kstamp ? -1 : c->timer.begin("frame_contours", cs);
-            // the slot-wide words (shared pool, heavy tally, frames done) sit at indices that depend on the batch's
-            // frame count; the last workgroup re-arms them for a batch of the same size, so a slot whose batch size
-            // changed (a stream's last, partial batch) zeroes them at the new indices first
-            if (B.ccl_F != F) {
-                HIP_TRY(c, hipMemsetAsync(B.d_count + 2 * F, 0, 2 * sizeof(int32_t), cs));
-                HIP_TRY(c, hipMemsetAsync(B.d_count + 3 * F + 2, 0, sizeof(int32_t), cs));
-                B.ccl_F = F;
-            }
-            HIP_TRY(c, launch_frame_contours(cs, fc, c->use_pix));
-            c->timer.end(tok_fc);
-        } else {
-            hipEvent_t gate_wait = nullptr;
-            if (!c->serial && c->lab_prev >= 0 && c->lab_prev != si) gate_wait = c->slots[c->lab_prev].ev_lab;
-            HIP_TRY(c, launch_tile_ccl(cs, fa, c->use_pix, &c->timer, gate_wait, B.ev_lab));
-            c->lab_prev = si;
-        }  // counts land in mapped h_count / h_overflow
-        B.fa = fa;
-        HIP_TRY(c, hipEventRecord(B.ev_done, cs));
-    } else {
-        PixelArgs a{};
-        a.bg = nullptr;
-        a.keep = c->d_keep;
-        a.has_keep = c->d_has_keep;
-        a.S = S;
-        a.h = c->h;
-        a.w = c->w;
-        a.ksize = c->p.ksize;
-        a.thresh = c->p.threshold;
-        a.alpha = c->p.avg;
-        a.beta = 1.0 - c->p.avg;
-        a.acc_vec_end = npx - npx % 16;
-        a.cvt_simd = npx >= 16;
-        for (int i = 0; i < c->p.ksize; i++) a.coef[i] = c->coef[i];
-        const size_t step_px = (size_t)S * c->work_plane;
-        for (int t = 0; t < n; t++) {
-            a.src = work + (size_t)t * step_px * 3;  // work image is [T][S][h][w][3] in every resize mode
-            a.init = (t == 0 && any_init) ? c->d_init : nullptr;
-            a.mask_out = c->d_mask + (size_t)t * step_px;
-            if (B.d_planes) {
-                a.gray_out = B.d_planes + (size_t)t * step_px;
-                a.blur_out = B.d_planes + F * c->work_plane + (size_t)t * step_px;
-                a.delta_out = B.d_planes + 2 * F * c->work_plane + (size_t)t * step_px;
-            }
-            int tok = c->timer.begin("pixel", ps);
-            HIP_TRY(c, launch_pixel_pp(ps, a, c->d_bg[c->bg_cur], c->d_bg[c->bg_cur ^ 1]));
-            c->timer.end(tok);
-            c->bg_cur ^= 1;
-        }
-        HIP_TRY(c, hipMemsetAsync(c->d_outer, 0, F * c->work_plane, ps));
-        CclArgs ca{c->d_mask, c->d_label, c->d_outer, c->d_cid, B.d_count, c->d_rec_dev, (int)F, c->h, c->w, c->p.max_contours};
-        HIP_TRY(c, launch_ccl(ps, ca, &c->timer));
-        HIP_TRY(c, hipMemcpyAsync(B.h_rec, c->d_rec_dev, F * c->p.max_contours * 5 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  ps));
-        HIP_TRY(c, hipMemsetAsync(B.d_count + F, 0, F * sizeof(int32_t), ps));
-        HIP_TRY(c, hipMemcpyAsync(B.h_overflow, B.d_count + F, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
-        HIP_TRY(c, hipMemcpyAsync(B.h_count, B.d_count, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
-        HIP_TRY(c, hipEventRecord(B.ev_done, ps));
+        const FusedArgs fa = fused_args(c, B, work, n, any_init);
+        if ((rc = run_pixel(c, B, fa, any_init)) || (rc = run_contours(c, B, si, fa))) return rc;
+    } else if ((rc = run_per_frame(c, B, work, n, any_init))) {
+        return rc;
     }
     for (int s = 0; s < S; s++) c->bg_init[s] = 1;
     B.n = n;
@@ -1315,15 +1110,16 @@ static int submit_impl(fm_ctx* c, const uint8_t* frames, int n, int on_device, f
     c->next_slot = (si + 1) % c->nslots;
     return FM_OK;
 }
+}  // namespace
 
 int fm_submit(fm_ctx* c, const uint8_t* frames, int n, int on_device) {
-    return submit_impl(c, frames, n, on_device, nullptr, nullptr, nullptr);
+    return submit(c, {InputKind::Bgr, n, on_device != 0, frames});
 }
 
 int fm_submit_streams(fm_ctx* c, const uint8_t* const* bgr, int n, int on_device) {
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     if (!bgr) return fail(c, FM_EINVAL, "null stream pointer array");
-    return submit_impl(c, nullptr, n, on_device, nullptr, nullptr, nullptr, bgr);
+    return submit(c, {InputKind::BgrStreams, n, on_device != 0, nullptr, bgr});
 }
 
 int fm_submit_jpeg(fm_ctx* c, fm_mjpeg* dec, const uint8_t* const* jpegs, const size_t* sizes, int n) {
@@ -1339,7 +1135,7 @@ int fm_submit_jpeg(fm_ctx* c, fm_mjpeg* dec, const uint8_t* const* jpegs, const 
     if (n >= 1 && (long long)n * c->p.n_streams > dmax)
         return fail(c, FM_EINVAL, "decoder takes %d frames per call, the batch has %lld", dmax,
                     (long long)n * c->p.n_streams);
-    return submit_impl(c, nullptr, n, 0, dec, jpegs, sizes);
+    return submit(c, {InputKind::Jpeg, n, false, nullptr, jpegs, dec, sizes});
 }
 
 // fm_yuv_layout resolved for width x height frames (pitch, chroma offset, extent, frame stride), or why not
@@ -1369,7 +1165,6 @@ static const char* yuv_resolve(int W, int H, const fm_yuv_layout* L, YuvSrc& y) 
     y.chroma_offset = coff;
     y.extent = extent;
     y.stride = L->frame_stride ? L->frame_stride : extent;
-    y.list = nullptr;
     return nullptr;
 }
 
@@ -1387,7 +1182,7 @@ int fm_submit_yuv(fm_ctx* c, const uint8_t* frames, int n, const fm_yuv_layout* 
     if (!frames) return fail(c, FM_EINVAL, "null frames");
     YuvSrc y{};
     if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return fail(c, FM_EINVAL, "%s", why);
-    return submit_impl(c, frames, n, on_device, nullptr, nullptr, nullptr, nullptr, &y);
+    return submit(c, {InputKind::Yuv, n, on_device != 0, frames, nullptr, nullptr, nullptr, y});
 }
 
 int fm_submit_yuv_list(fm_ctx* c, const uint8_t* const* frames, int n, const fm_yuv_layout* layout) {
@@ -1398,44 +1193,19 @@ int fm_submit_yuv_list(fm_ctx* c, const uint8_t* const* frames, int n, const fm_
     if (n < 1 || n > c->p.max_batch) return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d]", n, c->p.max_batch);
     for (size_t i = 0; i < (size_t)n * c->p.n_streams; i++)
         if (!frames[i]) return fail(c, FM_EINVAL, "null address for frame %zu", i);
-    y.list = frames;
-    return submit_impl(c, nullptr, n, 1, nullptr, nullptr, nullptr, nullptr, &y);
+    return submit(c, {InputKind::YuvList, n, true, nullptr, frames, nullptr, nullptr, y});
 }
 
-int fm_wait(fm_ctx* c) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if (c->inflight.empty()) return FM_OK;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int si = c->inflight.front();
-    c->inflight.erase(c->inflight.begin());
-    BatchSlot& B = c->slots[si];
-#ifdef FM_DEV_SWITCHES  // host time in fm_wait (dev build): blocked on the batch vs the post-pass after it
-    const auto hw0 = std::chrono::steady_clock::now();
-#endif
-    hipError_t e = hipEventSynchronize(B.ev_done);
-    if (e != hipSuccess) {
-        B.n = 0;
-        return fail(c, FM_EHIP, "hipEventSynchronize: %s", hipGetErrorString(e));
-    }
-#ifdef FM_DEV_SWITCHES
-    const auto hw1 = std::chrono::steady_clock::now();
-#endif
-    const int n = B.n, S = c->p.n_streams, cap = c->rec_cap;
-    const size_t F = (size_t)n * S;
-    // Frames whose records do not fit the cap are fetched whole, so len(frame.contours)
-    // and the records kept never depend on max_contours (fm.py:674-694 counts them all).
-    std::vector<std::pair<size_t, std::vector<int32_t>>> whole;
-#ifdef FM_BOUNDS_CHECK
-    if (*c->h_err) return fail(c, FM_EHIP, "contour-pass bounds check failed: codes 0x%x", *c->h_err);
-#endif
+namespace {
+using WholeFrames = std::vector<std::pair<size_t, std::vector<int32_t>>>;  // (frame, all its records), ascending
+
+// Frames whose records do not fit the cap are fetched whole, so len(frame.contours)
+// and the records kept never depend on max_contours (fm.py:674-694 counts them all).
+int fetch_whole_frames(fm_ctx* c, BatchSlot& B, size_t F, WholeFrames& whole) {
     c->fallbacks = 0;
-    if (c->use_fused) {
-        c->stats[0] = B.h_stats[0];
-        c->stats[1] = B.h_stats[1];
-    }
     for (size_t f = 0; f < F; f++) {
         const bool ovf = c->use_fused && B.h_overflow[f];
-        if (!ovf && B.h_count[f] <= cap) continue;
+        if (!ovf && B.h_count[f] <= c->rec_cap) continue;
         std::vector<int32_t> v;
         if (c->use_fused && !ovf) {
             if (int rc = emit_all(c, B, f, B.h_count[f], v)) return rc;
@@ -1449,25 +1219,30 @@ int fm_wait(fm_ctx* c) {
         }
         whole.emplace_back(f, std::move(v));
     }
-    c->timer.collect();
-    if (c->d_ts) {  // profiling: mean cycles between consecutive stamps of each labelled tile
-        std::vector<uint64_t> ts(F * c->ntiles * 16);
-        HIP_TRY(c, hipMemcpy(ts.data(), c->d_ts, ts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < F * c->ntiles; i++) {
-            const uint64_t* t = &ts[i * 16];
-            if (!t[1]) continue;
-            uint64_t prev = t[1];
-            for (int k = 2; k < 16; k++) {
-                if (!t[k]) continue;
-                c->ts_sum[k] += (double)(t[k] - prev);
-                c->ts_n[k]++;
-                prev = t[k];
-            }
+    return FM_OK;
+}
+
+// FM_TS (profiling): mean cycles between consecutive stamps of each labelled tile
+int fold_phase_stamps(fm_ctx* c, size_t F) {
+    std::vector<uint64_t> ts(F * c->ntiles * 16);
+    HIP_TRY(c, hipMemcpy(ts.data(), c->d_ts, ts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < F * c->ntiles; i++) {
+        const uint64_t* t = &ts[i * 16];
+        if (!t[1]) continue;
+        uint64_t prev = t[1];
+        for (int k = 2; k < 16; k++) {
+            if (!t[k]) continue;
+            c->ts_sum[k] += (double)(t[k] - prev);
+            c->ts_n[k]++;
+            prev = t[k];
         }
     }
-#ifdef FM_DEV_SWITCHES
-    const auto hw2 = std::chrono::steady_clock::now();
-#endif
+    return FM_OK;
+}
+
+// the batch's records -> c->contours: each frame's fm_contour list sorted by start pixel (raster order)
+void records_to_contours(fm_ctx* c, const BatchSlot& B, size_t F, const WholeFrames& whole) {
+    const int cap = c->rec_cap;
     c->ready_counts.assign(B.h_count, B.h_count + F);
     c->contours.assign(F, {});
     size_t wi = 0;
@@ -1497,6 +1272,45 @@ int fm_wait(fm_ctx* c) {
             o.npts = 0;
         }
     }
+}
+}  // namespace
+
+int fm_wait(fm_ctx* c) {
+    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (c->inflight.empty()) return FM_OK;
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const int si = c->inflight.front();
+    c->inflight.erase(c->inflight.begin());
+    BatchSlot& B = c->slots[si];
+#ifdef FM_DEV_SWITCHES  // host time in fm_wait (dev build): blocked on the batch vs the post-pass after it
+    const auto hw0 = std::chrono::steady_clock::now();
+#endif
+    hipError_t e = hipEventSynchronize(B.ev_done);
+    if (e != hipSuccess) {
+        B.n = 0;
+        return fail(c, FM_EHIP, "hipEventSynchronize: %s", hipGetErrorString(e));
+    }
+#ifdef FM_DEV_SWITCHES
+    const auto hw1 = std::chrono::steady_clock::now();
+#endif
+    const int n = B.n;
+    const size_t F = (size_t)n * c->p.n_streams;
+#ifdef FM_BOUNDS_CHECK
+    if (*c->h_err) return fail(c, FM_EHIP, "contour-pass bounds check failed: codes 0x%x", *c->h_err);
+#endif
+    if (c->use_fused) {
+        c->stats[0] = B.h_stats[0];
+        c->stats[1] = B.h_stats[1];
+    }
+    WholeFrames whole;
+    if (int rc = fetch_whole_frames(c, B, F, whole)) return rc;
+    c->timer.collect();
+    if (c->d_ts)
+        if (int rc = fold_phase_stamps(c, F)) return rc;
+#ifdef FM_DEV_SWITCHES
+    const auto hw2 = std::chrono::steady_clock::now();
+#endif
+    records_to_contours(c, B, F, whole);
 #ifdef FM_DEV_SWITCHES
     if (c->timer.enabled) {
         const auto hw3 = std::chrono::steady_clock::now();
@@ -1641,7 +1455,7 @@ int fm_frame_device(fm_ctx* c, int frame, int stream, const uint8_t** out) {
 int fm_read_background(fm_ctx* c, int stream, double* out) {
     if (!c || !out) return fail(c, FM_EINVAL, "null argument");
     if (int rc = check_idle(c)) return rc;
-    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    if (int rc = check_stream(c, stream)) return rc;
     if (!c->bg_init[stream]) return fail(c, FM_ESTATE, "stream %d has no background yet", stream);
     HIP_TRY(c, hipSetDevice(c->p.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1654,47 +1468,13 @@ int fm_read_background(fm_ctx* c, int stream, double* out) {
 int fm_write_background(fm_ctx* c, int stream, const double* in) {
     if (!c || !in) return fail(c, FM_EINVAL, "null argument");
     if (int rc = check_idle(c)) return rc;
-    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    if (int rc = check_stream(c, stream)) return rc;
     HIP_TRY(c, hipSetDevice(c->p.device));
     HIP_TRY(c, hipMemcpyAsync(c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, in, c->work_plane * sizeof(double),
                               hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bg_init[stream] = 1;
     return FM_OK;
-}
-
-int fm_kernel_times(fm_ctx* c, const char** names, double* ms, int64_t* launches, int cap) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    if (c->timer.fold_stamps() != 0) return fail(c, FM_EHIP, "reading the launch stamps failed");
-    const int n = (int)c->timer.names.size();
-    for (int i = 0; i < std::min(n, cap); i++) {
-        if (names) names[i] = c->timer.names[i];
-        if (ms) ms[i] = c->timer.ms[i];
-        if (launches) launches[i] = c->timer.launches[i];
-    }
-    return n;
-}
-
-int fm_kernel_time_spread(fm_ctx* c, double* ms_sq, int cap) {
-    if (!c || !ms_sq) return fail(c, FM_EINVAL, "null argument");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    if (c->timer.fold_stamps() != 0) return fail(c, FM_EHIP, "reading the launch stamps failed");
-    const int n = (int)c->timer.names.size();
-    for (int i = 0; i < std::min(n, cap); i++) ms_sq[i] = c->timer.ms_sq[i];
-    return n;
-}
-
-int fm_kernel_time_busy(fm_ctx* c, double* busy_ms, int cap) {
-    if (!c || !busy_ms) return fail(c, FM_EINVAL, "null argument");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    if (c->timer.fold_stamps() != 0) return fail(c, FM_EHIP, "reading the launch stamps failed");
-    const int n = (int)c->timer.names.size();
-    for (int i = 0; i < std::min(n, cap); i++) {
-        const auto& b = c->timer.busy[i];
-        busy_ms[i] = b.ms + (b.open ? (double)(b.e - b.s) * 1e-5 : 0.0);
-    }
-    return n;
 }
 
 int fm_kernel_time_stats(fm_ctx* c, const char** names, double* ms, int64_t* launches, double* stamped_ms,
@@ -1717,6 +1497,20 @@ int fm_kernel_time_stats(fm_ctx* c, const char** names, double* ms, int64_t* lau
     return n;
 }
 
+int fm_kernel_times(fm_ctx* c, const char** names, double* ms, int64_t* launches, int cap) {
+    return fm_kernel_time_stats(c, names, ms, launches, nullptr, nullptr, nullptr, nullptr, nullptr, cap);
+}
+
+int fm_kernel_time_spread(fm_ctx* c, double* ms_sq, int cap) {
+    if (!c || !ms_sq) return fail(c, FM_EINVAL, "null argument");
+    return fm_kernel_time_stats(c, nullptr, nullptr, nullptr, nullptr, nullptr, ms_sq, nullptr, nullptr, cap);
+}
+
+int fm_kernel_time_busy(fm_ctx* c, double* busy_ms, int cap) {
+    if (!c || !busy_ms) return fail(c, FM_EINVAL, "null argument");
+    return fm_kernel_time_stats(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, busy_ms, nullptr, cap);
+}
+
 int fm_reset_kernel_times(fm_ctx* c) {
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     HIP_TRY(c, hipSetDevice(c->p.device));
@@ -1724,11 +1518,11 @@ int fm_reset_kernel_times(fm_ctx* c) {
     return FM_OK;
 }
 
-}  // extern "C"
-
 int fm_footprint(const fm_ctx* c, size_t* device_bytes, size_t* pinned_bytes) {
     if (!c) return fail(nullptr, FM_EINVAL, "null context");
     if (device_bytes) *device_bytes = c->dev_bytes;
     if (pinned_bytes) *pinned_bytes = c->pinned_bytes;
     return FM_OK;
 }
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// fm_internal.h — shared declarations between the C ABI (fm_capi.cpp) and the
-// gfx950 kernels (fm_kernels.hip).  Not part of the public boundary.
+// fm_internal.h — shared declarations between the C ABI (fm_capi.cpp), its host helpers
+// (fm_tables.cpp, fm_timer.cpp) and the gfx950 kernels (fm_*.hip).  Not part of the public boundary.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,14 +26,12 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 // Developer switches (A/B experiments, profiling stamps) are read from the environment
 // only by the dev build (make VARIANT=dev -> libfm_hip_dev.so); the product library
 // ignores the environment.
-inline const char* dev_env(const char* name) {
 #ifdef FM_DEV_SWITCHES
-    return std::getenv(name);
+constexpr bool kDevSwitches = true;
 #else
-    (void)name;
-    return nullptr;
+constexpr bool kDevSwitches = false;
 #endif
-}
+inline const char* dev_env(const char* name) { return kDevSwitches ? std::getenv(name) : nullptr; }
 
 // Bounds checks on every data-dependent index of the contour pass (make VARIANT=checked ->
 // libfm_hip_checked.so): a violation sets bit `code` of the mapped error word, the access is
@@ -53,7 +51,7 @@ constexpr int kFrameCclTiles = 16;     // work images of at most this many tiles
 constexpr int kNodesShared = 16;       // + a shared overflow pool of this many per tile-frame (at least one
                                        //   worst-case frame), taken from only by frames past their quota
 
-// Host-built INTER_AREA tables (computeResizeAreaTab restated in fm_capi.cpp).
+// Host-built INTER_AREA tables (computeResizeAreaTab restated in fm_tables.cpp).
 // Per destination index d: taps start at src index ofs[d], cnt[d] taps, weights
 // wt[d * max_taps + j] (float32 exactly as OpenCV stores DecimateAlpha::alpha).
 struct AreaAxis {
@@ -185,8 +183,10 @@ __device__ __forceinline__ void kstamp_end_wg(uint64_t* ks) {
     if (threadIdx.x < 64) kstamp_end(ks);
 }
 
-// computeResizeAreaTab restated (fm_capi.cpp); false if a destination's taps are not consecutive
+// computeResizeAreaTab restated (fm_tables.cpp); false if a destination's taps are not consecutive
 bool build_area_axis(int ssize, int dsize, double scale, AreaAxis& A);
+// GaussianBlur's 8-bit fixed-point taps for CV_8U, sigma = 0 (fm_tables.cpp); false for an n it does not take
+bool gaussian_taps(int n, std::vector<int32_t>& out);
 
 // Kernel launchers (fm_kernels.hip, fm_fused.hip).  All asynchronous on `st`.
 hipError_t launch_resize_area(hipStream_t st, const uint8_t* src, uint8_t* dst, int F, int H, int W,
@@ -301,6 +301,19 @@ struct KernelTimer {
     void collect();                // folds in every pair whose end event has completed
     uint64_t* stamp(const char* name);  // this launch's stamp pair, nullptr when not stamping
     int fold_stamps();             // waits for the stamped streams, folds and re-arms the entries
+    // One launch on st: stamped if stamping (launch gets the stamp pair), else bracketed by events.
+    // name2: a launch of two stamped kernels (launch's second pair); unless both are stamped, events
+    // bracket the two under ev_name.  stamps = false: a kernel that does not stamp (events only).
+    template <class Launch>
+    hipError_t timed(hipStream_t st, const char* name, Launch&& launch, bool stamps = true, const char* name2 = nullptr,
+                     const char* ev_name = nullptr) {
+        uint64_t* k1 = stamps ? stamp(name) : nullptr;
+        uint64_t* k2 = stamps && name2 ? stamp(name2) : nullptr;
+        const int tok = (k1 && (k2 || !name2)) ? -1 : begin(ev_name ? ev_name : name, st);
+        const hipError_t e = launch(k1, k2);
+        if (e == hipSuccess) end(tok);
+        return e;
+    }
     void reset();
     ~KernelTimer();
 };
