@@ -21,7 +21,9 @@
 //           layout, straight into the caller's frame buffer.
 // Supported: 8-bit baseline / extended-sequential Huffman, grayscale or 3-component YCbCr with
 // Cb, Cr at 1x1 and Y at 1x1, 2x1 or 2x2; restart intervals optional; quantization and Huffman
-// tables may change from frame to frame.  Anything else: FM_ENOTSUP.
+// tables may change from frame to frame.  Anything else: FM_ENOTSUP, three components that libjpeg
+// would take as RGB (Adobe transform 0 or ids 'R','G','B' without JFIF) included.  Streams Pillow's
+// default encoder never writes are pinned by tests/test_gpu_jpeg_streams.py.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -1115,6 +1117,8 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
     if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return pfail(err, FM_EINVAL, "frame %d: no SOI", idx);
     size_t i = 2;
     bool sof = false;
+    bool jfif = false, adobe = false;  // jdmarker.c get_interesting_appn: APP0 'JFIF', APP14 'Adobe'
+    int adobe_transform = 0;
     while (i + 4 <= n) {
         if (p[i] != 0xFF) return pfail(err, FM_EINVAL, "frame %d: marker expected at byte %zu", idx, i);
         while (i < n && p[i] == 0xFF) i++;
@@ -1171,6 +1175,13 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
         } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
             return pfail(err, FM_ENOTSUP, "frame %d: SOF%d (progressive / lossless / arithmetic) not supported", idx,
                          m - 0xC0);
+        } else if (m == 0xE0) {
+            if (sl >= 14 && !memcmp(s, "JFIF\0", 5)) jfif = true;
+        } else if (m == 0xEE) {
+            if (sl >= 12 && !memcmp(s, "Adobe", 5)) {
+                adobe = true;
+                adobe_transform = s[11];
+            }
         } else if (m == 0xDD) {
             if (sl < 2) return pfail(err, FM_EINVAL, "frame %d: bad DRI", idx);
             J.dri = (s[0] << 8) | s[1];
@@ -1183,7 +1194,16 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
                 J.sid[k] = s[1 + 2 * k];
                 J.std_[k] = s[2 + 2 * k] >> 4;
                 J.sta[k] = s[2 + 2 * k] & 15;
+                // T.81 B.2.3: the scan's components in the frame's order (libjpeg refuses any other)
+                if (J.sid[k] != J.cid[k])
+                    return pfail(err, FM_EINVAL, "frame %d: scan component %d is not the frame's component %d", idx, k, k);
             }
+            // libjpeg's colour space of three components (jdapimin.c default_decompress_parms): JFIF says
+            // YCbCr; else Adobe's transform byte (0: RGB); else the ids 'R','G','B' say RGB.  The planes
+            // of an RGB stream are not converted: left to the host decoder.
+            if (J.nc == 3 && !jfif &&
+                (adobe ? adobe_transform == 0 : (J.cid[0] == 'R' && J.cid[1] == 'G' && J.cid[2] == 'B')))
+                return pfail(err, FM_ENOTSUP, "frame %d: RGB-coded JPEG (no YCbCr transform) not supported", idx);
             J.scan_begin = i + len;
             // the scan ends at the first marker that is neither stuffing (FF 00) nor RSTn; any run of
             // 0xFF fill bytes may precede a marker (T.81 B.1.1.2) and is skipped, as libjpeg's

@@ -162,13 +162,16 @@ def jpeg_layout(data: bytes):
 def jpeg_gpu_supported(data: bytes) -> bool:
     """Whether the GPU decoder takes this JPEG's layout (fm_jpeg.hip parse_jpeg / setup_geometry):
     SOF0/SOF1 Huffman, 8-bit, one component or three with Cb, Cr at 1x1 and Y at 1x1, 2x1 or 2x2,
-    one interleaved scan: the first SOS names every component of the frame (a file whose components
-    come in separate scans is refused by parse_jpeg)."""
+    one interleaved scan: the first SOS names every component of the frame, in the frame's order (a
+    file whose components come in separate scans is refused by parse_jpeg).  Three components must be
+    YCbCr by libjpeg's rule: a JFIF APP0 says so; else an Adobe APP14's transform byte (0: RGB); else
+    the ids 'R','G','B' say RGB.  RGB-coded frames go to the host decoder."""
     try:
         i = 2
         if data[:2] != b"\xff\xd8":
             return False
-        nc = None
+        nc = ids = None
+        jfif, adobe = False, None
         while i + 4 <= len(data):
             if data[i] != 0xFF:
                 return False
@@ -184,13 +187,21 @@ def jpeg_gpu_supported(data: bytes) -> bool:
                 if m not in (0xC0, 0xC1) or seg[0] != 8:
                     return False
                 nc = seg[5]
+                ids = [seg[6 + 3 * c] for c in range(nc)]
                 hv = [(seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15) for c in range(nc)]
                 ok = (1 <= hv[0][0] <= 4 and 1 <= hv[0][1] <= 4) if nc == 1 else \
                     (nc == 3 and hv[1] == hv[2] == (1, 1) and hv[0] in ((1, 1), (2, 1), (2, 2)))
                 if not ok:
                     return False
-            if m == 0xDA:  # the first scan: interleaved over every component of the frame
-                return nc is not None and len(seg) >= 1 and seg[0] == nc
+            if m == 0xE0 and len(seg) >= 14 and seg[:5] == b"JFIF\0":
+                jfif = True
+            if m == 0xEE and len(seg) >= 12 and seg[:5] == b"Adobe":
+                adobe = seg[11]
+            if m == 0xDA:  # the first scan: interleaved over every component of the frame, in its order
+                if nc is None or len(seg) < 1 or seg[0] != nc or [seg[1 + 2 * k] for k in range(nc)] != ids:
+                    return False
+                rgb = adobe == 0 if adobe is not None else ids == [0x52, 0x47, 0x42]
+                return not (nc == 3 and not jfif and rgb)
             i += ln
     except IndexError:
         return False

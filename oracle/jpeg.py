@@ -32,6 +32,7 @@ def parse(data: bytes) -> dict:
     if data[:2] != b"\xff\xd8":
         raise JpegError("no SOI")
     qt, ht, frame, scan, dri = {}, {}, None, None, 0
+    jfif, adobe = False, None  # jdmarker.c get_interesting_appn: APP0 'JFIF' seen, APP14 'Adobe' transform byte
     i = 2
     while i < len(data):
         if data[i] != 0xFF:
@@ -71,6 +72,8 @@ def parse(data: bytes) -> dict:
             if seg[0] != 8:
                 raise JpegError("only 8-bit samples")
             H, W, nc = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if nc not in (1, 3):
+                raise JpegError(f"{nc} components (1 or 3 supported)")
             comps = []
             for c in range(nc):
                 cid, hv, tq = seg[6 + 3 * c], seg[7 + 3 * c], seg[8 + 3 * c]
@@ -78,6 +81,11 @@ def parse(data: bytes) -> dict:
             frame = {"H": H, "W": W, "comps": comps}
         elif m in (0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF):
             raise JpegError(f"unsupported SOF {m:#x} (progressive / lossless / arithmetic)")
+        elif m == 0xE0:
+            jfif = jfif or (len(seg) >= 14 and seg[:5] == b"JFIF\0")
+        elif m == 0xEE:
+            if len(seg) >= 12 and seg[:5] == b"Adobe":
+                adobe = seg[11]
         elif m == 0xDD:  # DRI
             dri = (seg[0] << 8) | seg[1]
         elif m == 0xDA:  # SOS: the entropy-coded data follows the header
@@ -107,6 +115,13 @@ def parse(data: bytes) -> dict:
         raise JpegError("no frame or scan")
     if len(scan["sel"]) != len(frame["comps"]):
         raise JpegError("multi-scan (non-interleaved) JPEG not supported")
+    ids = [c["id"] for c in frame["comps"]]
+    if [s[0] for s in scan["sel"]] != ids:  # T.81 B.2.3; libjpeg refuses any other order
+        raise JpegError("the scan's components are not in the frame's order")
+    # jdapimin.c default_decompress_parms, three components: JFIF says YCbCr; else Adobe's transform
+    # byte (0: RGB); else the ids 'R','G','B' say RGB.  RGB planes are not restated here.
+    if len(ids) == 3 and not jfif and (adobe == 0 if adobe is not None else ids == [0x52, 0x47, 0x42]):
+        raise JpegError("RGB-coded JPEG (no YCbCr transform) not supported")
     for key, tab in STD_HUFF.items():  # jstdhuff.c std_huff_tables: slots 0 and 1 the stream left undefined
         ht.setdefault(key, tab)
     return {"qt": qt, "ht": ht, "frame": frame, "scan": scan, "dri": dri}
@@ -176,6 +191,7 @@ class _Bits:
         self._fill()
         v = (self.acc >> (self.n - k)) & ((1 << k) - 1)
         self.n -= k
+        self.acc &= (1 << self.n) - 1  # consumed bits dropped: the accumulator stays a machine word
         return v
 
     def huff(self, tab: dict) -> int:

@@ -76,6 +76,145 @@ def strip_dht(data: bytes) -> bytes:
     return bytes(out + data[last:])
 
 
+def segment(marker: int, payload: bytes) -> bytes:
+    """One marker segment: FF, the marker, the two length bytes, the payload."""
+    return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload
+
+
+def _rewrite(data: bytes, fn) -> bytes:
+    """The same JPEG with its header segments (SOI excluded, SOS included) replaced by what fn returns for
+    the list of [marker, payload] pairs; the entropy-coded data and what follows it are kept."""
+    segs = segments(data)
+    assert segs and segs[-1][0] == 0xDA, "no SOS"
+    out = fn([[m, data[a + 4:b]] for m, a, b in segs])
+    return data[:2] + b"".join(segment(m, p) for m, p in out) + data[segs[-1][2]:]
+
+
+def drop_segments(data: bytes, marker: int) -> bytes:
+    """The same JPEG without its segments of this marker."""
+    return _rewrite(data, lambda segs: [s for s in segs if s[0] != marker])
+
+
+def insert_after_soi(data: bytes, *segs: bytes) -> bytes:
+    """The same JPEG with whole segments (see segment()) put right after the SOI."""
+    assert data[:2] == b"\xff\xd8"
+    return data[:2] + b"".join(segs) + data[2:]
+
+
+def merge_segments(data: bytes, marker: int) -> bytes:
+    """Every segment of this marker (DQT or DHT: a payload is a list of tables) merged into one, at the place
+    of the first."""
+    def fn(segs):
+        body = b"".join(p for m, p in segs if m == marker)
+        out, done = [], False
+        for m, p in segs:
+            if m != marker:
+                out.append([m, p])
+            elif not done:
+                out.append([m, body])
+                done = True
+        return out
+    return _rewrite(data, fn)
+
+
+def _is_sof(m: int) -> bool:
+    return 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC)
+
+
+def renumber_components(data: bytes, ids) -> bytes:
+    """Component k of the frame gets id ids[k], in the SOF and in the SOS selectors together."""
+    def fn(segs):
+        old = {}
+        for s in segs:
+            p = bytearray(s[1])
+            if _is_sof(s[0]):
+                for k in range(p[5]):
+                    old[p[6 + 3 * k]] = ids[k]
+                    p[6 + 3 * k] = ids[k]
+            elif s[0] == 0xDA:
+                for k in range(p[0]):
+                    p[1 + 2 * k] = old[p[1 + 2 * k]]
+            s[1] = bytes(p)
+        return segs
+    return _rewrite(data, fn)
+
+
+def renumber_huffman(data: bytes, ids: dict) -> bytes:
+    """Huffman table id t becomes ids[t] (both classes), in every DHT and in the SOS selectors."""
+    def fn(segs):
+        for s in segs:
+            p = bytearray(s[1])
+            if s[0] == 0xC4:
+                q = 0
+                while q < len(p):
+                    p[q] = (p[q] & 0xF0) | ids.get(p[q] & 15, p[q] & 15)
+                    q += 17 + sum(p[q + 1:q + 17])
+            elif s[0] == 0xDA:
+                for k in range(p[0]):
+                    b = p[2 + 2 * k]
+                    p[2 + 2 * k] = (ids.get(b >> 4, b >> 4) << 4) | ids.get(b & 15, b & 15)
+            s[1] = bytes(p)
+        return segs
+    return _rewrite(data, fn)
+
+
+def renumber_quant(data: bytes, ids: dict) -> bytes:
+    """Quantization table id t becomes ids[t], in every DQT and in the SOF's component entries."""
+    def fn(segs):
+        for s in segs:
+            p = bytearray(s[1])
+            if s[0] == 0xDB:
+                q = 0
+                while q < len(p):
+                    step = 129 if p[q] >> 4 else 65
+                    p[q] = (p[q] & 0xF0) | ids.get(p[q] & 15, p[q] & 15)
+                    q += step
+            elif _is_sof(s[0]):
+                for k in range(p[5]):
+                    p[8 + 3 * k] = ids.get(p[8 + 3 * k], p[8 + 3 * k])
+            s[1] = bytes(p)
+        return segs
+    return _rewrite(data, fn)
+
+
+def set_gray_sampling(data: bytes, hv: int) -> bytes:
+    """A one-component frame with its SOF sampling byte set to hv (a single component's factors change
+    nothing: its scan is not interleaved, T.81 A.2.2)."""
+    def fn(segs):
+        for s in segs:
+            if _is_sof(s[0]):
+                assert s[1][5] == 1, "not a one-component frame"
+                s[1] = s[1][:7] + bytes([hv]) + s[1][8:]
+        return segs
+    return _rewrite(data, fn)
+
+
+def append_after_eoi(data: bytes, extra: bytes) -> bytes:
+    assert data[-2:] == b"\xff\xd9"
+    return data + extra
+
+
+def drop_eoi(data: bytes) -> bytes:
+    assert data[-2:] == b"\xff\xd9"
+    return data[:-2]
+
+
+def swap_sos_ids(data: bytes, a: int = 0, b: int = 1) -> bytes:
+    """The component selectors of scan entries a and b exchanged (their table selectors stay): a scan whose
+    component order differs from the frame's, which T.81 B.2.3 forbids and libjpeg refuses."""
+    def fn(segs):
+        p = bytearray(segs[-1][1])
+        p[1 + 2 * a], p[1 + 2 * b] = p[1 + 2 * b], p[1 + 2 * a]
+        segs[-1][1] = bytes(p)
+        return segs
+    return _rewrite(data, fn)
+
+
+def adobe_app14(transform: int) -> bytes:
+    """An Adobe APP14 segment: 'Adobe', version 100, flags0, flags1, the colour transform byte."""
+    return segment(0xEE, b"Adobe" + (100).to_bytes(2, "big") + b"\0\0\0\0" + bytes([transform]))
+
+
 def fill_before_markers(data: bytes, n: int = 2) -> bytes:
     """Insert n 0xFF fill bytes before every RSTn marker and the EOI of the scan (T.81 B.1.1.2 allows any
     number; libjpeg skips them)."""
@@ -89,3 +228,161 @@ def fill_before_markers(data: bytes, n: int = 2) -> bytes:
         out.append(c)
         k += 1
     return bytes(head + out)
+
+
+# ---- streams Pillow's default encoder never writes (tests/test_gpu_jpeg_streams.py, tests/test_jpeg_host.py)
+
+def _after_jfif(data: bytes, *segs: bytes) -> bytes:
+    """Segments put right after the JFIF APP0 (which stays first, as JFIF asks)."""
+    m, a, b = segments(data)[0]
+    assert m == 0xE0
+    return insert_after_soi(drop_segments(data, 0xE0), data[a:b], *segs)
+
+
+def _base(H: int, W: int, seed: int = 3, **kw) -> bytes:
+    """4:2:0 unless told otherwise; quality 85 unless the tables are given (Pillow would scale them by it)."""
+    return encode(image(H, W, "smooth", seed=seed), **{**({} if "qtables" in kw else {"quality": 85}), **kw})
+
+
+def _opt(H: int, W: int, seed: int = 3) -> bytes:
+    return _base(H, W, seed, optimize=True)
+
+
+def _gray(H: int, W: int, seed: int = 3) -> bytes:
+    return encode(image(H, W, "smooth", seed=seed)[..., 1], quality=85)
+
+
+_QT3 = [[1 + (k * 7) % 23 for k in range(64)], [2 + (k * 5) % 61 for k in range(64)], [3 + (k * 11) % 97 for k in range(64)]]
+_MARKERS = b"x\xff\xd8y\xff\xd9z\xff\xda\x00\x0c\x03\x01\x00\xff\xc4\xff\xd9"
+
+
+def _thumbnail() -> bytes:
+    return encode(image(8, 8, "noise", seed=9), quality=50)
+
+
+def _keep_rgb(H: int, W: int) -> bytes:
+    b = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(image(H, W, "smooth", seed=3)[..., ::-1])).save(b, "JPEG", quality=85, keep_rgb=True)
+    return b.getvalue()
+
+
+def _cmyk(H: int, W: int) -> bytes:
+    b = io.BytesIO()
+    Image.fromarray(image(H, W, "smooth", seed=3)[..., [0, 1, 2, 0]].copy(), "CMYK").save(b, "JPEG", quality=85)
+    return b.getvalue()
+
+
+# name -> (H, W, image seed = 3) -> (stream, the unpatched stream it must decode like or None).
+# The decoder takes all of these.
+STREAMS = {
+    "dqt16_sof1": lambda H, W, s=3: (_base(H, W, s, qtables=[[300] * 64, [1000] * 64]), None),
+    "three_qtables": lambda H, W, s=3: (_base(H, W, s, qtables=_QT3), None),
+    "quant_ids_2_3": lambda H, W, s=3: (renumber_quant(_base(H, W, s), {0: 2, 1: 3}), _base(H, W, s)),
+    "huff_ids_2_3": lambda H, W, s=3: (renumber_huffman(_base(H, W, s), {0: 2, 1: 3}), _base(H, W, s)),
+    # the stream's own (optimized) tables: a table taken from the wrong slot is then not the standard one either
+    "huff_ids_3_2": lambda H, W, s=3: (renumber_huffman(_opt(H, W, s), {0: 3, 1: 2}), _opt(H, W, s)),
+    "merged_dht": lambda H, W, s=3: (merge_segments(_opt(H, W, s), 0xC4), _opt(H, W, s)),
+    "merged_dqt": lambda H, W, s=3: (merge_segments(_base(H, W, s), 0xDB), _base(H, W, s)),
+    "merged_dqt16": lambda H, W, s=3: (merge_segments(_base(H, W, s, qtables=[[300] * 64, [1000] * 64]), 0xDB),
+                                  _base(H, W, s, qtables=[[300] * 64, [1000] * 64])),
+    "ids_012_jfif": lambda H, W, s=3: (renumber_components(_base(H, W, s), [0, 1, 2]), _base(H, W, s)),
+    "ids_012_no_jfif": lambda H, W, s=3: (drop_segments(renumber_components(_base(H, W, s), [0, 1, 2]), 0xE0), _base(H, W, s)),
+    "adobe1_no_jfif": lambda H, W, s=3: (insert_after_soi(drop_segments(_base(H, W, s), 0xE0), adobe_app14(1)), _base(H, W, s)),
+    "jfif_and_adobe0": lambda H, W, s=3: (_after_jfif(_base(H, W, s), adobe_app14(0)), _base(H, W, s)),
+    "app1_thumbnail": lambda H, W, s=3: (_after_jfif(_base(H, W, s), segment(0xE1, b"Exif\0\0" + _thumbnail())), _base(H, W, s)),
+    "app2_com_markers": lambda H, W, s=3: (_after_jfif(_base(H, W, s), segment(0xE2, _MARKERS), segment(0xFE, _MARKERS)),
+                                      _base(H, W, s)),
+    "trailing_bytes": lambda H, W, s=3: (append_after_eoi(_base(H, W, s), b"\0junk\xff\xff" + _base(H, W, s, quality=40)),
+                                    _base(H, W, s)),
+    "no_eoi": lambda H, W, s=3: (drop_eoi(_base(H, W, s)), _base(H, W, s)),
+    "gray_0x22": lambda H, W, s=3: (set_gray_sampling(_gray(H, W, s), 0x22), _gray(H, W, s)),
+    "gray_0x21": lambda H, W, s=3: (set_gray_sampling(_gray(H, W, s), 0x21), _gray(H, W, s)),
+    "gray_0x14": lambda H, W, s=3: (set_gray_sampling(_gray(H, W, s), 0x14), _gray(H, W, s)),
+    "gray_0x44": lambda H, W, s=3: (set_gray_sampling(_gray(H, W, s), 0x44), _gray(H, W, s)),
+}
+
+# name -> (H, W) -> stream.  The decoder refuses these: RGB-coded planes (libjpeg's colour-space rule), a scan
+# whose components are not in the frame's order, four components.
+REFUSED = {
+    "keep_rgb": _keep_rgb,
+    "adobe0_no_jfif": lambda H, W, s=3: insert_after_soi(drop_segments(_base(H, W, s, subsampling=0), 0xE0), adobe_app14(0)),
+    "ids_RGB_bare": lambda H, W, s=3: drop_segments(renumber_components(_base(H, W, s, subsampling=0), [0x52, 0x47, 0x42]), 0xE0),
+    "sos_ids_swapped": lambda H, W, s=3: swap_sos_ids(_base(H, W, s, subsampling=0), 0, 1),
+    "cmyk": _cmyk,
+}
+RGB_REFUSED = ("keep_rgb", "adobe0_no_jfif", "ids_RGB_bare")
+
+
+def as_jfif(data: bytes) -> bytes:
+    """The stream with component ids 1, 2, 3, no Adobe segment and a JFIF APP0: YCbCr by libjpeg's rule."""
+    d = drop_segments(drop_segments(renumber_components(data, [1, 2, 3]), 0xEE), 0xE0)
+    return insert_after_soi(d, segment(0xE0, b"JFIF\0\1\1\0\0\1\0\1\0\0"))
+
+
+def reference_decode_truncated(data: bytes) -> np.ndarray:
+    """reference_decode of a stream without EOI: libjpeg supplies the EOI, Pillow must be told to accept it."""
+    from PIL import ImageFile
+    old = ImageFile.LOAD_TRUNCATED_IMAGES
+    ImageFile.LOAD_TRUNCATED_IMAGES = True
+    try:
+        return reference_decode(data)
+    finally:
+        ImageFile.LOAD_TRUNCATED_IMAGES = old
+
+
+def stream_reference(name: str, data: bytes) -> np.ndarray:
+    return reference_decode_truncated(data) if name == "no_eoi" else reference_decode(data)
+
+
+# ---- entropy extremes
+
+SUBSAMPLINGS = [("444", 0), ("422", 1), ("420", 2)]
+
+
+def checkerboard(H: int, W: int) -> np.ndarray:
+    """8 x 8 blocks, black and white in turn: at quality 100 the luma DC goes from -1024 to 1016 and back."""
+    y, x = np.mgrid[0:H, 0:W]
+    return np.repeat(((((y >> 3) + (x >> 3)) & 1) * 255).astype(np.uint8)[..., None], 3, axis=2)
+
+
+def busy_noise(H: int, W: int, seed: int = 5) -> np.ndarray:
+    """Noise over a pixel checkerboard (the sign pattern of the DCT's basis function 7,7): at quality 100
+    coefficient 63 of every luma block is far from zero, so no block of the image ends in an EOB."""
+    y, x = np.mgrid[0:H, 0:W]
+    carrier = 128 + 60 * (1 - 2 * ((x + y) & 1))
+    rng = np.random.default_rng(seed)
+    return (carrier[..., None] + rng.integers(-50, 51, (H, W, 3))).astype(np.uint8)
+
+
+def constant(H: int, W: int) -> np.ndarray:
+    return np.full((H, W, 3), 128, np.uint8)
+
+
+def luma_dc_differences(j: dict, coefs) -> list:
+    """The DC differences of component 0 in scan order (no restart intervals), from oracle.jpeg.parse and
+    decode_coefficients: dequantized DC / its quantizer, block after block as the MCUs interleave them."""
+    assert j["dri"] == 0
+    c = j["frame"]["comps"][0]
+    dc = coefs[0][..., 0] // j["qt"][c["tq"]][0]
+    bh, bw = dc.shape
+    if len(j["frame"]["comps"]) == 1:
+        W, H = j["frame"]["W"], j["frame"]["H"]
+        seq = [dc[by, bx] for by in range(-(-H // 8)) for bx in range(-(-W // 8))]
+    else:
+        seq = [dc[my * c["v"] + v, mx * c["h"] + h] for my in range(bh // c["v"]) for mx in range(bw // c["h"])
+               for v in range(c["v"]) for h in range(c["h"])]
+    return [int(b) - int(a) for a, b in zip([0] + seq[:-1], seq)]
+
+
+def restart_interval_lengths(j: dict) -> list:
+    """Byte lengths of the restart intervals of oracle.jpeg.parse's entropy-coded segment."""
+    out, n, d, k = [], 0, j["scan"]["data"], 0
+    while k < len(d):
+        if d[k] == 0xFF and k + 1 < len(d) and 0xD0 <= d[k + 1] <= 0xD7:
+            out.append(n)
+            n = 0
+            k += 2
+        else:
+            n += 1
+            k += 1
+    return out + [n]

@@ -13,7 +13,9 @@ import numpy as np
 import pytest
 
 from oracle import jpeg
-from jpeg_cases import ENCODINGS, Image, encode, fill_before_markers, image, reference_decode, segments, strip_dht
+from jpeg_cases import (ENCODINGS, REFUSED, RGB_REFUSED, STREAMS, SUBSAMPLINGS, Image, as_jfif, busy_noise, checkerboard, constant,
+                        encode, fill_before_markers, image, luma_dc_differences, reference_decode,
+                        restart_interval_lengths, segments, stream_reference, strip_dht)
 
 pytestmark = pytest.mark.skipif(Image is None, reason="Pillow not importable")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_cases.npz")
@@ -167,6 +169,112 @@ def test_jpeg_gpu_supported_layouts():
     assert all(videoio.jpeg_gpu_supported(j) for j in ok)
     assert not videoio.jpeg_gpu_supported(encode(image(24, 40, "smooth"), quality=75, progressive=True))
     assert not videoio.jpeg_gpu_supported(b"not a jpeg")
+    # libjpeg's colour-space rule and T.81 B.2.3: RGB-coded planes and a scan out of the frame's order go to
+    # the host; every other stream shape of the list is the GPU decoder's
+    for name in RGB_REFUSED + ("sos_ids_swapped", "cmyk"):
+        assert not videoio.jpeg_gpu_supported(REFUSED[name](24, 40)), name
+    for name, make in STREAMS.items():
+        assert videoio.jpeg_gpu_supported(make(24, 40)[0]), name
+
+
+STREAM_SHAPES = [(37, 53), (16, 16)]
+
+
+@pytest.mark.parametrize("H,W", STREAM_SHAPES)
+@pytest.mark.parametrize("name", list(STREAMS))
+def test_streams_pillow_does_not_write(name, H, W):
+    """Table ids, merged segments, 16-bit tables, metadata, trailing bytes, a missing EOI, a gray frame's
+    sampling byte: the restatement equals libjpeg, and a patch that keeps the meaning keeps libjpeg's pixels
+    (a broken helper fails here as a helper)."""
+    data, base = STREAMS[name](H, W)
+    want = stream_reference(name, data)
+    if base is not None:
+        assert data != base and np.array_equal(want, reference_decode(base))
+    assert np.array_equal(_bgr(jpeg.decode(data)), want)
+
+
+def test_stream_patches_are_what_their_names_say():
+    H, W = 37, 53
+    mk = lambda name: STREAMS[name](H, W)[0]  # noqa: E731
+    seg = lambda d, m: [d[a + 4:b] for k, a, b in segments(d) if k == m]  # noqa: E731
+    d = mk("dqt16_sof1")
+    assert seg(d, 0xC1) and not seg(d, 0xC0) and all(p[0] >> 4 == 1 and len(p) == 129 for p in seg(d, 0xDB))
+    assert int(jpeg.parse(d)["qt"][1].max()) == 1000
+    j = jpeg.parse(mk("three_qtables"))
+    assert [c["tq"] for c in j["frame"]["comps"]] == [0, 1, 2] and not np.array_equal(j["qt"][1], j["qt"][2])
+    j = jpeg.parse(mk("quant_ids_2_3"))
+    assert [c["tq"] for c in j["frame"]["comps"]] == [2, 3, 3] and set(j["qt"]) == {2, 3}
+    for name, ids in (("huff_ids_2_3", (2, 3)), ("huff_ids_3_2", (3, 2))):
+        d = mk(name)
+        assert [p[0] & 15 for p in seg(d, 0xC4)] == [ids[0], ids[0], ids[1], ids[1]]
+        assert [(td, ta) for _, td, ta in jpeg.parse(d)["scan"]["sel"]] == [(ids[0],) * 2, (ids[1],) * 2, (ids[1],) * 2]
+    assert len(seg(mk("merged_dht"), 0xC4)) == 1 and len(seg(STREAMS["merged_dht"](H, W)[1], 0xC4)) == 4
+    std = [(list(bits), list(vals)) for bits, vals in jpeg.STD_HUFF.values()]
+    for name in ("merged_dht", "huff_ids_3_2"):  # four tables of the stream's own, none of them a standard one
+        own = [t for k, t in jpeg.parse(mk(name))["ht"].items() if t is not jpeg.STD_HUFF.get(k)]
+        assert len(own) == 4 and all((list(bits), list(vals)) not in std for bits, vals in own)
+    assert [len(p) for p in seg(mk("merged_dqt"), 0xDB)] == [130]
+    assert [len(p) for p in seg(mk("merged_dqt16"), 0xDB)] == [258]
+    for name, jfif in (("ids_012_jfif", True), ("ids_012_no_jfif", False)):
+        d = mk(name)
+        assert [c["id"] for c in jpeg.parse(d)["frame"]["comps"]] == [0, 1, 2] and bool(seg(d, 0xE0)) == jfif
+    d = mk("adobe1_no_jfif")
+    assert not seg(d, 0xE0) and seg(d, 0xEE)[0][:5] == b"Adobe" and seg(d, 0xEE)[0][11] == 1 and len(seg(d, 0xEE)[0]) == 12
+    d = mk("jfif_and_adobe0")
+    assert seg(d, 0xE0) and seg(d, 0xEE)[0][11] == 0
+    assert b"\xff\xd8" in seg(mk("app1_thumbnail"), 0xE1)[0] and b"\xff\xd9" in seg(mk("app1_thumbnail"), 0xE1)[0]
+    for m in (0xE2, 0xFE):
+        assert all(x in seg(mk("app2_com_markers"), m)[0] for x in (b"\xff\xd8", b"\xff\xd9", b"\xff\xda"))
+    d = mk("trailing_bytes")
+    assert d.count(b"\xff\xd8\xff\xe0") == 2 and not d.endswith(STREAMS["trailing_bytes"](H, W)[1][-64:])
+    assert b"\xff\xd9" not in mk("no_eoi")[-2:]
+    for hv in (0x22, 0x21, 0x14, 0x44):
+        c = jpeg.parse(mk(f"gray_{hv:#04x}"))["frame"]["comps"]
+        assert len(c) == 1 and (c[0]["h"], c[0]["v"]) == (hv >> 4, hv & 15)
+    # the refused ones: what makes each of them RGB, and the swapped scan
+    d = REFUSED["keep_rgb"](H, W)
+    assert not seg(d, 0xE0) and seg(d, 0xEE)[0][11] == 0 and [seg(d, 0xC0)[0][6 + 3 * k] for k in range(3)] == list(b"RGB")
+    d = REFUSED["adobe0_no_jfif"](H, W)
+    assert not seg(d, 0xE0) and seg(d, 0xEE)[0][11] == 0 and [seg(d, 0xC0)[0][6 + 3 * k] for k in range(3)] == [1, 2, 3]
+    d = REFUSED["ids_RGB_bare"](H, W)
+    assert not seg(d, 0xE0) and not seg(d, 0xEE) and [seg(d, 0xC0)[0][6 + 3 * k] for k in range(3)] == list(b"RGB")
+    d = REFUSED["sos_ids_swapped"](H, W)
+    assert [seg(d, 0xDA)[0][1 + 2 * k] for k in range(3)] == [2, 1, 3] and [seg(d, 0xDA)[0][2 + 2 * k] for k in range(3)] == [0, 0x11, 0x11]
+    assert seg(REFUSED["cmyk"](H, W), 0xC0)[0][5] == 4
+
+
+@pytest.mark.parametrize("name", list(REFUSED))
+def test_refused_streams(name):
+    """RGB-coded planes by libjpeg's colour-space rule (libjpeg returns them unconverted, which nothing here
+    restates), a scan whose components are not in the frame's order (libjpeg refuses it too), CMYK."""
+    data = REFUSED[name](37, 53)
+    with pytest.raises(jpeg.JpegError):
+        jpeg.decode(data)
+    if name in RGB_REFUSED:  # libjpeg takes them, and not as YCbCr: the same planes marked JFIF decode otherwise
+        ycc = jpeg.decode(as_jfif(data))
+        assert not np.array_equal(reference_decode(data), ycc)
+    if name == "sos_ids_swapped":
+        with pytest.raises(OSError):
+            reference_decode(data)
+
+
+@pytest.mark.parametrize("H,W", STREAM_SHAPES)
+@pytest.mark.parametrize("sub,ss", SUBSAMPLINGS)
+def test_entropy_extremes(sub, ss, H, W):
+    """A DC difference of category 11, blocks without an EOB, restart intervals of a few bytes: each edge is
+    shown to be present in the stream, then the restatement equals libjpeg."""
+    data = encode(checkerboard(H, W), quality=100, subsampling=ss)
+    j = jpeg.parse(data)
+    assert max(abs(v) for v in luma_dc_differences(j, jpeg.decode_coefficients(j))) == 2040
+    assert np.array_equal(jpeg.decode(data), reference_decode(data))
+    data = encode(busy_noise(H, W), quality=100, subsampling=ss)
+    luma = jpeg.decode_coefficients(jpeg.parse(data))[0]
+    assert np.all(luma[:-(-H // 8), :-(-W // 8), 63] != 0)  # every block of the image (MCU padding blocks are empty)
+    assert np.array_equal(jpeg.decode(data), reference_decode(data))
+    data = encode(constant(H, W), quality=75, subsampling=ss, restart_marker_blocks=1)
+    lens = restart_interval_lengths(jpeg.parse(data))
+    assert len(lens) == -(-H // (16 if ss == 2 else 8)) * -(-W // (8 if ss == 0 else 16)) and min(lens) <= 4
+    assert np.array_equal(jpeg.decode(data), reference_decode(data))
 
 
 def _marker_stream(ns, nc=3):
