@@ -22,6 +22,8 @@
 // 2..12-px gray halo re-read comes from L2/MALL: tiles are swizzled so that
 // horizontally adjacent tiles run on the same XCD), f64 background 16 B/px
 // per batch, bits 1/8 B/px/frame.
+#include <type_traits>
+
 #include "fm_internal.h"
 
 namespace fm {
@@ -721,58 +723,65 @@ template <int KC, int RW> constexpr int np_rows() {
     return m;
 }
 
-// RW: rows per wave (8, or 16 for k_pix5's 4-wave tiles and k_pixw's 128-row bands), NWT: waves per 64-row
-// contour tile, BAND: waves of the workgroup (wv counts the band's waves; wv % NWT is the tile's slice)
-template <int KC, bool KEEP, bool TAIL, bool SDWA, int RW = RPWV, int NWT = NW, int BAND = NWT>
-__device__ __forceinline__ void chain_rows_w(const FusedArgs& a, const uint32_t* Hp, const double* atab, double (&bg)[RW],
-                                             int wv, int ln, int x0, int y0, const ChainCtx& cc, uint32_t& colbits,
-                                             uint32_t& flags) {
-    using G = PW<KC>;
-    static_assert(RW * NWT == TS && (RW == 8 || RW == 16), "rows per wave");
-    constexpr int NPR = np_rows<KC, RW>();
-    uint32_t P[NPR];
+// The chain in pieces: chain_rows_w runs them row by row; k_pix5's 8-wave frame body issues every row's LDS
+// read first and puts the tap jobs' arithmetic between the table reads and the rows that use them.
+// The wave's H pairs: NPR dwords of its column
+template <int RW, int NPR>
+__device__ __forceinline__ void chain_pairs(uint32_t (&P)[NPR], const uint32_t* Hp, int wv, int ln) {
     const uint32_t* col = Hp + (RW / 2 * wv) * TS + ln;
 #pragma unroll
     for (int i = 0; i < NPR; i++) P[i] = col[i * TS];
-    const int w = a.w;
-    const double beta = a.beta;
-    const int thr = min(max(a.thresh, -1), 255);
-    const uint32_t bias = (uint32_t)(255 - thr);
-    uint32_t tb = 0, tb2 = 0;  // rows 0..7 / 8..15 (one dot4 moves a row's bit into byte 1 of the word)
-    static_for<RW>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        uint32_t acc = 32768u;
-        static_for<G::np(j)>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, P[G::p0(j) + i]),
-                                         __builtin_bit_cast(u16x2_t, tapv2<KC>(j, i)), acc, false);
-        });
-        if (KEEP) {
-            const uint32_t kw = j < 4 ? cc.keep_lo : j < 8 ? cc.keep_hi : j < 12 ? cc.keep_2 : cc.keep_3;
-            acc &= (uint32_t)__builtin_amdgcn_sbfe((int)kw, 8 * (j & 3), 8);
-        }
-        // SDWA: the blur byte (byte 2: acc < 2^24) times 8, the table's byte offset, in ONE instruction
-        // (the table must then be static LDS at address 0); else the blur value indexes the table
-        uint32_t boff = 0, blur = 0;
-        if constexpr (SDWA)
-            asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2"
-                : "=v"(boff) : "v"(acc));
-        else
-            blur = acc >> 16;
-        const double b = bg[j];
-        const uint32_t q = __builtin_amdgcn_cvt_pk_u8_f32(fabsf(__double2float_rn(b)), 2, acc);
-        const uint32_t r = __builtin_amdgcn_sad_u8(acc, q, bias);
-        if constexpr (j < 8) tb = __builtin_amdgcn_udot4(r, (1u << j) << 8, tb, false);
-        else tb2 = __builtin_amdgcn_udot4(r, (1u << (j - 8)) << 8, tb2, false);
-        const double bl = SDWA ? *reinterpret_cast<const double*>(reinterpret_cast<const char*>(atab) + boff)
-                               : atab[blur];
-        double nb = bg_fma(b, beta, bl);
-        if (TAIL) {
-            const long long li = (long long)(y0 + RW * wv + j) * w + x0 + ln;
-            if (li >= a.acc_vec_end) nb = __dadd_rn(bl, __dmul_rn(b, beta));
-        }
-        bg[j] = nb;
+}
+// Output row j's vertical taps (+2^15: the blur value is byte 2 of acc), the keep-mask applied, and where the
+// row's blur x alpha lies in the table
+template <int KC, bool KEEP, bool SDWA, int j, int NPR>
+__device__ __forceinline__ void chain_blur(const uint32_t (&P)[NPR], const ChainCtx& cc, uint32_t& acc, uint32_t& tix) {
+    using G = PW<KC>;
+    acc = 32768u;
+    static_for<G::np(j)>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, P[G::p0(j) + i]),
+                                     __builtin_bit_cast(u16x2_t, tapv2<KC>(j, i)), acc, false);
     });
+    if (KEEP) {
+        const uint32_t kw = j < 4 ? cc.keep_lo : j < 8 ? cc.keep_hi : j < 12 ? cc.keep_2 : cc.keep_3;
+        acc &= (uint32_t)__builtin_amdgcn_sbfe((int)kw, 8 * (j & 3), 8);
+    }
+    // SDWA: the blur byte (byte 2: acc < 2^24) times 8, the table's byte offset, in ONE instruction
+    // (the table must then be static LDS at address 0); else the blur value indexes the table
+    if constexpr (SDWA)
+        asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2"
+            : "=v"(tix) : "v"(acc));
+    else
+        tix = acc >> 16;
+}
+template <bool SDWA>
+__device__ __forceinline__ double chain_tab(const double* atab, uint32_t tix) {
+    return SDWA ? *reinterpret_cast<const double*>(reinterpret_cast<const char*>(atab) + tix) : atab[tix];
+}
+// Row j's threshold bit into tb (rows 0..7) / tb2 (rows 8..15): one dot4 moves the bit into byte 1 of the word
+template <int j>
+__device__ __forceinline__ void chain_bit(uint32_t acc, double b, uint32_t bias, uint32_t& tb, uint32_t& tb2) {
+    const uint32_t q = __builtin_amdgcn_cvt_pk_u8_f32(fabsf(__double2float_rn(b)), 2, acc);
+    const uint32_t r = __builtin_amdgcn_sad_u8(acc, q, bias);
+    if constexpr (j < 8) tb = __builtin_amdgcn_udot4(r, (1u << j) << 8, tb, false);
+    else tb2 = __builtin_amdgcn_udot4(r, (1u << (j - 8)) << 8, tb2, false);
+}
+// accumulateWeighted of row j's pixel of lane ln (TAIL: the scalar form from image index acc_vec_end on)
+template <bool TAIL, int RW, int j>
+__device__ __forceinline__ double chain_bg(const FusedArgs& a, double b, double beta, double bl, int wv, int ln, int x0, int y0,
+                                           int w) {
+    double nb = bg_fma(b, beta, bl);
+    if (TAIL) {
+        const long long li = (long long)(y0 + RW * wv + j) * w + x0 + ln;
+        if (li >= a.acc_vec_end) nb = __dadd_rn(bl, __dmul_rn(b, beta));
+    }
+    return nb;
+}
+// The wave's byte (or u16) of the tile's column words and its flag word
+template <int RW, int NWT, int BAND>
+__device__ __forceinline__ void chain_flags(uint32_t tb, uint32_t tb2, int wv, const ChainCtx& cc, uint32_t& colbits,
+                                            uint32_t& flags) {
     if constexpr (RW > 8) tb |= tb2 << 8;
     tb &= cc.tbmask;
     colbits = tb;
@@ -785,6 +794,32 @@ __device__ __forceinline__ void chain_rows_w(const FusedArgs& a, const uint32_t*
     if (ws == 0 && top) fl |= FLAG_T | ((top & 3ull) ? FLAG_TL : 0u) | ((top >> 62) ? FLAG_TR : 0u);
     if (ws == NWT - 1 && bot) fl |= FLAG_B | ((bot & 3ull) ? FLAG_BL : 0u) | ((bot >> 62) ? FLAG_BR : 0u);
     flags = fl;
+}
+
+// RW: rows per wave (8, or 16 for k_pix5's 4-wave tiles and k_pixw's 128-row bands), NWT: waves per 64-row
+// contour tile, BAND: waves of the workgroup (wv counts the band's waves; wv % NWT is the tile's slice)
+template <int KC, bool KEEP, bool TAIL, bool SDWA, int RW = RPWV, int NWT = NW, int BAND = NWT>
+__device__ __forceinline__ void chain_rows_w(const FusedArgs& a, const uint32_t* Hp, const double* atab, double (&bg)[RW],
+                                             int wv, int ln, int x0, int y0, const ChainCtx& cc, uint32_t& colbits,
+                                             uint32_t& flags) {
+    static_assert(RW * NWT == TS && (RW == 8 || RW == 16), "rows per wave");
+    uint32_t P[np_rows<KC, RW>()];
+    chain_pairs<RW>(P, Hp, wv, ln);
+    const int w = a.w;
+    const double beta = a.beta;
+    const int thr = min(max(a.thresh, -1), 255);
+    const uint32_t bias = (uint32_t)(255 - thr);
+    uint32_t tb = 0, tb2 = 0;
+    static_for<RW>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        uint32_t acc, tix;
+        chain_blur<KC, KEEP, SDWA, j>(P, cc, acc, tix);
+        const double b = bg[j];
+        chain_bit<j>(acc, b, bias, tb, tb2);
+        const double bl = chain_tab<SDWA>(atab, tix);
+        bg[j] = chain_bg<TAIL, RW, j>(a, b, beta, bl, wv, ln, x0, y0, w);
+    });
+    chain_flags<RW, NWT, BAND>(tb, tb2, wv, cc, colbits, flags);
 }
 
 // Horizontal taps with the byte window folded into the constants: output k of a quad sums its
@@ -985,7 +1020,7 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
     // background of the wave's 8 rows x 64 columns -> registers (as k_pix)
     double bg[RW];
     ChainCtx cc;
-    {
+    auto load_bg = [&]() __attribute__((always_inline)) {
         const double* bgi = a.bg_in + (size_t)s * plane;
         const int x = x0 + ln;
         cc.colmask = __builtin_amdgcn_ballot_w64(x < w);
@@ -1007,11 +1042,12 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
         const long long last = (long long)(y0 + RW * wv + RW - 1) * w + x0 + TS - 1;
         cc.vec = (uint32_t)__builtin_amdgcn_readfirstlane(last < a.acc_vec_end ? 1 : 0);
         cc.tbmask = x < w ? cc.rowvalid : 0u;
-    }
 #pragma unroll
-    for (int j = 0; j < RW; j++) asm volatile("" : "+v"(bg[j]));
-    asm volatile("" : "+v"(cc.keep_lo), "+v"(cc.keep_hi));
-    if constexpr (RW > 8) asm volatile("" : "+v"(cc.keep_2), "+v"(cc.keep_3));
+        for (int j = 0; j < RW; j++) asm volatile("" : "+v"(bg[j]));
+        asm volatile("" : "+v"(cc.keep_lo), "+v"(cc.keep_hi));
+        if constexpr (RW > 8) asm volatile("" : "+v"(cc.keep_2), "+v"(cc.keep_3));
+    };
+    if constexpr (NWB != 8) load_bg();
 
     uint32_t hcs[HS<KC>::NC];
     hs_consts<KC>(hcs);
@@ -1032,57 +1068,69 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             gb[gdst[i]] = gray4(rw.v[i].x, rw.v[i].y, rw.v[i].z);
         }
     };
-    auto tap_stage = [&](const uint32_t* gb, uint16_t* Hb) __attribute__((always_inline)) {
+    // A tap job in pieces (tap_stage runs them in turn; the 8-wave frame body reads first and sums later).
+    // edge: the tile holds a REFLECT_101 quad -- a bool, or a std::bool_constant where the kind of tile is compiled in
+    auto tap_read = [&](const uint32_t* gb, int i, int row, uint32_t (&q)[3]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) q[d] = gb[hsrc[i] + row * G::GS + d];
+    };
+    auto tap_row = [&](auto edge, int i, const uint32_t (&q)[3], uint32_t (&hh)[4]) __attribute__((always_inline)) {
+        // (qv[3]: the last tap group's window reaches one byte into it, with zero taps there)
+        uint32_t qv[4] = {q[0], q[1], q[2], 0u};
+        if (edge) {
+            if (hfix[i] & 1) qv[0] = __builtin_amdgcn_perm(qv[1], qv[1], 0x01020000u);
+            if (hfix[i] & 2) qv[1] = __builtin_amdgcn_perm(qv[0], qv[0], 0x00000102u);
+            if (hfix[i] & 4) qv[2] = __builtin_amdgcn_perm(qv[1], qv[1], 0x00000102u);
+        }
+        // outputs x0+4q+k, k = 0..3: taps over gray columns x0+4q+k-2 .. +2 = bytes k+2 .. k+6 of qv
+        hh[0] = hs_tap<KC, 0>(qv, hcs);
+        hh[1] = hs_tap<KC, 1>(qv, hcs);
+        hh[2] = hs_tap<KC, 2>(qv, hcs);
+        hh[3] = hs_tap<KC, 3>(qv, hcs);
+    };
+    // both rows' sums as row pairs, by one v_perm each (every sum < 2^16) instead of a shift and an or
+    auto tap_store = [&](uint16_t* Hb, int i, const uint32_t (&h)[4], const uint32_t (&k)[4]) __attribute__((always_inline)) {
+        *reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(Hb) + hdst[i]) =
+            make_uint4(__builtin_amdgcn_perm(k[0], h[0], 0x05040100u), __builtin_amdgcn_perm(k[1], h[1], 0x05040100u),
+                       __builtin_amdgcn_perm(k[2], h[2], 0x05040100u), __builtin_amdgcn_perm(k[3], h[3], 0x05040100u));
+    };
+    auto tap_job = [&](auto edge, const uint32_t* gb, uint16_t* Hb, int i) __attribute__((always_inline)) {
+        uint32_t q[3], h[4], k[4];
+        tap_read(gb, i, 0, q);
+        tap_row(edge, i, q, h);
+        tap_read(gb, i, 1, q);  // the next gray row
+        tap_row(edge, i, q, k);
+        tap_store(Hb, i, h, k);
+    };
+    auto tap_stage = [&](auto edge, const uint32_t* gb, uint16_t* Hb) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < HJX; i++) {
             if (i == G::HJ - 1 && wv >= G::HLASTW) break;  // wave-uniform
-            // (qv[3]: the last tap group's window reaches one byte into it, with zero taps there)
-            uint32_t qv[4] = {gb[hsrc[i]], gb[hsrc[i] + 1], gb[hsrc[i] + 2], 0u};
-            if (edge_tile) {
-                if (hfix[i] & 1) qv[0] = __builtin_amdgcn_perm(qv[1], qv[1], 0x01020000u);
-                if (hfix[i] & 2) qv[1] = __builtin_amdgcn_perm(qv[0], qv[0], 0x00000102u);
-                if (hfix[i] & 4) qv[2] = __builtin_amdgcn_perm(qv[1], qv[1], 0x00000102u);
-            }
-            // outputs x0+4q+k, k = 0..3: taps over gray columns x0+4q+k-2 .. +2 = bytes k+2 .. k+6 of qv
-            const uint32_t h0 = hs_tap<KC, 0>(qv, hcs);
-            const uint32_t h1 = hs_tap<KC, 1>(qv, hcs);
-            const uint32_t h2 = hs_tap<KC, 2>(qv, hcs);
-            const uint32_t h3 = hs_tap<KC, 3>(qv, hcs);
-            // the next gray row, then both rows' sums as row pairs
-            uint32_t qw[4] = {gb[hsrc[i] + G::GS], gb[hsrc[i] + G::GS + 1], gb[hsrc[i] + G::GS + 2], 0u};
-            if (edge_tile) {
-                if (hfix[i] & 1) qw[0] = __builtin_amdgcn_perm(qw[1], qw[1], 0x01020000u);
-                if (hfix[i] & 2) qw[1] = __builtin_amdgcn_perm(qw[0], qw[0], 0x00000102u);
-                if (hfix[i] & 4) qw[2] = __builtin_amdgcn_perm(qw[1], qw[1], 0x00000102u);
-            }
-            const uint32_t k0 = hs_tap<KC, 0>(qw, hcs);
-            const uint32_t k1 = hs_tap<KC, 1>(qw, hcs);
-            const uint32_t k2 = hs_tap<KC, 2>(qw, hcs);
-            const uint32_t k3 = hs_tap<KC, 3>(qw, hcs);
-            // row pairs by one v_perm each (every sum < 2^16) instead of a shift and an or
-            *reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(Hb) + hdst[i]) =
-                make_uint4(__builtin_amdgcn_perm(k0, h0, 0x05040100u), __builtin_amdgcn_perm(k1, h1, 0x05040100u),
-                           __builtin_amdgcn_perm(k2, h2, 0x05040100u), __builtin_amdgcn_perm(k3, h3, 0x05040100u));
+            tap_job(edge, gb, Hb, i);
         }
     };
     const int t0 = a.t_begin, t1 = a.t_end;
+    // The batch's prologue and frame loop for one kind of tile (edge, as in tap_row).
     // All work after the frame's barrier: chain(t), taps(t+1), gray(t+2), then the load of frame
     // t+3 into the registers gray(t+2) just consumed (one iteration in flight).  Loads are
     // unconditional, frame indices clamped to the batch (see load).
-    load((size_t)t0 * S + s);
-    gray_stage(gray);
-    load((size_t)min(t0 + 1, t1 - 1) * S + s);
-    __syncthreads();  // atab, gray(t0)
-    tap_stage(gray, Hs);
-    if (t0 + 1 < t1) gray_stage(gray + G::GBUF);
-    load((size_t)min(t0 + 2, t1 - 1) * S + s);
+    auto run = [&](auto edge) __attribute__((always_inline)) {
+        if constexpr (NWB == 8) load_bg();  // (in each copy: the background stays in the registers it was loaded into)
+        load((size_t)t0 * S + s);
+        gray_stage(gray);
+        load((size_t)min(t0 + 1, t1 - 1) * S + s);
+        __syncthreads();  // atab, gray(t0)
+        tap_stage(edge, gray, Hs);
+        if (t0 + 1 < t1) gray_stage(gray + G::GBUF);
+        load((size_t)min(t0 + 2, t1 - 1) * S + s);
 
-    // ONE frame loop: the chain variant (keep-mask, accumulateWeighted's scalar tail) is a
-    // wave-uniform branch inside it, re-read every frame so that the loop is not unswitched.
-    // Three loop copies would give the in-flight loads different registers in each, and the
-    // wait pass would then wait for them at the top of every frame.
-    const int var0 = TAIL ? (int)(cc.vec == 0) : 0;  // (cc.vec is wave-uniform)
-    auto frame = [&](int t, int b) __attribute__((always_inline)) {
+        // ONE frame loop: the chain variant (keep-mask, accumulateWeighted's scalar tail) is a
+        // wave-uniform branch inside it, re-read every frame so that the loop is not unswitched.
+        // Three loop copies would give the in-flight loads different registers in each, and the
+        // wait pass would then wait for them at the top of every frame.
+        const int var0 = TAIL ? (int)(cc.vec == 0) : 0;  // (cc.vec is wave-uniform)
+        for (int t = t0; t < t1; t++) {
+            const int b = (t - t0) & 1;
             const size_t f = (size_t)t * S + s;
             lds_barrier();
             uint32_t colbits = 0, fl = 0;
@@ -1094,11 +1142,64 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             if constexpr (KEEP) asm volatile("" : "+v"(ccf.keep_lo), "+v"(ccf.keep_hi));
             if constexpr (KEEP && RW > 8) asm volatile("" : "+v"(ccf.keep_2), "+v"(ccf.keep_3));
             const uint32_t* Hp = reinterpret_cast<const uint32_t*>(Hs + b * G::HBUF);
-            if (!TAIL || var == 0)
-                chain_rows_w<KC, KEEP, false, true, RW, NWB>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
-            else
-                chain_rows_w<KC, KEEP, true, true, RW, NWB>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
-            if (t + 1 < t1) tap_stage(gray + (b ^ 1) * G::GBUF, Hs + (b ^ 1) * G::HBUF);
+            if constexpr (NWB == 8) {
+                const uint32_t* gn = gray + (b ^ 1) * G::GBUF;
+                uint16_t* Hn = Hs + (b ^ 1) * G::HBUF;
+                // Four waves per SIMD, barrier-locked to one phase, cover little of an LDS round trip, so the wave
+                // covers its own: behind the barrier it issues every read whose address it knows (the chain's
+                // pairs, the full tap round's gray dwords); the table reads, whose addresses are the blur values,
+                // go out four rows at a time, with one gray row's taps between a group's reads and the rows that
+                // use them.  One basic block up to the flags, pinned in this order (the scheduler would otherwise
+                // sink the table reads below the taps): chain(t), taps(t+1) and gray(t+2) are independent, and the
+                // taps run past the batch's last frame too (into an H buffer nothing reads), like gray and the loads.
+                static_assert(G::HJ == 2 && RW == 8, "one full tap round, then wave 0's partial one");
+                uint32_t P[np_rows<KC, RW>()], q0[3], q1[3], acc[4], hh[4], hk[4], tb = 0, tb2 = 0;
+                double bl[4];
+                const double beta = a.beta;
+                const uint32_t bias = (uint32_t)(255 - min(max(a.thresh, -1), 255));
+                auto blur4 = [&](auto j0) __attribute__((always_inline)) {
+                    static_for<4>([&](auto jc) {
+                        constexpr int jj = decltype(jc)::value, j = decltype(j0)::value + jj;
+                        uint32_t tix;
+                        chain_blur<KC, KEEP, true, j>(P, ccf, acc[jj], tix);
+                        bl[jj] = chain_tab<true>(atab, tix);
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                auto rows4 = [&](auto j0, auto tail) __attribute__((always_inline)) {
+                    static_for<4>([&](auto jc) {
+                        constexpr int jj = decltype(jc)::value, j = decltype(j0)::value + jj;
+                        chain_bit<j>(acc[jj], bg[j], bias, tb, tb2);
+                        bg[j] = chain_bg<decltype(tail)::value, RW, j>(a, bg[j], beta, bl[jj], wvf, ln, x0f, y0f, w);
+                    });
+                };
+                auto chain4 = [&](auto j0) __attribute__((always_inline)) {
+                    if (!TAIL || var == 0) rows4(j0, std::false_type{});
+                    else rows4(j0, std::true_type{});
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                chain_pairs<RW>(P, Hp, wvf, ln);
+                tap_read(gn, 0, 0, q0);
+                tap_read(gn, 0, 1, q1);
+                __builtin_amdgcn_sched_barrier(0);
+                blur4(std::integral_constant<int, 0>{});
+                tap_row(edge, 0, q0, hh);
+                __builtin_amdgcn_sched_barrier(0);
+                chain4(std::integral_constant<int, 0>{});
+                blur4(std::integral_constant<int, 4>{});
+                tap_row(edge, 0, q1, hk);
+                tap_store(Hn, 0, hh, hk);
+                __builtin_amdgcn_sched_barrier(0);
+                chain4(std::integral_constant<int, 4>{});
+                chain_flags<RW, NWB, NWB>(tb, tb2, wvf, ccf, colbits, fl);
+                if (wv < G::HLASTW) tap_job(edge, gn, Hn, 1);  // wave-uniform: the partial last round
+            } else {
+                if (!TAIL || var == 0)
+                    chain_rows_w<KC, KEEP, false, true, RW, NWB>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
+                else
+                    chain_rows_w<KC, KEEP, true, true, RW, NWB>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
+                if (t + 1 < t1) tap_stage(edge, gray + (b ^ 1) * G::GBUF, Hs + (b ^ 1) * G::HBUF);
+            }
             // unconditional like the loads (past the batch's end it fills a buffer nothing reads):
             // a skipped gray stage leaves the loads unwaited on that path, and the wait pass then
             // makes every frame wait for the stores below before the next loads
@@ -1115,8 +1216,17 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             }
             // unconditional (see load): past the batch's last frame it re-reads that frame
             load((size_t)min(t + 3, t1 - 1) * S + s);
+        }
     };
-    for (int t = t0; t < t1; t++) frame(t, (t - t0) & 1);
+    // Eight waves: edge and interior tiles each get their own copy, chosen before the first load (no load in
+    // flight is a phi between the copies), so the interior frame body has no REFLECT_101 branches.  Four waves
+    // (16 rows and two full tap rounds a wave: no registers to spare) keep the flag at run time.
+    if constexpr (NWB == 8) {
+        if (edge_tile) run(std::true_type{});
+        else run(std::false_type{});
+    } else {
+        run(edge_tile);
+    }
 
     double* bgo = a.bg_out + (size_t)s * plane;
     const int x = x0 + ln;
