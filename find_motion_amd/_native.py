@@ -33,7 +33,7 @@ EXPORTED = (
     "fm_mjpeg_create", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_decode", "fm_mjpeg_last_ms",
     "fm_submit_jpeg", "fm_read_frame", "fm_mjpeg_tune", "fm_frame_device", "fm_mjpeg_geometry",
     "fm_submit_streams", "fm_footprint", "fm_haar_detect_frame_list", "fm_haar_detect_frame_list_async",
-    "fm_haar_collect",
+    "fm_haar_collect", "fm_haar_last_sweep",
     "fm_jpeg_header", "fm_mjpeg_enc_create", "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_encode",
     "fm_mjpeg_encode_frame_list", "fm_mjpeg_enc_get", "fm_mjpeg_enc_coefficients", "fm_mjpeg_enc_last_ms",
     "fm_get_contour_points", "fm_last_trace_stats",
@@ -140,6 +140,7 @@ def load() -> C.CDLL:
     L.fm_haar_collect.argtypes = [vp, vp, i32, vp, i32]
     L.fm_haar_last_ms.argtypes = [vp]
     L.fm_haar_last_ms.restype = C.c_double
+    L.fm_haar_last_sweep.argtypes = [vp]
     L.fm_mjpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fm_mjpeg_destroy.argtypes = [vp]
     L.fm_mjpeg_destroy.restype = None
@@ -760,6 +761,11 @@ class CascadeClassifier:
 
     def last_ms(self) -> float:
         return float(load().fm_haar_last_ms(self._h))
+
+    def last_sweep(self) -> int:
+        """The window sweep of the last call (fm_haar_last_sweep): 0 none yet or no window, 1 the tiled
+        sweep on LDS patches, 2 the global-memory sweep of cascades whose patches do not fit in LDS."""
+        return int(load().fm_haar_last_sweep(self._h))
 
     def close(self):
         if self._h:

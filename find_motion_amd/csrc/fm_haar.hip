@@ -616,6 +616,7 @@ struct fm_haar {
     size_t cap_cand = 0;
     std::vector<int32_t> cand;  // last call's candidates of image 0 (x, y, w, h)
     double last_ms = 0.;
+    int last_sweep = 0;  // the last detection's window sweep: 0 none, 1 k_hdetect, 2 k_heval + k_heval_tail
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // FM_HAAR_TIMES (dev build): host seconds per phase over all calls -- resize setup, geometry + launches,
     // result copy + wait, post-pass -- printed at destroy
@@ -890,6 +891,7 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
     h->pend_sc.clear();
     h->pend_g = Geo{};
     h->cand.clear();
+    h->last_sweep = 0;
     // scales (detectMultiScaleNoGrouping)
     if (max_w == 0 || max_h == 0) {
         max_w = W;
@@ -998,11 +1000,13 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
         const int pw_max = (TW - 1) * 2 + h->win_w + 1, ph_max = (TH - 1) * 2 + h->win_h + 1;
         const size_t lds = (size_t)pw_max * ph_max * 4 * (h->has_tilted ? 2 : 1);
         if (FM_HAAR_TILES && lds <= 56 * 1024) {
+            h->last_sweep = 1;
             if (g.NT > 0)
                 hipLaunchKernelGGL(k_hdetect, dim3((unsigned)g.NT, (unsigned)n), dim3(TW * TH), lds, h->stream, h->d_S, h->d_Q,
                                    h->d_T, h->d_res, split, h->cd, g, pw_max);
             goto swept;
         }
+        h->last_sweep = 2;
         if ((rc = grow(h, &h->d_live, h->cap_live, (size_t)nw))) return rc;
         if (!h->d_nlive) HH(h, hipMalloc((void**)&h->d_nlive, sizeof(int)));
         HH(h, hipMemsetAsync(h->d_nlive, 0, sizeof(int), h->stream));
@@ -1243,6 +1247,8 @@ int fm_haar_candidates(const fm_haar* h, int32_t* rects, int cap) {
 }
 
 double fm_haar_last_ms(const fm_haar* h) { return h ? h->last_ms : 0.; }
+
+int fm_haar_last_sweep(const fm_haar* h) { return h ? h->last_sweep : 0; }
 
 }  // extern "C"
 

@@ -292,6 +292,10 @@ int fm_haar_collect(fm_haar* det, int32_t* rects, int cap, int32_t* counts, int 
 int fm_haar_candidates(const fm_haar* det, int32_t* rects, int cap);
 /* Device time of the last fm_haar_detect's kernels (HIP events), ms. */
 double fm_haar_last_ms(const fm_haar* det);
+/* Which window sweep the last detection queued (read-only, for tests): 0 none yet or no window to
+ * evaluate, 1 the tiled sweep on LDS integral patches, 2 the global-memory sweep that cascades whose
+ * patches do not fit in LDS take (large or large tilted windows). */
+int fm_haar_last_sweep(const fm_haar* det);
 
 /* ---- Decode side: MJPEG frames decoded on the GPU ------
  * Stands in for cv2.VideoCapture.read (find_motion.py:413, :497-506) on MJPEG

@@ -64,6 +64,20 @@ def load_frontalface():
     return cs, z
 
 
+def load_loosened():
+    """{name: dict(lam, stage_threshold, roi=(candidates, detections), small=(candidates, detections))} of
+    tests/golden/cascades_loosened.npz (make_golden_cascades_loosened.py): the cascades of CASCADE_LOOKUP
+    with haar_cases.loosen(cs, lam) thresholds on make_image(2) and make_image(2, w=128, h=80)."""
+    z = np.load(os.path.join(GOLDEN, "cascades_loosened.npz"), allow_pickle=False)
+    rects = lambda a: [tuple(int(v) for v in r) for r in a]  # noqa: E731
+    names = sorted({k.split("__")[0] for k in z.files})
+    return {n: dict(lam=float(z[n + "__lam"]), stage_threshold=z[n + "__stage_threshold"],
+                    late={im: int(z[f"{n}__{im}_late"]) for im in ("roi", "small")},  # rejected in stages >= 4
+                    **{im: (rects(z[f"{n}__{im}_candidates"]), rects(z[f"{n}__{im}_detections"]))
+                       for im in ("roi", "small")})
+            for n in names}
+
+
 def load_licence_plate_old():
     """(Cascade, [(seed, candidates, detections)]) of tests/golden/cascade_licence_plate_old.npz
     (make_golden_cascade_old.py)."""

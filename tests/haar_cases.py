@@ -8,6 +8,8 @@ optionally, tilted) features, with thresholds that pass a fraction of windows.
 """
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from find_motion_amd.cascade import THRESHOLD_EPS, Cascade
@@ -77,6 +79,46 @@ def make_cascade(seed=0, win=(20, 20), stages=4, trees=5, depth=1, tilted=False,
                    np.asarray(left, np.int32), np.asarray(right, np.int32), np.asarray(feat, np.int32),
                    np.asarray(nthr, np.float32), np.asarray(leaves, np.float32), np.stack(rects),
                    np.stack(wts).astype(np.float32), np.asarray(tl, np.uint8))
+
+
+def loosen(cs: Cascade, lam: float) -> Cascade:
+    """A copy of `cs` whose stage thresholds are lowered by lam times the stage's leaf spread:
+    thr'[s] = float32(float(thr[s]) - lam * sum over the stage's trees of (max leaf - min leaf)).
+    Features, node thresholds, trees and leaves stay as trained.  With their trained thresholds the
+    reference's cascades reject every window of a synthetic image in the first stages; loosened ones
+    give candidate lists and windows that reach every stage."""
+    thr = cs.stage_threshold.copy()
+    ti = li = 0
+    for s in range(cs.n_stages):
+        spread = 0.0
+        for _ in range(int(cs.stage_ntrees[s])):
+            nn = int(cs.tree_nodes[ti])
+            lv = cs.leaves[li:li + nn + 1]
+            spread += float(lv.max()) - float(lv.min())
+            ti += 1
+            li += nn + 1
+        thr[s] = np.float32(float(cs.stage_threshold[s]) - lam * spread)
+    return dataclasses.replace(cs, stage_threshold=thr)
+
+
+def candidates_and_results(cs: Cascade, img: np.ndarray, scale_factor=1.1):
+    """oracle.haar.detect_candidates plus the per-window results of every haar.eval_windows call it made,
+    concatenated over the scales (1 accepted, 0 rejected by stage 0, -k rejected by stage k or flat)."""
+    from oracle import haar
+
+    seen, orig = [], haar.eval_windows
+
+    def spy(*a):
+        r = orig(*a)
+        seen.append(r)
+        return r
+
+    haar.eval_windows = spy
+    try:
+        cand = haar.detect_candidates(cs, img, scale_factor)
+    finally:
+        haar.eval_windows = orig
+    return cand, (np.concatenate(seen) if seen else np.zeros(0, np.int64))
 
 
 def make_image(seed=0, w=300, h=169, squares=4, channels=3) -> np.ndarray:

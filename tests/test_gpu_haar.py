@@ -1,9 +1,11 @@
 """GPU parity of the object-ROI stage (fm_haar_*) against
 oracle/haar.py: the ungrouped candidate rects of detectMultiScaleNoGrouping and
 the grouped detections must be identical (integer rects, same order).
-Cascades and images are synthetic (tests/haar_cases.py); the reference's
-cascade files are not on the GPU box.  Parity vs OpenCV itself: unpinned.
+Images are synthetic; cascades are synthetic too (tests/haar_cases.py) or the
+reference's own files, committed as fixtures (tests/golden/haarcascades), with
+their trained or loosened stage thresholds.  Parity vs OpenCV itself: unpinned.
 """
+import functools
 import glob
 import os
 
@@ -11,7 +13,8 @@ import numpy as np
 import pytest
 
 from find_motion_amd import CascadeClassifier
-from haar_cases import make_cascade, make_image
+from find_motion_amd.cascade import CASCADE_LOOKUP
+from haar_cases import candidates_and_results, loosen, make_cascade, make_image
 import oracle
 from oracle import haar
 
@@ -282,6 +285,139 @@ def test_old_format_licence_plate_cascade():
         got = det.detectMultiScale(plate_image(seed), scaleFactor=1.1, minNeighbors=5)
         assert [tuple(r) for r in det.candidates().tolist()] == cand, seed
         assert [tuple(r) for r in np.asarray(got).reshape(-1, 4).tolist()] == dets, seed
+    det.close()
+
+
+# --- every cascade the drop-in can load, with loosened thresholds (tests/golden/cascades_loosened.npz) ---
+
+@pytest.mark.parametrize("name", list(CASCADE_LOOKUP))
+def test_loosened_reference_cascades(name):
+    """The nine cascades of CASCADE_LOOKUP -- tilted features, multi-node trees, 14x28 and 19x23 windows, a
+    47-stage cascade of 8,468 stumps among them -- with stage thresholds lowered until the synthetic images
+    give candidates and windows reach the late stages (haar_cases.loosen; features, trees and leaves stay
+    the reference's).  Candidates and grouped detections equal the fixture's (oracle/haar.py, run by
+    tests/golden/make_golden_cascades_loosened.py) on the 300x169 and the 128x80 image, and a batch of
+    three 300x169 images gives each image's detections (blockIdx.y > 0 with real stage sizes)."""
+    from find_motion_amd.cascade import parse
+    from golden_cases import cascade_xml, load_loosened
+
+    e = load_loosened()[name]
+    cs = loosen(parse(cascade_xml(name)), e["lam"])
+    assert np.array_equal(cs.stage_threshold, e["stage_threshold"])
+    det = CascadeClassifier(cs)
+    imgs = {"roi": make_image(2), "small": make_image(2, w=128, h=80)}
+    for key, img in imgs.items():
+        cand, dets = e[key]
+        got = det.detectMultiScale(img, scaleFactor=1.1, minNeighbors=3)
+        assert [tuple(r) for r in det.candidates().tolist()] == cand, key
+        assert [tuple(r) for r in np.asarray(got).reshape(-1, 4).tolist()] == dets, key
+        assert det.last_sweep() == 1, key  # all nine windows fit the tiled sweep's LDS patches
+    assert len(e["roi"][0]) >= 20 and len(e["roi"][1]) >= 1 and len(e["small"][0]) >= 4
+    batch = det.detect_batch(np.stack([imgs["roi"]] * 3), 1.1, 3)
+    for i in range(3):
+        assert [tuple(r) for r in batch[i].tolist()] == e["roi"][1], i
+    assert [tuple(r) for r in det.candidates().tolist()] == e["roi"][0]
+    det.close()
+
+
+# --- which window sweep ran; short cascades ------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _flat_windows(win, size):
+    """Windows of make_image(2, *size) that setWindow refuses (the -1s of a one-stage cascade)."""
+    _, res = candidates_and_results(make_cascade(1, win=win, stages=1), make_image(2, w=size[0], h=size[1]), 1.1)
+    return int((res == -1).sum())
+
+
+def _check_against_live_oracle(cs, size, sweep, one_stage=False):
+    """Candidates and grouped detections (minNeighbors 3) equal oracle/haar.py's, the expected sweep ran,
+    and the comparison is not vacuous: the oracle's per-window results hold accepted windows (at least
+    50, at most half of all), windows stage 0 rejects and windows a later stage rejects (flat windows,
+    which eval_windows reports like a stage-1 rejection, are not counted as such).  Returns the counts."""
+    img = make_image(2, w=size[0], h=size[1])
+    ref_c, res = candidates_and_results(cs, img, 1.1)
+    acc, zero = int((res == 1).sum()), int((res == 0).sum())
+    later = int((res < 0).sum()) - _flat_windows((cs.win_w, cs.win_h), size)
+    print(f"windows {len(res)}: accepted {acc}, rejected by stage 0 {zero}, rejected later {later}, "
+          f"candidates {len(ref_c)}")
+    if one_stage:
+        assert acc > 0 and zero > 0 and later == 0
+    else:
+        assert 50 <= acc <= len(res) // 2 and zero > 0 and later > 0
+    det = CascadeClassifier(cs)
+    assert det.last_sweep() == 0  # nothing detected yet
+    got = det.detectMultiScale(img, scaleFactor=1.1, minNeighbors=3)
+    assert det.last_sweep() == sweep
+    assert [tuple(r) for r in det.candidates().tolist()] == ref_c
+    assert [tuple(r) for r in np.asarray(got).reshape(-1, 4).tolist()] == haar.group_rectangles(ref_c, 3)
+    if sweep == 2:
+        # two different images in one call: the global-memory sweep's window index spans the batch, and
+        # its survivor list mixes the images' windows
+        flip = np.ascontiguousarray(img[::-1])
+        both = det.detect_batch(np.stack([flip, img]), 1.1, 0)  # minNeighbors 0: every candidate of both
+        ref_f = haar.detect_candidates(cs, flip, 1.1)
+        assert ref_f != ref_c and len(ref_f) >= 50
+        assert [tuple(r) for r in both[0].tolist()] == ref_f
+        assert [tuple(r) for r in both[1].tolist()] == ref_c
+        assert det.last_sweep() == 2
+    det.close()
+    return acc, zero, later
+
+
+# windows whose integral patches, (31 + w) * (31 + h) * 4 bytes (twice that with tilted features), exceed the
+# 56 KiB the tiled sweep may take run the global-memory sweep: per-window results on make_image(2) are
+#   100x100 stumps, 6 stages:        8,984 windows, 3,065 accepted, 5,442 by stage 0,   477 later (stage 5)
+#   100x100 stumps, 3 stages:        8,984 windows, 2,451 accepted, 5,442 by stage 0, 1,091 later (stage 2)
+#   60x60 tilted depth-2, 6 stages: 26,437 windows, 1,045 accepted, 15,785 by stage 0, 7,293 later (stages 2, 4)
+#   60x60 tilted stumps, 6 stages:  26,437 windows, 6,170 accepted, 15,785 by stage 0, 2,168 later (stages 3, 5)
+#   20x20 tilted depth-2, 4 stages: 75,643 windows, 2,280 accepted, 25,216 by stage 0, 10,795 later (stage 2)
+SWEEP_CASES = [
+    (1, 0.38, dict(win=(100, 100), stages=6), 2),                          # head + tail launch
+    (3, 0.38, dict(win=(100, 100), stages=3), 2),                          # no tail: the head writes accepts
+    (1, 0.38, dict(win=(60, 60), stages=6, depth=2, tilted=True), 2),      # 91 * 91 * 8 bytes > 56 KiB
+    (6, 0.38, dict(win=(60, 60), stages=6, tilted=True), 2),
+    (1, 0.38, dict(depth=2, tilted=True), 1),                              # 20x20: the tiled sweep
+]
+
+
+@pytest.mark.parametrize("seed,tight,kw,sweep", SWEEP_CASES)
+def test_global_memory_sweep_matches_oracle(seed, tight, kw, sweep):
+    """k_heval + k_heval_tail (set_window, feature() on the global integral images, the stump-prefetch
+    branch of run_stages, the survivor list) run only for windows too large for LDS patches; no cascade
+    of the reference is, so these synthetic ones are the coverage, and last_sweep() keeps a change of the
+    LDS limit from moving it silently.  The 20x20 companion must stay on the tiled sweep."""
+    _check_against_live_oracle(make_cascade(seed, tight=tight, **kw), (300, 169), sweep)
+
+
+# k_hdetect forms its phases from split (4) and n_stages: one stage (a single phase, no tail), two (split
+# clamped to 2; the bench's cascade), three (three head phases, no tail), five (a one-stage tail).
+# Per-window results on make_image(2, w=173, h=97), 17,435 windows, 7,008 rejected by stage 0, 6,277 flat:
+#   1 stage stumps: 4,150 accepted            2 stages stumps: 3,715 accepted, 435 later
+#   2 stages tilted depth-2: 1,643 / 2,507    3 stages stumps: 3,096 / 1,054    3 tilted depth-2: 864 / 3,286
+#   5 stages stumps: 3,004 / 1,146 (92 by the tail stage)    5 tilted depth-2: 787 / 3,363 (77 by the tail)
+SHORT_CASES = [
+    (1, 0.38, dict(stages=1)),
+    (5, 0.50, dict(stages=2)),
+    (4, 0.47, dict(stages=2, depth=2, tilted=True)),
+    (2, 0.38, dict(stages=3)),
+    (1, 0.38, dict(stages=3, depth=2, tilted=True)),
+    (2, 0.38, dict(stages=5)),
+    (1, 0.38, dict(stages=5, depth=2, tilted=True)),
+]
+
+
+@pytest.mark.parametrize("seed,tight,kw", SHORT_CASES)
+def test_short_cascades_on_the_tiled_sweep(seed, tight, kw):
+    _check_against_live_oracle(make_cascade(seed, tight=tight, **kw), (173, 97), 1, one_stage=kw["stages"] == 1)
+
+
+def test_last_sweep_is_zero_without_windows():
+    cs = make_cascade(1, tight=0.41, depth=2)
+    det = CascadeClassifier(cs)
+    det.detectMultiScale(make_image(2), 1.1, 3)
+    assert det.last_sweep() == 1
+    assert len(det.detectMultiScale(np.ascontiguousarray(make_image(7, w=40, h=40)[:, :19]), 1.1, 1)) == 0
+    assert det.last_sweep() == 0  # narrower than the window: no window, no sweep
     det.close()
 
 
