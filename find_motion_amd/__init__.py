@@ -37,6 +37,7 @@ from ._native import (  # noqa: F401
     MJpegEncoder,
     MotionEngine,
     NativeLibraryMissing,
+    YoloDetector,
     rasterize_masks,
     yuv_frame_bytes,
 )

@@ -38,7 +38,12 @@ EXPORTED = (
     "fm_mjpeg_encode_frame_list", "fm_mjpeg_enc_get", "fm_mjpeg_enc_coefficients", "fm_mjpeg_enc_last_ms",
     "fm_get_contour_points", "fm_last_trace_stats",
     "fm_yuv_frame_bytes", "fm_submit_yuv", "fm_submit_yuv_list",
+    "fm_yolo_create", "fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_layer_shape", "fm_yolo_detect_frames",
+    "fm_yolo_detect_frame_list", "fm_yolo_forward", "fm_yolo_decode", "fm_yolo_layer_output",
+    "fm_yolo_route_in_place", "fm_yolo_last_ms",
 )
+YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
+YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
 # fm_yuv_layout.format (FM_YUV_*), by fourcc
 YUV_NV12, YUV_I420, YUV_YUY2, YUV_UYVY = 0, 1, 2, 3
 YUV_FORMATS = {"NV12": YUV_NV12, "I420": YUV_I420, "IYUV": YUV_I420, "YUY2": YUV_YUY2, "YUYV": YUV_YUY2,
@@ -68,6 +73,19 @@ class FMHaarDesc(C.Structure):
                 ("node_left", C.c_void_p), ("node_right", C.c_void_p), ("node_feature", C.c_void_p),
                 ("node_threshold", C.c_void_p), ("leaves", C.c_void_p), ("feat_rects", C.c_void_p),
                 ("feat_weights", C.c_void_p), ("feat_tilted", C.c_void_p)]
+
+
+class FMYoloLayer(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("filters", C.c_int32), ("size", C.c_int32), ("stride", C.c_int32),
+                ("pad", C.c_int32), ("leaky", C.c_int32), ("src", C.c_int32 * 2), ("weight_ofs", C.c_int64),
+                ("bias_ofs", C.c_int64), ("n_mask", C.c_int32), ("anchor_ofs", C.c_int32)]
+
+
+class FMYoloDesc(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("layers", C.POINTER(FMYoloLayer)), ("weights", C.c_void_p),
+                ("n_weights", C.c_int64), ("biases", C.c_void_p), ("n_biases", C.c_int64), ("anchors", C.c_void_p),
+                ("n_anchors", C.c_int32), ("channels", C.c_int32), ("net_w", C.c_int32), ("net_h", C.c_int32),
+                ("classes", C.c_int32), ("max_frames", C.c_int32), ("zero_thresh", C.c_float)]
 
 
 class FMYuvLayout(C.Structure):
@@ -170,8 +188,22 @@ def load() -> C.CDLL:
     L.fm_mjpeg_enc_coefficients.argtypes = [vp, i32, vp, C.c_size_t]
     L.fm_mjpeg_enc_last_ms.argtypes = [vp]
     L.fm_mjpeg_enc_last_ms.restype = C.c_double
+    L.fm_yolo_create.argtypes = [i32, C.POINTER(FMYoloDesc), C.POINTER(vp)]
+    L.fm_yolo_destroy.argtypes = [vp]
+    L.fm_yolo_destroy.restype = None
+    L.fm_yolo_last_error.argtypes = [vp]
+    L.fm_yolo_last_error.restype = C.c_char_p
+    L.fm_yolo_layer_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.fm_yolo_detect_frames.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, i32, vp, vp]
+    L.fm_yolo_detect_frame_list.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, i32, vp, vp]
+    L.fm_yolo_forward.argtypes = [vp, vp, i32]
+    L.fm_yolo_decode.argtypes = [vp, i32, C.c_float, vp, i32, vp]
+    L.fm_yolo_layer_output.argtypes = [vp, i32, vp, C.c_size_t]
+    L.fm_yolo_route_in_place.argtypes = [vp, i32]
+    L.fm_yolo_last_ms.argtypes = [vp, vp]
+    L.fm_yolo_last_ms.restype = C.c_double
     for name in EXPORTED:
-        if name not in ("fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
+        if name not in ("fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_last_ms", "fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
                         "fm_haar_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
                         "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_enc_last_ms"):
             getattr(L, name).restype = i32
@@ -770,6 +802,212 @@ class CascadeClassifier:
     def close(self):
         if self._h:
             load().fm_haar_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def yolo_desc(layers, params, net_w=416, net_h=416, max_frames=1, zero_thresh=0.2, channels=None):
+    """darknet.parse_cfg's layer list + darknet.load_weights' parameters -> (FMYoloDesc, keep-alive list).
+    The description is passed on as parsed: fm_yolo_create does the checking."""
+    from . import darknet as dk
+    kinds = {dk.CONV: YOLO_CONV, dk.MAXPOOL: YOLO_MAXPOOL, dk.UPSAMPLE: YOLO_UPSAMPLE, dk.ROUTE: YOLO_ROUTE,
+             dk.SHORTCUT: YOLO_SHORTCUT, dk.YOLO: YOLO_HEAD}
+    arr = (FMYoloLayer * max(len(layers), 1))()
+    ws, bs, anchors = [], [], []
+    nw = nb = 0
+    classes = 0
+    for i, ly in enumerate(layers):
+        q = arr[i]
+        q.kind = kinds.get(ly["kind"], -1)
+        q.src[0] = q.src[1] = -1
+        if ly["kind"] == dk.CONV:
+            w, b = params[i]
+            w, b = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)
+            q.filters, q.size, q.stride, q.pad = ly["filters"], ly["size"], ly["stride"], ly["pad"]
+            q.leaky = 1 if ly["activation"] == "leaky" else 0
+            q.weight_ofs, q.bias_ofs = nw, nb
+            ws.append(w.ravel())
+            bs.append(b.ravel())
+            nw += w.size
+            nb += b.size
+        elif ly["kind"] == dk.MAXPOOL:
+            q.size, q.stride = ly["size"], ly["stride"]
+        elif ly["kind"] == dk.UPSAMPLE:
+            q.stride = ly["stride"]
+        elif ly["kind"] == dk.ROUTE:
+            for k, s in enumerate(ly["layers"][:2]):
+                q.src[k] = s
+        elif ly["kind"] == dk.SHORTCUT:
+            q.src[0] = ly["from"]
+        elif ly["kind"] == dk.YOLO:
+            q.n_mask, q.anchor_ofs = len(ly["mask"]), len(anchors)
+            anchors.extend(ly["anchors"][m] for m in ly["mask"])
+            classes = ly["classes"] if classes in (0, ly["classes"]) else -1
+    wv = np.concatenate(ws).astype(np.float32) if ws else np.zeros(0, np.float32)
+    bv = np.concatenate(bs).astype(np.float32) if bs else np.zeros(0, np.float32)
+    av = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(-1, 2))
+    if channels is None:
+        channels = layers[0]["in_c"] if layers else 3
+    d = FMYoloDesc(len(layers), arr, _ptr(wv), wv.size, _ptr(bv), bv.size, _ptr(av), len(av), int(channels),
+                   int(net_w), int(net_h), int(classes), int(max_frames), float(zero_thresh))
+    return d, [arr, wv, bv, av]
+
+
+class YoloDetector:
+    """cvlib.detect_common_objects on the GPU from the user's Darknet files (find_motion.py:733-741).
+
+    `YoloDetector.from_dir(dir, tiny)` reads yolov3[-tiny].cfg, yolov3[-tiny].weights and
+    yolov3_classes.txt (find_motion_amd.darknet); `detect_frames` returns cvlib's (bboxes, labels, confs)
+    per frame.  The network input is 416 x 416 whatever the cfg's [net] says, as cvlib passes it."""
+
+    def __init__(self, layers, params, classes, net_w: int = 416, net_h: int = 416, max_frames: int = 1,
+                 zero_thresh: float = 0.2, device: int = 0, channels=None):
+        L = load()
+        self.layers, self.classes = layers, list(classes)
+        self.net_w, self.net_h, self.max_frames = int(net_w), int(net_h), int(max_frames)
+        d, self._keep = yolo_desc(layers, params, net_w, net_h, max_frames, zero_thresh, channels)
+        h = C.c_void_p()
+        rc = L.fm_yolo_create(int(device), C.byref(d), C.byref(h))
+        self._h = h
+        if rc != FM_OK:
+            msg = L.fm_yolo_last_error(h).decode() if h else ""
+            L.fm_yolo_destroy(h)
+            self._h = None
+            raise FMError(rc, f"fm_yolo_create: {msg}")
+        rows = C.c_int()
+        L.fm_yolo_layer_shape(self._h, -1, None, None, None, C.byref(rows))
+        self.rows = rows.value  # candidate rows of all heads, per frame
+
+    @classmethod
+    def from_dir(cls, directory, tiny: bool = False, device: int = 0, **kw):
+        from . import darknet as dk
+        stem = os.path.join(directory, "yolov3-tiny" if tiny else "yolov3")
+        with open(stem + ".cfg", "r") as f:
+            _net, layers = dk.parse_cfg(f.read())
+        params = dk.load_weights(stem + ".weights", layers)
+        classes = dk.load_classes(os.path.join(directory, "yolov3_classes.txt"))
+        nc = {ly["classes"] for ly in layers if ly["kind"] == dk.YOLO}
+        if not nc or any(n > len(classes) for n in nc):
+            raise ValueError(f"{stem}.cfg: heads of {sorted(nc)} classes, {len(classes)} names in yolov3_classes.txt")
+        return cls(layers, params, classes, device=device, **kw)
+
+    def _fail(self, rc: int, what: str):
+        raise FMError(rc, f"{what}: {load().fm_yolo_last_error(self._h).decode()}")
+
+    def _run(self, call, n: int, what: str):
+        """call(cand, cap, counts) until the rows fit: a list of [k, 9] float32 arrays, one per frame."""
+        cap = 64
+        while True:
+            cand = np.zeros((n, cap, YOLO_CAND), np.float32)
+            counts = np.zeros(n, np.int32)
+            rc = call(_ptr(cand), cap, _ptr(counts))
+            if rc != FM_OK:
+                self._fail(rc, what)
+            if counts.max(initial=0) <= cap:
+                return [cand[i, :counts[i]].copy() for i in range(n)]
+            cap = int(counts.max())
+
+    def candidates(self, frames, width: int = 300, confidence: float = 0.25):
+        """The decoded rows above the confidence of each frame, sorted by (head, row), and the ROI height.
+        `frames` as CascadeClassifier.detect_frames takes them: a host array [n, H, W, 3] BGR, a contiguous
+        uint8 torch tensor on the detector's GPU, or a tuple (device address, n, H, W)."""
+        L = load()
+        rh = C.c_int32()
+        if isinstance(frames, tuple):
+            ptr, n, H, W = frames
+            fr, ptr, on_dev = None, C.c_void_p(ptr), 1
+        elif getattr(frames, "is_cuda", False):
+            import torch
+            if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+                raise ValueError("device frames must be a contiguous uint8 tensor [n, H, W, 3]")
+            torch.cuda.current_stream(frames.device).synchronize()
+            fr, ptr, on_dev = frames, C.c_void_p(frames.data_ptr()), 1
+            n, H, W = frames.shape[:3]
+        else:
+            fr = np.ascontiguousarray(frames, np.uint8)
+            if fr.ndim != 4 or fr.shape[3] != 3:
+                raise ValueError("frames must be [n, H, W, 3]")
+            ptr, on_dev = _ptr(fr), 0
+            n, H, W = fr.shape[:3]
+        n, H, W = int(n), int(H), int(W)
+        rows = self._run(lambda c, cap, k: L.fm_yolo_detect_frames(self._h, ptr, n, H, W, on_dev, int(width),
+                                                                   float(confidence), c, cap, k, C.byref(rh)),
+                         n, "fm_yolo_detect_frames")
+        return rows, rh.value
+
+    def candidates_frame_list(self, ptrs, H: int, W: int, width: int = 300, confidence: float = 0.25):
+        """`candidates` over frames in device memory at separate addresses (fm_yolo_detect_frame_list)."""
+        L = load()
+        n = len(ptrs)
+        arr = (C.c_void_p * n)(*[int(p) for p in ptrs])
+        rh = C.c_int32()
+        rows = self._run(lambda c, cap, k: L.fm_yolo_detect_frame_list(self._h, C.cast(arr, C.c_void_p), n, int(H),
+                                                                       int(W), int(width), float(confidence), c, cap,
+                                                                       k, C.byref(rh)),
+                         n, "fm_yolo_detect_frame_list")
+        return rows, rh.value
+
+    def detect_frames(self, frames, width: int = 300, confidence: float = 0.25, nms: float = 0.3):
+        """cvlib.detect_common_objects(imutils.resize(frame, width=width), confidence, nms) per frame:
+        a list of (bboxes [x1, y1, x2, y2], labels, confs)."""
+        from . import darknet as dk
+        rows, rh = self.candidates(frames, width, confidence)
+        return [dk.detections(r, int(width), rh, self.classes, confidence, nms) for r in rows]
+
+    def detect_frame_list(self, ptrs, H: int, W: int, width: int = 300, confidence: float = 0.25, nms: float = 0.3):
+        from . import darknet as dk
+        rows, rh = self.candidates_frame_list(ptrs, H, W, width, confidence)
+        return [dk.detections(r, int(width), rh, self.classes, confidence, nms) for r in rows]
+
+    # -- parity tests ------------------------------------------------------------
+    def forward(self, blob) -> None:
+        """The network alone on a host blob [n, channels, net_h, net_w] float32 (fm_yolo_forward)."""
+        b = np.ascontiguousarray(blob, np.float32)
+        rc = load().fm_yolo_forward(self._h, _ptr(b), int(b.shape[0]))
+        if rc != FM_OK:
+            self._fail(rc, "fm_yolo_forward")
+
+    def decode(self, n: int, confidence: float = 0.25):
+        """The decode alone on the last call's head tensors (fm_yolo_decode)."""
+        L = load()
+        return self._run(lambda c, cap, k: L.fm_yolo_decode(self._h, int(n), float(confidence), c, cap, k), int(n),
+                         "fm_yolo_decode")
+
+    def layer_shape(self, layer: int):
+        c, h, w = C.c_int(), C.c_int(), C.c_int()
+        if load().fm_yolo_layer_shape(self._h, int(layer), C.byref(c), C.byref(h), C.byref(w), None) != FM_OK:
+            raise IndexError(f"layer {layer}")
+        return c.value, h.value, w.value
+
+    def layer_output(self, layer: int, n: int) -> np.ndarray:
+        """Layer `layer`'s activations [n, c, h, w] of the last call over n frames (-1: the network input)."""
+        out = np.zeros((int(n),) + self.layer_shape(layer), np.float32)
+        rc = load().fm_yolo_layer_output(self._h, int(layer), _ptr(out), out.size)
+        if rc < 0:
+            self._fail(rc, "fm_yolo_layer_output")
+        if rc != out.size:
+            raise FMError(FM_ESTATE, f"fm_yolo_layer_output: the last call ran {rc // max(out[0].size, 1)} frames, not {n}")
+        return out
+
+    def route_in_place(self, layer: int) -> bool:
+        rc = load().fm_yolo_route_in_place(self._h, int(layer))
+        if rc < 0:
+            raise IndexError(f"layer {layer} is not a route")
+        return bool(rc)
+
+    def last_ms(self) -> dict:
+        st = (C.c_double * 3)()
+        total = float(load().fm_yolo_last_ms(self._h, C.cast(st, C.c_void_p)))
+        return {"blob": st[0], "network": st[1], "decode": st[2], "total": total}
+
+    def close(self):
+        if self._h:
+            load().fm_yolo_destroy(self._h)
             self._h = None
 
     def __del__(self):

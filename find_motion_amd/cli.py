@@ -53,6 +53,10 @@ def get_args(parser: ArgumentParser) -> None:
     parser.add_argument("--cascade-object", "-O", nargs="*", type=str,
                         help="Specific types of objects to detect using haar cascades (slow!)")
     parser.add_argument("--yolo-tiny", "-yt", action="store_true", help="Use fast common object detection")
+    parser.add_argument("--yolo-dir", default=None,
+                        help="Directory with cvlib's yolov3[-tiny].cfg, yolov3[-tiny].weights and yolov3_classes.txt "
+                             "(~/.cvlib/object_detection/yolo/yolov3): tag written frames with YOLOv3 on the GPU "
+                             "(default: $FM_YOLO_DIR, else off)")
     parser.add_argument("--blur-scale", "-b", type=int, default=20,
                         help="Scale of gaussian blur size compared to video width (used as 1/blur_scale)")
     parser.add_argument("--box-size", "-B", type=int, default=100, help="Pixel size to scale the video to for processing")
@@ -211,7 +215,7 @@ def _job_kwargs(args) -> dict:
                 blur_scale=args.blur_scale, box_size=args.box_size, min_box_scale=args.min_box_scale,
                 threshold=args.threshold, avg=args.avg, fps=args.fps, min_time=args.mintime,
                 cache_time=args.cachetime, multiprocess=args.processes > 1, cascades=args.cascade_object,
-                yolo_tiny=args.yolo_tiny, gpu_decode=getattr(args, "gpu_decode", None),
+                yolo_tiny=args.yolo_tiny, yolo_dir=getattr(args, "yolo_dir", None), gpu_decode=getattr(args, "gpu_decode", None),
                 gpu_encode=getattr(args, "gpu_encode", None),
                 contour_points=bool(getattr(args, "contour_points", False)))
 

@@ -53,7 +53,10 @@ results and the decisions are identical for any batch -- only ref_frame is
 then observed at batch boundaries), capture (a ready capture object),
 gpu_decode, gpu_encode (see above), contour_points (every frame.contours[i]
 then carries its CHAIN_APPROX_SIMPLE points, traced on the GPU: np.asarray(c)
-is the (n, 1, 2) int32 array cv2.findContours returns at fm.py:269-272).
+is the (n, 1, 2) int32 array cv2.findContours returns at fm.py:269-272),
+yolo_dir (the directory of cvlib's yolov3 files, default $FM_YOLO_DIR: find_objects
+then tags frames with YOLOv3 on the GPU as fm.py:733-741 does with cvlib; without
+it that stage is off).
 
 There is no CPU fallback: without the HIP library this module raises
 NativeLibraryMissing at VideoMotion construction.
@@ -71,8 +74,8 @@ from collections import deque
 import numpy as np
 
 from . import videoio
-from ._native import (PLANE_BLUR, PLANE_DELTA, PLANE_GRAY, CascadeClassifier, MJpegDecoder, MotionEngine,
-                      rasterize_masks)
+from ._native import (PLANE_BLUR, PLANE_DELTA, PLANE_GRAY, CascadeClassifier, FMError, MJpegDecoder, MotionEngine,
+                      YoloDetector, rasterize_masks)
 from .feeder import BatchFeeder
 
 log = logging.getLogger("find_motion_amd")
@@ -83,6 +86,7 @@ GREEN = (0, 255, 0)
 
 # fm.py:104-122
 _CASCADES: dict = {}  # (path, device) -> CascadeClassifier
+_YOLOS: dict = {}  # (cfg path, weights path, names path, device) -> YoloDetector
 
 CASCADE_LOOKUP = {
     "frontalcatface": "Cat 1",
@@ -230,7 +234,7 @@ class VideoMotion:
                  device: int = 0, batch: int = 1, capture=None, engine: MotionEngine = None,
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
                  pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None,
-                 contour_points: bool = False) -> None:
+                 contour_points: bool = False, yolo_dir: str = None) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -264,6 +268,8 @@ class VideoMotion:
         self.cascades = None
         self._load_cascades()
         self.tiny = yolo_tiny
+        self.yolo_dir = yolo_dir if yolo_dir is not None else (os.environ.get("FM_YOLO_DIR") or None)
+        self.yolo = None  # the YOLOv3 detector (_load_yolo), only with a yolo_dir
         self.amount_of_frames = -1
         self.frame_width = -1
         self.frame_height = -1
@@ -362,7 +368,27 @@ class VideoMotion:
         if self.mask_areas:
             h, w = self._engine.work_shape
             self._engine.set_mask(self._stream, rasterize_masks(h, w, self.scale, self.mask_areas))
+        if self.yolo_dir:
+            self._load_yolo()
         return True
+
+    def _load_yolo(self) -> None:
+        """cvlib's model files (yolov3[-tiny].cfg, yolov3[-tiny].weights, yolov3_classes.txt) from `yolo_dir`,
+        run on the GPU (find_motion_amd.YoloDetector).  A missing or refused file leaves the stage off."""
+        stem = os.path.join(self.yolo_dir, "yolov3-tiny" if self.tiny else "yolov3")
+        files = (stem + ".cfg", stem + ".weights", os.path.join(self.yolo_dir, "yolov3_classes.txt"))
+        missing = [f for f in files if not os.path.isfile(f)]
+        if missing:
+            self.log.warning("YOLO files not found: %s: object detection skipped", missing)
+            return
+        key = tuple(os.path.realpath(f) for f in files) + (self.device,)
+        if key not in _YOLOS:  # one device copy per file set and device, shared by every stream
+            try:
+                _YOLOS[key] = YoloDetector.from_dir(self.yolo_dir, tiny=self.tiny, device=self.device)
+            except (ValueError, OSError, FMError) as e:
+                self.log.warning("YOLO files in %s refused (%s): object detection skipped", self.yolo_dir, e)
+                return
+        self.yolo = _YOLOS[key]
 
     def _get_video_info(self) -> None:
         """fm.py:427-444"""
@@ -586,7 +612,7 @@ class VideoMotion:
         """fm.py:611-616"""
         return [(int(a[0] * scale), int(a[1] * scale)) for a in area]
 
-    # -- objects (fm.py:703-762): Haar needs OpenCV; cvlib YOLO is not available offline
+    # -- objects (fm.py:703-762): Haar cascades when asked for, YOLOv3 with a yolo_dir
     def find_objects(self, frame: VideoFrame = None, width=300, skip=15, scaleFactor=1.1, minNeighbours=5,
                      confidence=0.25) -> typing.Set[str]:
         frame = self.current_frame if frame is None else frame
@@ -595,7 +621,7 @@ class VideoMotion:
             return set()
         self.object_counter = 0
         self.last_objects = {}
-        if self.cascades:
+        if self.cascades or self.yolo is not None:
             # frame.resized = imutils.resize(frame.raw, width=width) happens on the device inside
             # detect_frames (INTER_AREA); rects are in ROI coordinates as in the reference
             lazy = getattr(frame, "_raw", True) is None and getattr(frame, "_load", None) is not None
@@ -612,6 +638,11 @@ class VideoMotion:
                 found = cascade.detect_frames(src, width, scaleFactor, minNeighbours)[0]
                 for rect in found:
                     self.last_objects.setdefault(title, []).append(VideoMotion.make_area_from_rect(tuple(int(v) for v in rect)))
+            if self.yolo is not None:
+                # cv.detect_common_objects(frame.resized, confidence=confidence, model=...), fm.py:733-741
+                bbox, labels, _conf = self.yolo.detect_frames(src, width, confidence)[0]
+                for box, label in zip(bbox, labels):
+                    self.last_objects.setdefault(label, []).append(VideoMotion.make_area_from_box(tuple(box)))
         return set(self.last_objects.keys())
 
     # -- display (fm.py:765-821): only with OpenCV and --show

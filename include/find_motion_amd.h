@@ -457,6 +457,85 @@ int fm_mjpeg_enc_coefficients(fm_mjpeg_enc* enc, int frame, int16_t* out, size_t
  * round trips that size the buffers lie inside it), ms. */
 double fm_mjpeg_enc_last_ms(const fm_mjpeg_enc* enc);
 
+/* ---- YOLOv3 object stage ----------------------------------
+ * Replaces cvlib.detect_common_objects(frame.resized, confidence=0.25,
+ * model='yolov3[-tiny]') at find_motion.py:733-741: blobFromImage, the Darknet
+ * network in f32 (convolutions as implicit GEMMs on the f32-input MFMA) and the
+ * region layers' decode.  find_motion_amd/darknet.py reads the cfg and weights
+ * files into this description; boxes and NMS are the caller's (a few dozen rows).
+ * Independent of fm_ctx: one detector per model and device. */
+#define FM_YOLO_CONV 0
+#define FM_YOLO_MAXPOOL 1
+#define FM_YOLO_UPSAMPLE 2
+#define FM_YOLO_ROUTE 3
+#define FM_YOLO_SHORTCUT 4
+#define FM_YOLO_HEAD 5
+#define FM_YOLO_CAND 9 /* floats per candidate: head, row, bx, by, bw, bh, obj, class, p */
+typedef struct fm_yolo fm_yolo;
+typedef struct fm_yolo_layer {
+    int32_t kind;      /* FM_YOLO_* */
+    int32_t filters;   /* conv: output channels */
+    int32_t size;      /* conv: 1 or 3; maxpool: 2 */
+    int32_t stride;    /* conv, maxpool: 1 or 2; upsample: 2 */
+    int32_t pad;       /* conv: zero padding in pixels, 0 .. size / 2 */
+    int32_t leaky;     /* conv: 1 = x > 0 ? x : 0.1f * x, 0 = linear */
+    int32_t from[2];   /* route: source layers (absolute; from[1] = -1 for one); shortcut: from[0] */
+    int64_t weight_ofs; /* conv: its [filters][c][size][size] block in weights, in floats */
+    int64_t bias_ofs;  /* conv: its [filters] block in biases */
+    int32_t n_mask;    /* head: anchors it decodes */
+    int32_t anchor_ofs; /* head: its n_mask (w, h) pairs start at anchors[2 * anchor_ofs] */
+} fm_yolo_layer;
+typedef struct fm_yolo_desc {
+    int32_t n_layers;
+    const fm_yolo_layer* layers;
+    const float* weights;  /* batch norm folded in (darknet.load_weights) */
+    int64_t n_weights;
+    const float* biases;
+    int64_t n_biases;
+    const float* anchors;  /* (w, h) pairs in network-input pixels, the heads' masks already applied */
+    int32_t n_anchors;     /* pairs */
+    int32_t channels;      /* network input channels (3 for frames) */
+    int32_t net_w, net_h;  /* network input size (cvlib: 416 x 416 whatever the cfg's [net] says) */
+    int32_t classes;
+    int32_t max_frames;    /* frames per call the activation buffers are sized for */
+    float zero_thresh;     /* class scores <= this are zeroed (OpenCV's region layer: 0.2) */
+} fm_yolo_desc;
+
+/* Validate the description (FM_EINVAL before any HIP call: a route or shortcut to a later layer, channel
+ * counts or sizes that do not chain, a head whose input channels != n_mask * (classes + 5), offsets outside
+ * the arrays ...), then upload the re-packed weights and allocate every layer's activations.  *out is set
+ * even on failure so that fm_yolo_last_error can say why; release it with fm_yolo_destroy. */
+int fm_yolo_create(int device, const fm_yolo_desc* desc, fm_yolo** out);
+void fm_yolo_destroy(fm_yolo* det);
+const char* fm_yolo_last_error(const fm_yolo* det);
+/* Layer `layer`'s output shape (-1: the network input); total candidate rows of all heads in *rows.
+ * Any pointer may be NULL. */
+int fm_yolo_layer_shape(const fm_yolo* det, int layer, int* c, int* h, int* w, int* rows);
+/* find_objects' YOLO pass on n raw frames ([n][H][W][3] BGR; host memory, or device memory when
+ * on_device): INTER_AREA to width roi_w (imutils.resize: height int(H * roi_w / W), *roi_h_out; FM_ENOTSUP
+ * when W < roi_w), 8-bit INTER_LINEAR to the network size, the network, the decode.  cand[n][cap][9] gets
+ * each frame's rows whose best class score exceeds `confidence`, sorted by (head, row); counts[n] their
+ * number (may exceed cap; only cap are written).  More than max_frames: FM_EINVAL, nothing enqueued.
+ * Synchronous. */
+int fm_yolo_detect_frames(fm_yolo* det, const uint8_t* frames, int n, int H, int W, int on_device, int roi_w,
+                          float confidence, float* cand, int cap, int32_t* counts, int* roi_h_out);
+/* fm_yolo_detect_frames over n frames in device memory at n separate addresses (e.g. fm_frame_device). */
+int fm_yolo_detect_frame_list(fm_yolo* det, const uint8_t* const* frames, int n, int H, int W, int roi_w,
+                              float confidence, float* cand, int cap, int32_t* counts, int* roi_h_out);
+/* The network alone on a caller's blob (host, [n][channels][net_h][net_w] f32): parity tests. */
+int fm_yolo_forward(fm_yolo* det, const float* blob, int n);
+/* The decode alone, on the head tensors the last call left: parity tests.  Results as fm_yolo_detect_frames. */
+int fm_yolo_decode(fm_yolo* det, int n, float confidence, float* cand, int cap, int32_t* counts);
+/* Layer `layer`'s activations of the last call ([n][c][h][w] f32 for the n frames it ran; -1: the network
+ * input), copied to out: parity tests.  Returns their number (cap counts floats; FM_EINVAL when smaller). */
+int fm_yolo_layer_output(fm_yolo* det, int layer, float* out, size_t cap);
+/* Whether layer `layer` (a route) takes its inputs in place -- its sources wrote at channel offsets of its
+ * buffer -- 1, or by the copy kernel, 0 (read-only, for tests). */
+int fm_yolo_route_in_place(const fm_yolo* det, int layer);
+/* Device time of the last call per stage (HIP events), ms: resize + blob, network, decode; returns their sum.
+ * stages may be NULL. */
+double fm_yolo_last_ms(const fm_yolo* det, double* stages);
+
 #ifdef __cplusplus
 }
 #endif

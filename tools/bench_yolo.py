@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Time of the YOLOv3 object stage (fm_yolo_detect_frames) per call: 17 frames of 1080p -> INTER_AREA to
+width 300 -> 416 x 416 blob -> the network -> the decode.
+
+The layer list is yolov3-tiny's (or, with --model yolov3, the full Darknet-53 stack), restated here; the
+weights are random (no trained file is needed to time a network; the objectness biases are pushed down, yet how
+many rows the decode keeps -- `rows_kept` -- is an accident of the weights, not a trained network's few dozen).
+Reported per call: ms per stage (HIP
+events), the convolutions' FLOPs over the network stage's time against the 157 TFLOP/s f32-matrix peak, and the
+same convolution stack through torch.nn.functional.conv2d in the same run -- a yardstick only: torch picks
+its own algorithms and may not keep f32 products exact.
+
+Usage: python tools/bench_yolo.py [--model yolov3-tiny|yolov3] [--frames 17] [--iters 10] [--log FILE]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_TFLOPS = 157.0  # f32-input MFMA, MI355X
+
+ANCHORS_TINY = "10,14, 23,27, 37,58, 81,82, 135,169, 344,319"
+ANCHORS = "10,13, 16,30, 33,23, 30,61, 62,45, 59,119, 116,90, 156,198, 373,326"
+
+
+def conv(filters, size, stride=1, act="leaky", bn=1):
+    return (f"[convolutional]\n{'batch_normalize=1' if bn else ''}\nfilters={filters}\nsize={size}\nstride={stride}\n"
+            f"pad=1\nactivation={act}\n")
+
+
+def yolo(mask, anchors, num):
+    return (f"[yolo]\nmask = {mask}\nanchors = {anchors}\nclasses=80\nnum={num}\njitter=.3\nignore_thresh = .7\n"
+            "truth_thresh = 1\nrandom=1\n")
+
+
+def tiny_cfg() -> str:
+    pool = "[maxpool]\nsize=2\nstride=2\n"
+    body = []
+    for f in (16, 32, 64, 128, 256):
+        body += [conv(f, 3), pool]
+    body += [conv(512, 3), "[maxpool]\nsize=2\nstride=1\n", conv(1024, 3), conv(256, 1), conv(512, 3),
+             conv(255, 1, 1, "linear", 0), yolo("3,4,5", ANCHORS_TINY, 6), "[route]\nlayers = -4\n", conv(128, 1),
+             "[upsample]\nstride=2\n", "[route]\nlayers = -1, 8\n", conv(256, 3), conv(255, 1, 1, "linear", 0),
+             yolo("0,1,2", ANCHORS_TINY, 6)]
+    return "[net]\nwidth=416\nheight=416\nchannels=3\n\n" + "\n".join(body)
+
+
+def full_cfg() -> str:
+    res = "[shortcut]\nfrom=-3\nactivation=linear\n"
+    body = [conv(32, 3)]
+    for f, blocks in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
+        body.append(conv(f, 3, 2))
+        for _ in range(blocks):
+            body += [conv(f // 2, 1), conv(f, 3), res]
+    for f, mask, back in ((512, "6,7,8", None), (256, "3,4,5", 61), (128, "0,1,2", 36)):
+        if back is not None:
+            body += ["[route]\nlayers = -4\n", conv(f, 1), "[upsample]\nstride=2\n", f"[route]\nlayers = -1, {back}\n"]
+        for _ in range(3):
+            body += [conv(f, 1), conv(2 * f, 3)]
+        body += [conv(255, 1, 1, "linear", 0), yolo(mask, ANCHORS, 9)]
+    return "[net]\nwidth=416\nheight=416\nchannels=3\n\n" + "\n".join(body)
+
+
+def random_params(layers, seed=0):
+    from find_motion_amd import darknet as dk
+    rng = np.random.default_rng(seed)
+    params = [None] * len(layers)
+    for ly in layers:
+        if ly["kind"] != dk.CONV:
+            continue
+        n, c, s = ly["filters"], ly["in_c"], ly["size"]
+        w = (rng.standard_normal((n, c, s, s)) * math.sqrt(2.0 / (c * s * s))).astype(np.float32)
+        b = (rng.standard_normal(n) * 0.1).astype(np.float32)
+        nxt = layers[ly["index"] + 1] if ly["index"] + 1 < len(layers) else None
+        if nxt is not None and nxt["kind"] == dk.YOLO:
+            b[4::85] -= np.float32(6.0)
+        params[ly["index"]] = (w, b)
+    return params
+
+
+def conv_shapes(layers, net=416):
+    """(cin, cout, size, stride, pad, leaky, h_in, w_in, source) per convolution, walking the shapes."""
+    from find_motion_amd import darknet as dk
+    hw, out = [], []
+    for ly in layers:
+        h = hw[-1] if hw else net
+        k = ly["kind"]
+        if k == dk.CONV:
+            out.append((ly["in_c"], ly["filters"], ly["size"], ly["stride"], ly["pad"], ly["activation"] == "leaky", h))
+            h = (h + 2 * ly["pad"] - ly["size"]) // ly["stride"] + 1
+        elif k == dk.MAXPOOL:
+            h = h if ly["stride"] == 1 else (h + 1) // 2
+        elif k == dk.UPSAMPLE:
+            h *= 2
+        elif k == dk.ROUTE:
+            h = hw[ly["layers"][0]]
+        hw.append(h)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="yolov3-tiny", choices=("yolov3-tiny", "yolov3"))
+    ap.add_argument("--frames", type=int, default=17)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--log", default=None, help="append the result lines to this file")
+    a = ap.parse_args()
+    import torch
+    import torch.nn.functional as F
+
+    from find_motion_amd import YoloDetector
+    from find_motion_amd import darknet as dk
+
+    _, layers = dk.parse_cfg(tiny_cfg() if a.model == "yolov3-tiny" else full_cfg())
+    params = random_params(layers)
+    det = YoloDetector(layers, params, [str(i) for i in range(80)], max_frames=a.frames)
+    rng = np.random.default_rng(1)
+    frames = rng.integers(0, 256, (a.frames, 1080, 1920, 3), dtype=np.uint8)
+    dev = torch.from_numpy(frames).cuda()
+    shapes = conv_shapes(layers)
+    flops = sum(2.0 * ci * s * s * co * (((h + 2 * p - s) // st + 1) ** 2) for ci, co, s, st, p, _, h in shapes) * a.frames
+    stages = {"blob": [], "network": [], "decode": [], "total": []}
+    rows = 0
+    for it in range(a.iters + 2):
+        res, _ = det.candidates(dev)
+        if it >= 2:
+            ms = det.last_ms()
+            for k in stages:
+                stages[k].append(ms[k])
+            rows = sum(len(r) for r in res)
+    med = {k: float(np.median(v)) for k, v in stages.items()}
+    # the same convolutions through torch, layer by layer on inputs of the right shape
+    tw = [(torch.from_numpy(params[ly["index"]][0]).cuda(), torch.from_numpy(params[ly["index"]][1]).cuda())
+          for ly in layers if ly["kind"] == dk.CONV]
+    xs = [torch.randn(a.frames, ci, h, h, device="cuda") for ci, _, _, _, _, _, h in shapes]
+    tms = []
+    for it in range(a.iters + 2):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for (w, b), x, (_, _, s, st, p, leaky, _) in zip(tw, xs, shapes):
+            y = F.conv2d(x, w, b, stride=st, padding=p)
+            if leaky:
+                y = F.leaky_relu(y, 0.1)
+        e1.record()
+        torch.cuda.synchronize()
+        if it >= 2:
+            tms.append(e0.elapsed_time(e1))
+    tmed = float(np.median(tms))
+    out = {"model": a.model, "frames": a.frames, "source": "1920x1080", "layers": len(layers), "convs": len(shapes),
+           "ms_blob": round(med["blob"], 3), "ms_network": round(med["network"], 3), "ms_decode": round(med["decode"], 3),
+           "ms_total": round(med["total"], 3), "conv_gflop_per_call": round(flops / 1e9, 2),
+           "conv_tflops_over_network_ms": round(flops / (med["network"] * 1e-3) / 1e12, 2),
+           "fraction_of_157_tf_peak": round(flops / (med["network"] * 1e-3) / 1e12 / PEAK_TFLOPS, 4),
+           "torch_conv2d_ms": round(tmed, 3), "torch_conv2d_tflops": round(flops / (tmed * 1e-3) / 1e12, 2),
+           "rows_kept": rows, "iters": a.iters}
+    line = json.dumps(out)
+    print(line)
+    if a.log:
+        with open(a.log, "a") as f:
+            f.write(line + "\n")
+    det.close()
+
+
+if __name__ == "__main__":
+    main()
