@@ -77,6 +77,7 @@ struct BatchSlot {
     int32_t* d_rec = nullptr;       // device alias of h_rec
     uint8_t* h_init = nullptr;      // pinned [S]
     hipEvent_t ev_pix = nullptr, ev_done = nullptr, ev_rs = nullptr, ev_lab = nullptr;  // (ev_lab: labelling done)
+    hipEvent_t ev_in = nullptr;     // caller's stream (fm_set_hip_stream): its work queued before the submit
     hipStream_t ccl_stream = nullptr;  // this slot's contour pass (slots' passes run concurrently)
     int n = 0;                      // frames in flight in this slot (0 = none)
     FusedArgs fa{};                 // the contour pass's arguments (fm_wait re-emits frames past the cap)
@@ -177,7 +178,7 @@ struct fm_ctx {
         for (hipStream_t st : {own_stream, aux_stream, rs_stream, rs_stream2})
             if (st) (void)hipStreamDestroy(st);
         for (BatchSlot& b : slots)
-            for (hipEvent_t ev : {b.ev_pix, b.ev_done, b.ev_rs, b.ev_lab})
+            for (hipEvent_t ev : {b.ev_pix, b.ev_done, b.ev_rs, b.ev_lab, b.ev_in})
                 if (ev) (void)hipEventDestroy(ev);
         for (const auto& kv : dev_sizes) (void)hipFree(const_cast<void*>(kv.first));
         for (const auto& kv : pin_sizes) (void)hipHostFree(const_cast<void*>(kv.first));
@@ -608,7 +609,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         }
         b.ccl_stream = c->ccl_streams[i % c->nccl];
         if (i < c->nccl) c->timer.extra.push_back(b.ccl_stream);  // fold_stamps waits for it too
-        for (hipEvent_t* ev : {&b.ev_pix, &b.ev_done, &b.ev_rs, &b.ev_lab})
+        for (hipEvent_t* ev : {&b.ev_pix, &b.ev_done, &b.ev_rs, &b.ev_lab, &b.ev_in})
             HIP_TRY(cp, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     }
     // pixel-level CCL: the whole batch on the v1 path, one frame for the fused path's overflow fallback
@@ -1083,7 +1084,16 @@ int submit(fm_ctx* c, BatchInput in) {
     const uint8_t *src = nullptr, *work = nullptr;
     bool staged = false;
     int rc;
-    if ((rc = pick_input_stream(c, in, si, &rs)) || (rc = stage_input(c, B, in, rs, &src, &staged)) ||
+    if ((rc = pick_input_stream(c, in, si, &rs))) return rc;
+    // On a caller's stream (fm_set_hip_stream) the batch is ordered after the work the caller queued there
+    // before this call, such as the decode or copy that fills device input: the input stream waits for it
+    // before it touches the input.  (The context's own stream only ever carries this context's work, which
+    // the input stream runs ahead of: no wait there.)
+    if (rs != ps && ps != c->own_stream) {
+        HIP_TRY(c, hipEventRecord(B.ev_in, ps));
+        HIP_TRY(c, hipStreamWaitEvent(rs, B.ev_in, 0));
+    }
+    if ((rc = stage_input(c, B, in, rs, &src, &staged)) ||
         (rc = resize_input(c, B, rs, src, (size_t)n * S, &work)))
         return rc;
     if (rs != ps && (staged || c->rmode != ResizeMode::Identity)) {  // something ran on the input stream

@@ -189,7 +189,21 @@ int fm_read_background(fm_ctx* ctx, int stream, double* out);
 int fm_write_background(fm_ctx* ctx, int stream, const double* in);
 
 /* Launch on the caller's HIP stream (hipStream_t) instead of the context's own
- * stream; NULL restores the context stream. */
+ * stream; NULL restores the context stream.  FM_ESTATE while a batch is in flight.
+ *
+ * Ordering.  On a caller's stream every fm_submit* call is ordered after the work
+ * the caller queued on that stream before the call: device input (fm_submit /
+ * fm_submit_streams / fm_submit_yuv with on_device = 1, fm_submit_yuv_list) may
+ * still be being written by a decode or copy queued there, with no host
+ * synchronisation.  The context keeps its private input stream for the copies,
+ * the YUV conversion and the INTER_AREA resize; that stream first waits for an
+ * event recorded on the caller's stream.  Work the caller queues on its stream
+ * after the call runs after the batch's pixel kernels, which have read the input
+ * by then (the contour pass runs on the context's other streams: results are
+ * read after fm_wait, as always).  On the context's own stream nothing orders a
+ * batch against the caller's streams: device input must be complete before the
+ * call.  The caller keeps ownership of its stream; fm_destroy synchronises it
+ * and leaves it usable. */
 int fm_set_hip_stream(fm_ctx* ctx, void* hip_stream);
 
 /* Memory the context holds: device bytes (fm_create's buffers, plus input staging allocated on the

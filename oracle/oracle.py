@@ -192,6 +192,18 @@ class OracleStream:
     def initialized(self) -> bool:
         return bool(self._init.value)
 
+    def reset(self) -> None:
+        """VideoMotion.ref_frame = None (fm.py:414): the next frame's blur becomes the background (fm.py:651-652)."""
+        self._init.value = 0
+
+    def set_background(self, bg: np.ndarray) -> None:
+        """VideoMotion.ref_frame = bg: the float64 background is replaced and counts as initialised."""
+        bg = np.asarray(bg, dtype=np.float64)
+        if bg.shape != self.bg.shape:
+            raise ValueError(f"background shape {bg.shape} != work shape {self.bg.shape}")
+        self.bg[...] = bg
+        self._init.value = 1
+
     def step(self, bgr: np.ndarray, cap: int = 4096) -> dict:
         """blur_frame + mask_off_areas + find_diff for one frame (fm.py:866-868)."""
         c = self.cfg

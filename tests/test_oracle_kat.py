@@ -490,3 +490,79 @@ def test_sequence_schedule_equals_frame_steps(oracle_lib, W, H, box, k, masked):
             np.testing.assert_array_equal(got.areas(j), r["areas"])
             np.testing.assert_array_equal(got.masks[j], r["mask"])
         np.testing.assert_array_equal(b.bg, a.bg)
+
+
+# ---------------------------------------------------------------------------
+# ref_frame assignments (fm.py:414: ref_frame = None; the drop-in also takes an array)
+
+def _same_step(a, b):
+    assert a["count"] == b["count"] and a["boxes"] == b["boxes"] and a["origins"] == b["origins"]
+    for name in ("gray", "blur", "delta", "mask"):
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_reset_stream_steps_like_a_fresh_one(oracle_lib, masked):
+    """OracleStream.reset(): the stream forgets its background, so from the next frame on it equals a stream
+    created at that frame (fm.py:651-652 takes the frame's blur as the background), whatever it held before;
+    the reset frame itself has an all-zero delta."""
+    from find_motion_amd.synthetic import batch as syn_batch
+
+    W, H, box, k = 230, 130, 100, 5
+    cfg = oracle_lib.OracleConfig(H=H, W=W, box=box, ksize=k, thresh=12, alpha=0.1)
+    keep = None
+    if masked:
+        keep = np.ones((cfg.h, cfg.w), np.uint8)
+        keep[: cfg.h // 2, : cfg.w // 3] = 0
+    fr = syn_batch(W, H, 1, 20, 9)[:, 0]
+    old = oracle_lib.OracleStream(cfg, keep)
+    for i in range(4):
+        old.step(fr[i])
+    assert old.initialized and old.step(fr[4])["count"] > 0
+    old.reset()
+    assert not old.initialized
+    stale = old.bg.copy()
+    fresh = oracle_lib.OracleStream(cfg, keep)
+    for i in range(5, 9):
+        a, b = old.step(fr[i]), fresh.step(fr[i])
+        _same_step(a, b)
+        if i == 5:
+            assert not a["delta"].any() and a["count"] == 0
+            assert not np.array_equal(old.bg, stale)
+        np.testing.assert_array_equal(old.bg, fresh.bg)
+        assert old.initialized
+    assert a["count"] > 0
+
+
+def test_set_background_continues_like_the_donor_stream(oracle_lib):
+    """OracleStream.set_background(bg): a stream given another stream's background steps exactly like it from
+    then on -- a fresh stream (no first-frame initialisation follows) and one that held another background; the
+    array is copied, so the donor's later steps do not reach the receiver."""
+    from find_motion_amd.synthetic import batch as syn_batch
+
+    W, H, box, k = 160, 120, 160, 7
+    cfg = oracle_lib.OracleConfig(H=H, W=W, box=box, ksize=k, thresh=10, alpha=0.25)
+    fr = syn_batch(W, H, 2, 50, 8)
+    donor, other = oracle_lib.OracleStream(cfg), oracle_lib.OracleStream(cfg)
+    for i in range(4):
+        donor.step(fr[i, 0])
+        other.step(fr[i, 1])
+    assert not np.array_equal(donor.bg, other.bg)
+    fresh = oracle_lib.OracleStream(cfg)
+    snap = donor.bg.copy()
+    fresh.set_background(donor.bg)
+    other.set_background(donor.bg)
+    assert fresh.initialized and other.initialized
+    with pytest.raises(ValueError):
+        fresh.set_background(np.zeros((cfg.h + 1, cfg.w)))
+    seen = 0
+    for i in range(4, 8):
+        want = donor.step(fr[i, 0])
+        if i == 4:  # the donor moved on, the receivers still hold the snapshot
+            np.testing.assert_array_equal(fresh.bg, snap)
+            assert not np.array_equal(donor.bg, snap)
+        for st in (fresh, other):
+            _same_step(st.step(fr[i, 0]), want)
+            np.testing.assert_array_equal(st.bg, donor.bg)
+        seen += want["count"]
+    assert seen > 0
