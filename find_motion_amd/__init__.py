@@ -38,6 +38,7 @@ from ._native import (  # noqa: F401
     MotionEngine,
     NativeLibraryMissing,
     YoloDetector,
+    plan,
     rasterize_masks,
     yuv_frame_bytes,
 )

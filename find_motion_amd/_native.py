@@ -41,6 +41,7 @@ EXPORTED = (
     "fm_yolo_create", "fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_layer_shape", "fm_yolo_detect_frames",
     "fm_yolo_detect_frame_list", "fm_yolo_forward", "fm_yolo_decode", "fm_yolo_layer_output",
     "fm_yolo_route_in_place", "fm_yolo_last_ms",
+    "fm_plan",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -64,6 +65,11 @@ class FMParams(C.Structure):
     _fields_ = [("device", C.c_int), ("n_streams", C.c_int), ("src_w", C.c_int), ("src_h", C.c_int),
                 ("box_size", C.c_int), ("ksize", C.c_int), ("threshold", C.c_int), ("avg", C.c_double),
                 ("max_batch", C.c_int), ("max_contours", C.c_int), ("flags", C.c_uint)]
+
+
+class FMPlan(C.Structure):
+    _fields_ = [("work_h", C.c_int32), ("work_w", C.c_int32), ("tiles", C.c_int32), ("max_inflight", C.c_int32),
+                ("pixel_path", C.c_char * 16)]
 
 
 class FMHaarDesc(C.Structure):
@@ -139,6 +145,7 @@ def load() -> C.CDLL:
     L.fm_reset_kernel_times.argtypes = [vp]
     L.fm_rasterize_masks.argtypes = [i32, i32, C.c_double, vp, vp, i32, vp]
     L.fm_max_inflight.argtypes = [vp]
+    L.fm_plan.argtypes = [C.POINTER(FMParams), C.POINTER(FMPlan)]
     L.fm_last_fallbacks.argtypes = [vp]
     L.fm_last_ccl_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.fm_get_contour_points.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -256,6 +263,32 @@ def yuv_frame_bytes(width: int, height: int, fmt, pitch: int = 0, chroma_offset:
     return int(n.value)
 
 
+def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_points=False) -> int:
+    """fm_params.flags of MotionEngine's keyword arguments."""
+    return ((FM_FLAG_KEEP_PLANES if keep_planes else 0) | (FM_FLAG_CONTOUR_AREA if contour_area else 0) |
+            (FM_FLAG_CONTOUR_POINTS if contour_points else 0) |
+            (FM_FLAG_PROFILE_PIX if profile == "pix" else FM_FLAG_PROFILE if profile else 0))
+
+
+def plan(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: int, threshold: int = 12,
+         avg: float = 0.1, max_batch: int = 1, max_contours: int = 4096, keep_planes: bool = False,
+         profile: bool | str = False, device: int = 0, contour_area: bool = False,
+         contour_points: bool = False) -> dict:
+    """What MotionEngine(**params) would set up, asked of the library without touching a device (fm_plan: the
+    same validation and selection as fm_create): work_shape (h, w), tiles, max_inflight and pixel_path, one of
+    "small", "pix", "fused", "wide" and "pixel" (the per-frame path: one batch in flight).  FMError as
+    MotionEngine raises it for parameters the engine refuses."""
+    L = load()
+    p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg), max_batch,
+                 max_contours, engine_flags(keep_planes, profile, contour_area, contour_points))
+    out = FMPlan()
+    rc = L.fm_plan(C.byref(p), C.byref(out))
+    if rc != FM_OK:
+        raise FMError(rc, L.fm_last_error(None).decode())
+    return {"work_shape": (out.work_h, out.work_w), "tiles": out.tiles, "max_inflight": out.max_inflight,
+            "pixel_path": out.pixel_path.decode()}
+
+
 @dataclass
 class Contour:
     """One external contour of VideoFrame.contours (fm.py:269-276).
@@ -296,10 +329,7 @@ class MotionEngine:
         # profile: True = every kernel timed with HIP events, "pix" = pixel-stream kernels only
         self._L = load()
         p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg),
-                     max_batch, max_contours,
-                     (FM_FLAG_KEEP_PLANES if keep_planes else 0) | (FM_FLAG_CONTOUR_AREA if contour_area else 0) |
-                     (FM_FLAG_CONTOUR_POINTS if contour_points else 0) |
-                     (FM_FLAG_PROFILE_PIX if profile == "pix" else FM_FLAG_PROFILE if profile else 0))
+                     max_batch, max_contours, engine_flags(keep_planes, profile, contour_area, contour_points))
         h = C.c_void_p()
         rc = self._L.fm_create(C.byref(h), C.byref(p))
         if rc != FM_OK:
@@ -310,6 +340,10 @@ class MotionEngine:
         self._check(self._L.fm_work_size(h, C.byref(hh), C.byref(ww)))
         self.work_shape = (hh.value, ww.value)
         self.max_inflight = self._L.fm_max_inflight(h)
+        pl = FMPlan()   # the selection fm_create just made (the same function): which kernels run the pixel chain
+        self._check(self._L.fm_plan(C.byref(p), C.byref(pl)))
+        self.pixel_path = pl.pixel_path.decode()
+        self.tiles = pl.tiles
         self.n_streams = n_streams
         self.src_shape = (src_h, src_w, 3)
         self.device = int(device)

@@ -46,6 +46,7 @@ enum class ResizeMode { Identity, Fast, General };
 #define FM_SLOTS 10
 #endif
 constexpr int kSlots = FM_SLOTS;
+constexpr int kWideSlots = 4;  // batch slots of the wide-Gaussian path (its slots carry the blur scratch)
 struct BatchSlot {
     uint8_t* d_in = nullptr;        // host-fed staging [T][S][H][W][3]
     uint8_t* d_yuv = nullptr;       // host-fed YUV staging of fm_submit_yuv (first use; grown on demand)
@@ -56,6 +57,7 @@ struct BatchSlot {
     uint8_t* d_planes = nullptr;    // [3][T][S][h*w] gray, blur, frame_delta (FM_FLAG_KEEP_PLANES)
     uint64_t* d_bits = nullptr;     // threshold bit rows (k_pix output)
     uint8_t* d_sblur = nullptr;     // small work images: blur bytes [T*S][w][nty * 64] (k_small_blur -> k_small_scan)
+    uint8_t* d_wblur = nullptr;     // wide Gaussians: blur bytes, same layout (k_wide_blur -> k_small_scan)
     uint64_t* d_dbits = nullptr;    // dilated bit rows = VideoFrame.thresh
     TileRec* d_tiles = nullptr;
     NodeRec* d_nodes = nullptr;
@@ -138,6 +140,7 @@ struct fm_ctx {
     bool use_fused = false;
     bool use_pix = false;          // k_pix + dilating tile CCL (else k_fused dilates itself)
     bool use_small = false;        // the pixel stage as k_small_blur + k_small_scan (small work images)
+    bool use_wide = false;         // the pixel stage as k_wide_blur + k_small_scan (ksize above k_fused's)
     bool frame_ccl = false;        // the contour pass as one workgroup per frame (ntiles <= kFrameCclTiles)
     int ntx = 0, nty = 0, ntiles = 0, nnodes = 0;  // nnodes: per batch slot
     int nquota = 0;                                             // nodes of each frame's quota
@@ -440,10 +443,10 @@ int fm_abi_version(void) { return FM_ABI_VERSION; }
 
 const char* fm_last_error(const fm_ctx* ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 
-int fm_create(fm_ctx** out, const fm_params* prm) {
-    if (!out || !prm) return fail(nullptr, FM_EINVAL, "null argument");
-    *out = nullptr;
-    const fm_params& p = *prm;
+// The context's host-side plan: validation, the work size, the resize mode and its tables, the taps and the
+// choice of pixel path and slot count.  No device is touched; fm_create builds on it and fm_plan reports it,
+// so the two cannot disagree.
+static int plan_context(fm_ctx* c, const fm_params& p) {
     if (p.n_streams < 1 || p.src_w < 1 || p.src_h < 1 || p.box_size < 1 || p.max_batch < 1 || p.max_contours < 1)
         return fail(nullptr, FM_EINVAL, "invalid geometry (streams %d, src %dx%d, box %d, batch %d, contours %d)",
                     p.n_streams, p.src_w, p.src_h, p.box_size, p.max_batch, p.max_contours);
@@ -451,7 +454,6 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         return fail(nullptr, FM_EINVAL, "ksize %d must be odd and in [1, %d]", p.ksize, kMaxK);
     if (!(p.avg == p.avg)) return fail(nullptr, FM_EINVAL, "avg is NaN");
 
-    std::unique_ptr<fm_ctx> c(new fm_ctx());
     c->p = p;
     c->w = p.box_size;
     c->h = (int)(p.src_h * ((double)p.box_size / (double)p.src_w));  // imutils.resize
@@ -480,10 +482,9 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     if (!gaussian_taps(p.ksize, c->coef)) return fail(nullptr, FM_EINVAL, "bad ksize %d", p.ksize);
     if (pixel_lds_bytes(p.ksize) > 160 * 1024) return fail(nullptr, FM_ENOTSUP, "ksize %d too large for the LDS tile", p.ksize);
 
-    fm_ctx* cp = c.get();
-    HIP_TRY(cp, hipSetDevice(p.device));
+    const int tiles = ((c->w + 63) / 64) * ((c->h + 63) / 64);
     c->use_fused = p.ksize <= fused_max_ksize() && fused_lds_bytes(p.ksize) <= 160 * 1024 &&
-                   ((c->w + 63) / 64) * ((c->h + 63) / 64) <= 8192;  // region labelling holds the tile grid in LDS
+                   tiles <= 8192;  // region labelling holds the tile grid in LDS
     // small work images (mode D: 1080p -> 100 x 56), any k: frame-parallel blur + per-pixel scan
     // (fm_small.hip; mode D 634 -> 746 k frames/s, round 5), unless the caller keeps the gray / blur /
     // delta planes (k_pix writes them).  Both it and k_pix write threshold bits for the dilating contour pass.
@@ -492,6 +493,46 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     if (const char* e = dev_env("FM_SMALL")) c->use_small = c->use_small && std::atoi(e) != 0;
     c->use_pix = c->use_small || (c->use_fused && pix_supported(p.ksize) && (size_t)c->h * c->w >= 16 &&
                                   pix_lds_bytes(p.ksize) <= 160 * 1024 && dev_env("FM_NO_PIX") == nullptr);
+    // Gaussian sizes above k_fused's on more than kFrameCclTiles tiles (the reference's default blur scale with
+    // a raised box: -B 1920 gives k = 97): frame-parallel strip blur + the same scan (fm_wide.hip), with the
+    // tile machinery of the fused paths behind it.  Kept planes stay with the per-frame kernel, as above.
+    c->use_wide = p.ksize > fused_max_ksize() && !(p.flags & FM_FLAG_KEEP_PLANES) && tiles > kFrameCclTiles &&
+                  tiles <= 8192 && wide_supported(p.ksize, c->coef.data());
+    if (const char* e = dev_env("FM_WIDE")) c->use_wide = c->use_wide && std::atoi(e) != 0;
+    if (c->use_wide) c->use_fused = c->use_pix = true;
+    // a slot of the wide path also holds 1 B per pixel-frame of blur bytes (0.53 GB at 1080p x 256 frames, 2.1 GB
+    // at 2160p): kWideSlots of them
+    c->nslots = c->use_wide ? std::min(kSlots, kWideSlots) : c->use_fused ? kSlots : 1;
+    return FM_OK;
+}
+
+// the plan's pixel path by name (fm_plan, MotionEngine.pixel_path)
+static const char* pixel_path_name(const fm_ctx* c) {
+    return c->use_wide ? "wide" : c->use_small ? "small" : c->use_pix ? "pix" : c->use_fused ? "fused" : "pixel";
+}
+
+int fm_plan(const fm_params* prm, struct fm_plan* out) {
+    if (!prm || !out) return fail(nullptr, FM_EINVAL, "null argument");
+    std::memset(out, 0, sizeof *out);
+    fm_ctx c;  // host fields only: nothing to release
+    if (int rc = plan_context(&c, *prm)) return rc;
+    out->work_h = c.h;
+    out->work_w = c.w;
+    out->tiles = ((c.w + 63) / 64) * ((c.h + 63) / 64);
+    out->max_inflight = c.nslots;
+    std::snprintf(out->pixel_path, sizeof out->pixel_path, "%s", pixel_path_name(&c));
+    return FM_OK;
+}
+
+int fm_create(fm_ctx** out, const fm_params* prm) {
+    if (!out || !prm) return fail(nullptr, FM_EINVAL, "null argument");
+    *out = nullptr;
+    const fm_params& p = *prm;
+    std::unique_ptr<fm_ctx> c(new fm_ctx());
+    if (int rc = plan_context(c.get(), p)) return rc;
+
+    fm_ctx* cp = c.get();
+    HIP_TRY(cp, hipSetDevice(p.device));
     // The pixel stream at high priority: it gets a hardware queue of its own instead of sharing one (in
     // order) with a contour-pass stream.  (Round 4 gave small work images' pixel stream 8 CUs of its own
     // -- k_pix5's chain / producer waves on two tiles were a latency chain the next resize starved; the
@@ -532,7 +573,6 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     c->src_frame_bytes = (size_t)p.src_h * p.src_w * 3;
     const size_t frames = S * T, px = frames * c->work_plane;
     int rc;
-    c->nslots = c->use_fused ? kSlots : 1;
     // contour-pass streams shared round-robin by the slots: few streams, because the
     // runtime multiplexes streams onto GPU_MAX_HW_QUEUES (4) hardware queues in order,
     // and a contour kernel queued ahead of a pixel kernel on a shared queue stalls it
@@ -583,6 +623,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
                 (rc = dalloc(cp, &b.d_dbits, frames * c->ntiles * 64)) ||
                 (c->use_pix && (rc = dalloc(cp, &b.d_bits, frames * c->ntiles * 64))) ||
                 (c->use_small && (rc = dalloc(cp, &b.d_sblur, small_scratch_bytes(c->h, c->w, c->nty, frames)))) ||
+                (c->use_wide && (rc = dalloc(cp, &b.d_wblur, wide_scratch_bytes(c->w, c->nty, frames)))) ||
                 (rc = dalloc(cp, &b.d_nodes, (size_t)c->nnodes)))
                 return rc;
         }
@@ -955,6 +996,10 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
             HIP_TRY(c, c->timer.timed(ps, init ? "small_blur_init" : "small_blur", [&](uint64_t* k1, uint64_t* k2) {
                 return launch_small(ps, fp, B.d_sblur, k1, k2);
             }, true, init ? "small_scan_init" : "small_scan", init ? "small_init" : "small"));
+        else if (c->use_wide)
+            HIP_TRY(c, c->timer.timed(ps, init ? "wide_blur_init" : "wide_blur", [&](uint64_t* k1, uint64_t* k2) {
+                return launch_wide(ps, fp, B.d_wblur, k1, k2);
+            }, true, init ? "wide_scan_init" : "wide_scan", init ? "wide_init" : "wide"));
         else
             HIP_TRY(c, c->timer.timed(ps, name, [&](uint64_t* ks, uint64_t*) {
                 fp.kstamp = ks;

@@ -225,6 +225,14 @@ bool pix_supported(int ksize);
 bool small_supported(int h, int w, int ksize);
 size_t small_scratch_bytes(int h, int w, int nty, size_t frames);
 hipError_t launch_small(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint64_t* ks_blur, uint64_t* ks_scan);
+hipError_t launch_small_scan(hipStream_t st, const FusedArgs& a, const uint8_t* sblur, uint64_t* ks_scan);
+// Gaussian sizes above k_fused's on larger work images (fm_wide.hip): k_wide_blur (every frame of the launch in
+// parallel, a workgroup per column strip sliding down an LDS ring of horizontal sums) + k_small_scan; coef: the
+// context's taps; wblur: wide_scratch_bytes of the batch's frames
+bool wide_supported(int ksize, const int32_t* coef);
+int wide_lds_bytes(int ksize, const int32_t* coef);
+size_t wide_scratch_bytes(int w, int nty, size_t frames);
+hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks_blur, uint64_t* ks_scan);
 // CCL over tile summaries; dilate = true: a.bits are threshold rows to dilate into a.dbits
 // gate_wait / gate_done (optional): the labelling kernel waits for gate_wait (the previous batch's
 // labelling) and gate_done is recorded after it, so that one batch's labelling runs at a time

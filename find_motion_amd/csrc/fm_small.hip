@@ -229,7 +229,15 @@ hipError_t launch_small(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint
     FusedArgs b = a;
     b.kstamp = ks1;
     hipLaunchKernelGGL(sm::k_small_blur, dim3(nf), dim3(sm::BT), lds, st, b, sblur, CS);
-    b.kstamp = ks2;
+    return launch_small_scan(st, a, sblur, ks2);
+}
+
+// the scan alone, over blur bytes [F][x][a.nty * 64] of frames [a.t_begin, a.t_end) that are already written and
+// whose tile flags and padding bit words are cleared (k_small_blur, or fm_wide.hip's k_wide_blur)
+hipError_t launch_small_scan(hipStream_t st, const FusedArgs& a, const uint8_t* sblur, uint64_t* ks) {
+    const int CS = a.nty * 64;
+    FusedArgs b = a;
+    b.kstamp = ks;
     const int njobs = a.S * a.w * a.nty;
     const dim3 grid((njobs + sm::ST / 64 - 1) / (sm::ST / 64));
     if (a.acc_vec_end < (long long)a.h * a.w) hipLaunchKernelGGL(sm::k_small_scan<true>, grid, dim3(sm::ST), 0, st, b, sblur, CS);

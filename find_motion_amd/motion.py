@@ -365,12 +365,37 @@ class VideoMotion:
                                         avg=self.avg, max_batch=self.batch, keep_planes=self.keep_planes,
                                         device=self.device, contour_area=self.area_filter,
                                         **({"contour_points": True} if self.contour_points else {}))
+        self._log_pixel_path()
         if self.mask_areas:
             h, w = self._engine.work_shape
             self._engine.set_mask(self._stream, rasterize_masks(h, w, self.scale, self.mask_areas))
         if self.yolo_dir:
             self._load_yolo()
         return True
+
+    def _log_pixel_path(self) -> None:
+        """One line per video naming the kernels that run its per-pixel chain (MotionEngine.pixel_path), and a
+        warning when that is the per-frame path (one k_pixel launch per frame, one batch in flight), with the
+        condition that put it there."""
+        path = getattr(self._engine, "pixel_path", None)
+        if path is None:
+            return
+        h, w = self._engine.work_shape
+        k = self.gaussian[0]
+        self.log.info("%s: %d x %d work image, Gaussian %d: pixel path '%s', %d batch(es) in flight", self.filename,
+                      w, h, k, path, getattr(self._engine, "max_inflight", 1))
+        if path != "pixel":
+            return
+        tiles = getattr(self._engine, "tiles", ((w + 63) // 64) * ((h + 63) // 64))
+        if self.keep_planes:
+            why = "the gray / blur / delta planes are kept (show or debug), which only the per-frame kernel serves at this Gaussian size"
+        elif tiles <= 16:
+            why = f"the work image has only {tiles} tiles of 64 x 64 (the batched path for this Gaussian size needs more than 16)"
+        elif tiles > 8192:
+            why = f"the work image has {tiles} tiles of 64 x 64 (the batched paths take at most 8192)"
+        else:
+            why = f"no batched kernel takes Gaussian size {k} on this work image"
+        self.log.warning("%s: on the per-frame pixel path, far slower than the batched ones: %s", self.filename, why)
 
     def _load_yolo(self) -> None:
         """cvlib's model files (yolov3[-tiny].cfg, yolov3[-tiny].weights, yolov3_classes.txt) from `yolo_dir`,

@@ -95,6 +95,23 @@ int fm_abi_version(void);
 int fm_create(fm_ctx** out, const fm_params* params);
 void fm_destroy(fm_ctx* ctx);
 
+/* What fm_create would set up for params, without touching a device: the same validation (and error codes)
+ * and the same selection, by the same code.  pixel_path names the kernels of the per-pixel chain:
+ *   "small"  k_small_blur + k_small_scan (work images of at most 16,384 pixels)
+ *   "pix"    k_pix (ksize 3, 5, 7, 21)
+ *   "fused"  k_fused (other ksize up to 49)
+ *   "wide"   k_wide_blur + k_small_scan (ksize above 49, more than 16 and at most 8,192 tiles of 64 x 64,
+ *            no FM_FLAG_KEEP_PLANES)
+ *   "pixel"  one k_pixel launch per frame and the pixel-level CCL: one batch in flight
+ * (The struct has no typedef: C keeps struct tags apart from function names, not typedef names.) */
+struct fm_plan {
+    int32_t work_h, work_w; /* fm_work_size */
+    int32_t tiles;          /* 64 x 64 tiles of the work image */
+    int32_t max_inflight;   /* fm_max_inflight */
+    char pixel_path[16];
+};
+int fm_plan(const fm_params* params, struct fm_plan* out);
+
 /* Last error message for ctx (or the calling thread's last error if ctx is NULL). */
 const char* fm_last_error(const fm_ctx* ctx);
 
