@@ -8,6 +8,8 @@ import io
 
 import numpy as np
 
+import jpeg_encode_ref as ref
+
 try:
     from PIL import Image
 except ImportError:  # pragma: no cover - Pillow is in the image; the tests skip without it
@@ -356,6 +358,177 @@ def busy_noise(H: int, W: int, seed: int = 5) -> np.ndarray:
 
 def constant(H: int, W: int) -> np.ndarray:
     return np.full((H, W, 3), 128, np.uint8)
+
+
+def chroma_checkerboard(H: int, W: int, cell: int = 8) -> np.ndarray:
+    """cell x cell squares, blue (Cb 255) and yellow (Cb 0) in turn, Y and Cr nearly level: at quality 100 the Cb
+    DC goes from 1016 to -1024 and back, a difference of category 11 with both signs.  cell = 16 keeps that
+    through 4:2:0's 2 x 2 averaging."""
+    y, x = np.mgrid[0:H, 0:W]
+    blue = (((y // cell) + (x // cell)) & 1) == 0
+    return np.where(blue[..., None], np.array([255, 0, 0], np.uint8), np.array([0, 255, 255], np.uint8))
+
+
+def dc_ladder(slot: int) -> np.ndarray:
+    """17 level 8 x 8 blocks in a row, 127 and 127 + 2^k in turn for k = 0..7: at quality 100 and 4:4:4 the DC
+    differences of the component are -8, then +8 * 2^k and -8 * 2^k, categories 4 to 11 with both signs (1 to 3
+    come with symbol_sweep).  Slot 0: gray levels.  Slot 1: B = L, G = R = 255 - L, whose Cb is L exactly."""
+    levels = [127]
+    for k in range(8):
+        levels += [127 + (1 << k), 127]
+    p = np.repeat(np.repeat(np.array(levels)[None, :], 8, 0), 8, 1)
+    return np.stack([p, p, p] if slot == 0 else [p, 255 - p, 255 - p], -1).astype(np.uint8)
+
+
+# ---- the write side's entropy coder: every (run, size) symbol, ZRL chains, the stuffing kernels' seams
+
+SWEEP_QUALITIES = (10, 25, 50, 75, 90, 100)
+SWEEP_LONE = (17, 18, 33, 34, 49, 50, 63)  # zigzag positions: 1, 2, 3 ZRLs before the value; 63 leaves no EOB
+SWEEP_COLS = 20                            # blocks per image row
+
+
+def _dct_basis() -> np.ndarray:
+    """[u][x]: the orthonormal 8-point DCT-II matrix."""
+    x = np.arange(8)
+    m = np.cos((2 * x[None, :] + 1) * x[:, None] * np.pi / 16) / 2
+    m[0] /= np.sqrt(2)
+    return m
+
+
+def sweep_planes(slot: int, quality: int) -> np.ndarray:
+    """The 8 x 8 sample blocks of symbol_sweep, u8 [n][8][8], aimed at the quantization table of `slot` at this
+    quality (jpeg_set_quality's scaling, force_baseline):
+      - for each run 0..15, size 1..10 and sign, the float IDCT of one coefficient at zigzag position 1 + run
+        (2^size - 1, or -2^(size - 1)) times its quantizer, plus 128, rounded and clipped;
+      - the same with a lone +-1 at each of SWEEP_LONE;
+      - for each AC basis function, its sign pattern in 0 / 255 (at quality 100: the size 9 and 10 values).
+    What a block really codes to is for the encoder under test and the reference to agree on: clipping bends
+    the large targets, and rounding adds +-1 coefficients at quality 100."""
+    q = ref.quant_tables(quality)[slot]
+    m = _dct_basis()
+    targets = [(1 + run, v) for run in range(16) for size in range(1, 11) for v in ((1 << size) - 1, -(1 << (size - 1)))]
+    targets += [(k, v) for k in SWEEP_LONE for v in (1, -1)]
+    blocks = []
+    for k, v in targets:
+        c = np.zeros(64)
+        c[ref.ZIGZAG[k]] = v * q[ref.ZIGZAG[k]]
+        blocks.append(np.rint(m.T @ c.reshape(8, 8) @ m + 128).clip(0, 255))
+    for k in range(1, 64):
+        c = np.zeros(64)
+        c[ref.ZIGZAG[k]] = 1
+        blocks.append(np.where(m.T @ c.reshape(8, 8) @ m > 0, 255, 0))
+    return np.array(blocks).astype(np.uint8)
+
+
+def symbol_sweep(slot: int, quality: int) -> np.ndarray:
+    """BGR u8 image, to be encoded 4:4:4, whose blocks are sweep_planes(slot, quality), SWEEP_COLS to a row (the
+    last row filled with level 128).  Slot 0 (luma tables): a gray image.  Slot 1 (chroma tables): the blocks
+    are the Cb plane under Y = Cr = 128, converted to BGR by the JFIF equations, rounded and clipped."""
+    b = sweep_planes(slot, quality)
+    rows = -(-len(b) // SWEEP_COLS)
+    b = np.concatenate([b, np.full((rows * SWEEP_COLS - len(b), 8, 8), 128, np.uint8)])
+    p = b.reshape(rows, SWEEP_COLS, 8, 8).transpose(0, 2, 1, 3).reshape(rows * 8, SWEEP_COLS * 8)
+    if slot == 0:
+        return np.repeat(p[..., None], 3, axis=2)
+    cb = p.astype(np.float64) - 128
+    bgr = np.stack([128 + 1.772 * cb, 128 - 0.344136 * cb, np.full_like(cb, 128)], -1)
+    return np.rint(bgr).clip(0, 255).astype(np.uint8)
+
+
+SEAM_SHAPE = (64, 96)  # H, W: at 4:4:4 and quality 100 a noise frame's scan is about 25 KB, seven 4 KiB tiles
+SEAM_TILE = 4096       # bytes of unstuffed stream per workgroup of the stuffing kernels (kTile, fm_jpeg_enc.hip)
+
+# (image seed, restart interval in MCUs, conditions): seeded noise frames in whose Pillow file the conditions
+# hold -- found by a search over seeds 0..399 at intervals 0, 1 and 2, and asserted by
+# tests/test_jpeg_encode_host.py, so that the GPU tests on them cannot pass vacuously.
+#   pair        FF 00 D0..D7 in the scan with restart markers on: a data pair that looks like an RSTn marker
+#   ones_rst    FF 00 FF Dn: an all-ones padded byte before an RSTn marker
+#   ones_eoi    the scan ends in FF 00: an all-ones byte before the EOI
+#   tile_end    a data FF on the last byte of a tile of the unstuffed stream
+#   tile_ffff   FF FF across such a tile seam
+SEAM_CASES = [
+    (0, 1, {"pair", "ones_rst"}),
+    (1, 2, {"pair", "ones_rst"}),
+    (3, 0, {"ones_eoi"}),
+    (3, 1, {"ones_eoi", "ones_rst"}),
+    (4, 1, {"tile_end"}),
+    (13, 0, {"tile_end", "ones_eoi"}),
+    (27, 2, {"tile_end"}),
+    (399, 1, {"tile_end", "tile_ffff"}),
+]
+
+
+SHORT_SHAPE = (16, 32)  # H, W: eight 4:4:4 MCUs; a constant frame's scan is 14 bytes, less than a lane's 16
+
+
+def seam_frame(seed: int) -> np.ndarray:
+    return image(*SEAM_SHAPE, "noise", seed=seed)
+
+
+def binary_noise(H: int, W: int, seed: int) -> np.ndarray:
+    """Every sample 0 or 255: about 100 bytes a block at quality 100."""
+    return (np.random.default_rng(seed).integers(0, 2, (H, W, 3)) * 255).astype(np.uint8)
+
+
+def scan_of(data: bytes) -> bytes:
+    """The entropy-coded segment of a baseline file as written: after the SOS, without the EOI."""
+    sos = [b for m, a, b in segments(data) if m == 0xDA][0]
+    assert data[-2:] == b"\xff\xd9"
+    return data[sos:-2]
+
+
+def unstuffed_data_ff(scan: bytes):
+    """(the scan with every FF 00 turned into FF, the offsets in it of those data FFs)."""
+    out, ffs, k = bytearray(), [], 0
+    while k < len(scan):
+        out.append(scan[k])
+        if scan[k] == 0xFF and k + 1 < len(scan) and scan[k + 1] == 0:
+            ffs.append(len(out) - 1)
+            k += 1
+        k += 1
+    return bytes(out), ffs
+
+
+def seam_conditions(data: bytes) -> set:
+    """Which of SEAM_CASES' conditions hold in this file (Pillow's)."""
+    scan = scan_of(data)
+    un, ffs = unstuffed_data_ff(scan)
+    got = set()
+    for k in range(len(scan) - 2):
+        if scan[k] == 0xFF and scan[k + 1] == 0:
+            if 0xD0 <= scan[k + 2] <= 0xD7:
+                got.add("pair")
+            if k + 3 < len(scan) and scan[k + 2] == 0xFF and 0xD0 <= scan[k + 3] <= 0xD7:
+                got.add("ones_rst")
+    if scan[-2:] == b"\xff\x00":
+        got.add("ones_eoi")
+    for p in ffs:
+        if p % SEAM_TILE == SEAM_TILE - 1 and p + 1 < len(un):
+            got.add("tile_end")
+            if un[p + 1] == 0xFF:
+                got.add("tile_ffff")
+    return got
+
+
+def _entropy_cases() -> dict:
+    """name -> (image function, quality, subsampling, restart intervals in MCUs): the inputs on which the encoder's
+    entropy coder is pinned (tests/test_gpu_jpeg_encode.py) and, through Pillow's files, the decoder's."""
+    out = {}
+    for slot, nm in ((0, "luma"), (1, "chroma")):
+        for q in SWEEP_QUALITIES:
+            out[f"sweep_{nm}_q{q}"] = (lambda slot=slot, q=q: symbol_sweep(slot, q), q, 0, (0, 1))
+        out[f"ladder_{nm}"] = (lambda slot=slot: dc_ladder(slot), 100, 0, (0,))
+    for sub, ss in SUBSAMPLINGS[::2]:
+        out[f"checker_luma_{sub}"] = (lambda: checkerboard(24, 40), 100, ss, (0,))
+        out[f"checker_chroma_{sub}"] = (lambda ss=ss: chroma_checkerboard(32, 48, 16 if ss else 8), 100, ss, (0,))
+        out[f"busy_noise_{sub}"] = (lambda: busy_noise(37, 53), 100, ss, (0, 1))
+    out["constant"] = (lambda: constant(16, 16), 75, 2, (0, 1))
+    return out
+
+
+ENTROPY_CASES = _entropy_cases()
+# the 4:4:4 ones: Cb and Cr blocks are then whole blocks of the image, and the scan is Y, Cb, Cr in turn
+COVERAGE_CASES = [n for n, c in ENTROPY_CASES.items() if c[2] == 0]
 
 
 def luma_dc_differences(j: dict, coefs) -> list:

@@ -4,10 +4,17 @@ The reference writes motion frames with cv2.VideoWriter, codec 'MJPG' by default
 encoder's target is the file Pillow writes for the same pixels and settings -- what videoio.MjpegAviWriter writes
 on the host -- so every comparison here is of whole files.  On a mismatch the quantized coefficients are compared
 with the numpy restatement (tests/jpeg_encode_ref.py, pinned to Pillow in tests/test_jpeg_encode_host.py) first,
-so the failure names the stage: colour / DCT / quantization, header, or entropy coding."""
+so the failure names the stage: colour / DCT / quantization, header, or entropy coding.
+
+The entropy coder and the stream assembly are pinned on inputs built for them (tests/jpeg_cases.py), whose
+properties -- the symbols reached, the byte patterns at the tile seams -- tests/test_jpeg_encode_host.py asserts
+from the reference's side: every AC symbol but three, three ZRLs in a block, both signs of every size and DC
+category, the quality scaling's clamps and switch, runs of several blocks per lane of k_enc_scan with restart
+intervals starting inside them, and FF bytes wherever k_enc_ffcount / k_enc_stuff must decide about them."""
 import numpy as np
 import pytest
 
+import jpeg_cases as jc
 import jpeg_encode_ref as ref
 from find_motion_amd import FMError, MJpegDecoder, MJpegEncoder, motion, videoio
 from find_motion_amd.synthetic import SyntheticVideo
@@ -59,6 +66,101 @@ def test_encoder_equals_pillow(shape, setting):
     enc = MJpegEncoder(W, H, max_frames=4, quality=q, subsampling=s, restart_interval=restart_mcus(W, s, r))
     got = enc.encode(np.stack(frames))
     assert_equals_pillow(enc, frames, got, [pillow(f, q, s, r) for f in frames])
+    enc.close()
+
+
+@pytest.mark.parametrize("name", list(jc.ENTROPY_CASES))
+def test_entropy_cases_equal_pillow(name):
+    """The symbol sweeps (every 16-bit code of both AC tables, 1 to 3 ZRLs, value at coefficient 63 after them),
+    DC differences of every category in both tables, blocks without an EOB, a scan of a few bytes; with a
+    restart after every MCU too where the case says so."""
+    fn, q, s, restarts = jc.ENTROPY_CASES[name]
+    img = fn()
+    H, W = img.shape[:2]
+    for r in restarts:
+        enc = MJpegEncoder(W, H, max_frames=1, quality=q, subsampling=s, restart_interval=r)
+        assert_equals_pillow(enc, [img], enc.encode(img))
+        enc.close()
+
+
+# jpeg_set_quality's scaling: 1 and 10 clamp to 255, 23 is the last quality that clamps, 49 / 50 / 51 the switch
+QUALITY_SWEEP = [(q, 2) for q in (1, 10, 23, 24, 25, 49, 50, 51, 99)] + [(1, 0)]
+
+
+@pytest.mark.parametrize("q,s", QUALITY_SWEEP)
+def test_quality_sweep_equals_pillow(q, s):
+    H, W = 37, 53
+    frames = [image(H, W, kind, seed=7) for kind in ("noise", "smooth")]
+    enc = MJpegEncoder(W, H, max_frames=2, quality=q, subsampling=s)
+    assert_equals_pillow(enc, frames, enc.encode(np.stack(frames)))
+    enc.close()
+
+
+# k_enc_scan gives each of its 256 lanes a run of per = ceil(blocks / 256) consecutive blocks; ib = blocks per
+# restart interval.  (H, W, subsampling, restart interval in MCUs):
+SCAN_LAYOUT = [
+    # 17 x 16 MCUs of 3 blocks = 816 blocks, per = 4.  ib = 3: every run of four holds an interval start inside
+    # it, every third run two (at its first and at its last block); ib = 15: a start in four runs of fifteen
+    (128, 136, 0, 1), (128, 136, 0, 5),
+    # 21 x 7 MCUs of 4 blocks = 588 blocks, per = 3.  ib = 4: intervals longer than a run, a start in three runs
+    # of four, at each position of a run in turn; ib = 28: most runs without a start, between runs that have one
+    (50, 330, 1, 1), (50, 330, 1, 7),
+    # 13 x 8 MCUs of 6 blocks = 624 blocks, per = 3: lanes 208..255 have no blocks.  ib = 6, 12, 78 (a row of 13
+    # MCUs) and 618 (103 MCUs: the last interval is one MCU) are multiples of a run: starts at runs' first blocks
+    (120, 200, 2, 1), (120, 200, 2, 2), (120, 200, 2, "row"), (120, 200, 2, 103),
+]
+
+
+@pytest.mark.parametrize("H,W,s,r", SCAN_LAYOUT)
+def test_scan_layout_with_runs_of_blocks_and_restarts(H, W, s, r):
+    frames = [image(H, W, "noise", seed=H + W + k) for k in range(2)]  # noise: block lengths vary
+    n = restart_mcus(W, s, r)
+    enc = MJpegEncoder(W, H, max_frames=2, quality=90, subsampling=s, restart_interval=n)
+    assert -(-enc.blocks // 256) == (4 if s == 0 else 3)
+    assert_equals_pillow(enc, frames, enc.encode(np.stack(frames)), [pillow(f, 90, s, r) for f in frames])
+    enc.close()
+
+
+@pytest.mark.parametrize("seed,r,conditions", jc.SEAM_CASES, ids=lambda v: str(v) if isinstance(v, int) else None)
+def test_seam_frames_equal_pillow(seed, r, conditions):
+    """Seven-tile scans in which Pillow's file has (tests/test_jpeg_encode_host.py asserts it) a data FF followed
+    by a data D0..D7 with restart markers on, an all-ones byte before an RSTn or the EOI, a data FF on a tile's
+    last byte, FF FF across a tile seam."""
+    H, W = jc.SEAM_SHAPE
+    f = jc.seam_frame(seed)
+    enc = MJpegEncoder(W, H, max_frames=1, quality=100, subsampling=0, restart_interval=r)
+    assert_equals_pillow(enc, [f], enc.encode(f))
+    enc.close()
+
+
+def _both_orders(enc, frames):
+    want = [pillow(f, enc.quality, enc.subsampling, enc.restart_interval) for f in frames]
+    assert_equals_pillow(enc, frames, enc.encode(np.stack(frames)), want)
+    assert_equals_pillow(enc, frames[::-1], enc.encode(np.stack(frames[::-1])), want[::-1])
+
+
+@pytest.mark.parametrize("r", [0, 1, 2])
+def test_short_stream_between_seven_tile_frames(r):
+    """The seam frames of one restart interval in one call, a constant frame (168 bytes of scan: less than 11
+    lanes of one tile) after the first; then the same encoder on the reversed order.  Every frame's place in the
+    unstuffed buffer, its tiles' numbers and its place in the output depend on the frames before it."""
+    H, W = jc.SEAM_SHAPE
+    frames = [jc.seam_frame(seed) for seed, ri, _ in jc.SEAM_CASES if ri == r]
+    assert len(frames) >= 2
+    frames.insert(1, jc.constant(H, W))
+    enc = MJpegEncoder(W, H, max_frames=len(frames), quality=100, subsampling=0, restart_interval=r)
+    _both_orders(enc, frames)
+    enc.close()
+
+
+@pytest.mark.parametrize("r", [0, 1])
+def test_stream_shorter_than_a_lane_between_longer_ones(r):
+    """A scan of 14 bytes (a constant 32 x 16 frame, 4:4:4; a few more with restart markers) between scans of
+    2.4 KB, the longest this frame size gives: one tile whose only busy lane holds 14 bytes."""
+    H, W = jc.SHORT_SHAPE
+    frames = [jc.binary_noise(H, W, 0), jc.constant(H, W), jc.binary_noise(H, W, 1), jc.constant(H, W)]
+    enc = MJpegEncoder(W, H, max_frames=4, quality=100, subsampling=0, restart_interval=r)
+    _both_orders(enc, frames)
     enc.close()
 
 

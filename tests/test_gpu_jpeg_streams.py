@@ -1,7 +1,8 @@
 """The GPU MJPEG decoder on streams Pillow's default encoder never writes (camera and file MJPEG are the one
 input the project does not produce itself): table ids 2 and 3, merged DQT / DHT segments, 16-bit quantization
 tables, three quantization tables, other component ids, Adobe and JFIF metadata, APPn / COM payloads that
-hold marker bytes, bytes after EOI, no EOI, a gray frame's sampling byte, and the entropy coder's extremes.
+hold marker bytes, bytes after EOI, no EOI, a gray frame's sampling byte, and the entropy coder's extremes
+(with Pillow's files of the inputs the GPU encoder's entropy coder is pinned on: its symbol sweeps and seam frames).
 
 Every comparison is np.array_equal against Pillow's libjpeg-turbo decode of the same bytes; where a patch
 keeps the stream's meaning, Pillow's decode of the patched bytes must equal its decode of the unpatched ones,
@@ -13,8 +14,9 @@ import pytest
 
 from find_motion_amd import FMError, MJpegDecoder
 from find_motion_amd._native import FM_EINVAL, FM_ENOTSUP
-from jpeg_cases import (REFUSED, RGB_REFUSED, STREAMS, SUBSAMPLINGS, Image, as_jfif, busy_noise, checkerboard, constant, encode,
-                        image, luma_dc_differences, reference_decode, restart_interval_lengths, stream_reference)
+from jpeg_cases import (ENTROPY_CASES, REFUSED, RGB_REFUSED, SEAM_CASES, SEAM_SHAPE, STREAMS, SUBSAMPLINGS, Image, as_jfif,
+                        busy_noise, checkerboard, constant, encode, image, luma_dc_differences, reference_decode,
+                        restart_interval_lengths, seam_frame, stream_reference)
 from oracle import jpeg
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(Image is None, reason="Pillow not importable")]
@@ -114,6 +116,29 @@ def test_restart_intervals_of_a_few_bytes(sub, ss, H, W):
     data = encode(constant(H, W), quality=75, subsampling=ss, restart_marker_blocks=1)
     lens = restart_interval_lengths(jpeg.parse(data))
     assert len(lens) == -(-H // (16 if ss == 2 else 8)) * -(-W // (8 if ss == 0 else 16)) and min(lens) <= 4
+    _decode_alone(data, H, W, reference_decode(data))
+
+
+SWEEPS = [(n, 0) for n in ENTROPY_CASES if n.startswith("sweep_")] + [("sweep_luma_q100", 1), ("sweep_chroma_q50", 1)]
+
+
+@pytest.mark.parametrize("name,restart", SWEEPS)
+def test_symbol_sweeps(name, restart):
+    """Pillow's files of the encoder's symbol sweeps (tests/test_jpeg_encode_host.py counts what they reach: all
+    but three of the 2 x 162 AC symbols, so every 16-bit code, with up to 10 extra bits, on the path past the
+    10-bit lookup table; three ZRLs in a block; a value at coefficient 63 after them)."""
+    fn, q, ss, _ = ENTROPY_CASES[name]
+    img = fn()
+    data = encode(img, quality=q, subsampling=ss, **(dict(restart_marker_blocks=restart) if restart else {}))
+    _decode_alone(data, img.shape[0], img.shape[1], reference_decode(data))
+
+
+@pytest.mark.parametrize("seed,restart,conditions", SEAM_CASES, ids=lambda v: str(v) if isinstance(v, int) else None)
+def test_seam_frames(seed, restart, conditions):
+    """The encoder's seam frames, read: 25 KB scans with a data FF before a data D0..D7 among restart markers,
+    all-ones bytes before RSTn and EOI."""
+    H, W = SEAM_SHAPE
+    data = encode(seam_frame(seed), quality=100, subsampling=0, **(dict(restart_marker_blocks=restart) if restart else {}))
     _decode_alone(data, H, W, reference_decode(data))
 
 

@@ -54,6 +54,167 @@ def test_restart_case_wraps_the_marker_numbers():
     assert marks == [0xD0 + (i & 7) for i in range(11)]
 
 
+# --- the entropy coder's inputs: what the GPU tests encode, pinned and measured here ---------------------------
+
+_COEF = {}
+
+
+def case_image(name):
+    fn, q, s, restarts = jc.ENTROPY_CASES[name]
+    return fn(), q, s, restarts
+
+
+def case_coefficients(name):
+    """ref.coefficients of an entropy case, computed once (the arrays are shared: do not write to them)."""
+    if name not in _COEF:
+        img, q, s, _ = case_image(name)
+        _COEF[name] = ref.coefficients(img, q, s)
+        _COEF[name].setflags(write=False)
+    return _COEF[name]
+
+
+@pytest.mark.parametrize("name", list(jc.ENTROPY_CASES))
+def test_restatement_equals_pillow_on_the_entropy_cases(name):
+    """What licenses reading coverage off ref.coefficients: on these images too the restatement writes Pillow's
+    file, at every setting the GPU encodes them with."""
+    img, q, s, restarts = case_image(name)
+    H, W = img.shape[:2]
+    for r in restarts:
+        got = ref.header(W, H, q, s, r) + ref.entropy_code(case_coefficients(name), s, r) + b"\xff\xd9"
+        assert got == pillow(img, q, s, r), r
+
+
+QUALITY_SWEEP = [(q, 2) for q in (1, 10, 23, 24, 25, 49, 50, 51, 99)] + [(1, 0)]  # (quality, subsampling)
+
+
+@pytest.mark.parametrize("q,s", QUALITY_SWEEP)
+@pytest.mark.parametrize("kind", ["noise", "smooth"])
+def test_restatement_equals_pillow_over_the_quality_scaling(q, s, kind):
+    """jpeg_set_quality's scaling, force_baseline: quality 1 (scale 5000: every entry clamps to 255), 10 (most do),
+    23 / 24 / 25 (scale 217 / 208 / 200: the last quality at which an entry clamps, and the first two without),
+    49 / 50 / 51 (the formula's switch), 99 (scale 2)."""
+    img = jc.image(37, 53, kind, seed=7)
+    assert ref.encode(img, q, s, 0) == pillow(img, q, s, 0)
+
+
+def test_quality_scaling_clamps_where_the_sweep_says():
+    lq = {q: ref.quant_tables(q)[0] for q in (1, 10, 23, 24)}
+    assert (lq[1] == 255).all() and 0 < (lq[10] == 255).sum() < 64
+    assert (lq[23] == 255).sum() == 2 and lq[24].max() == 252  # 121 and 120 * 217 / 100 clamp, 121 * 208 / 100 does not
+
+
+# (H, W, subsampling, restart intervals): a frame of more than 256 blocks gives each lane of k_enc_scan a run of
+# per = ceil(blocks / 256) consecutive blocks; see tests/test_gpu_jpeg_encode.py for what each shape is for
+SCAN_LAYOUT = [(128, 136, 0, (1, 5)), (50, 330, 1, (1, 7)), (120, 200, 2, (1, 2, "row", 103))]
+
+
+@pytest.mark.parametrize("H,W,s,restarts", SCAN_LAYOUT, ids=lambda v: str(v).replace(" ", ""))
+def test_restatement_equals_pillow_on_the_scan_layout_shapes(H, W, s, restarts):
+    img = jc.image(H, W, "noise", seed=H + W)
+    co = ref.coefficients(img, 90, s)
+    for r in restarts:
+        n = restart_mcus(W, s, r)
+        assert ref.header(W, H, 90, s, n) + ref.entropy_code(co, s, n) + b"\xff\xd9" == pillow(img, 90, s, r), r
+
+
+ALL_AC = {(run << 4) | size for run in range(16) for size in range(1, 11)} | {0x00, 0xF0}
+# the (run, size) symbols that no 4:4:4 entropy case reaches, per table: written out, so that coverage cannot shrink
+# unnoticed (a construction that reaches more of them is welcome: shorten these)
+MISSING_AC = [{0x58}, {0xC9, 0xE9}]
+
+
+def entropy_stats(coef):
+    """Of a 4:4:4 frame's scan-order coefficients, per Huffman table slot (0: Y, 1: Cb and Cr): the AC symbols,
+    the most ZRLs in a block, whether a block has coefficient 63 after a run of at least 48, the AC sizes by
+    sign, the DC categories by sign (no restart intervals)."""
+    st = [dict(ac=set(), zrl=0, late=False, size=set(), dc=set()) for _ in range(2)]
+    for comp in range(3):
+        t = st[min(comp, 1)]
+        blocks = coef[comp::3].astype(np.int64)
+        for d, blk in zip(np.diff(blocks[:, 0], prepend=0), blocks):
+            syms = list(ref._symbols(int(d), blk))
+            (_, cat), _ = syms[0]
+            t["dc"].add((cat, int(np.sign(d))))
+            ac = [(rs, v) for (_, rs), v in syms[1:]]
+            t["ac"] |= {rs for rs, _ in ac}
+            t["zrl"] = max(t["zrl"], sum(rs == 0xF0 for rs, _ in ac))
+            t["size"] |= {(rs & 15, int(np.sign(v))) for rs, v in ac if rs & 15}
+            nz = np.nonzero(blk[1:63])[0]
+            t["late"] |= bool(blk[63]) and (len(nz) == 0 or nz[-1] + 1 <= 63 - 49)
+    return st
+
+
+def test_entropy_cases_reach_the_whole_of_both_tables(capsys):
+    """Computed from the reference alone (ref.coefficients, equal to Pillow's on these images by the test above):
+    what the GPU encoder is asked to write, it is asked to write for nearly every symbol."""
+    total = [dict(ac=set(), zrl=0, late=False, size=set(), dc=set()) for _ in range(2)]
+    for name in jc.COVERAGE_CASES:
+        for t, s in zip(total, entropy_stats(case_coefficients(name))):
+            t["ac"] |= s["ac"]
+            t["size"] |= s["size"]
+            t["dc"] |= s["dc"]
+            t["zrl"] = max(t["zrl"], s["zrl"])
+            t["late"] |= s["late"]
+    with capsys.disabled():
+        for slot, t in enumerate(total):
+            print(f"\n{'luma' if slot == 0 else 'chroma'} tables: {len(t['ac'])} of {len(ALL_AC)} AC symbols, missing "
+                  f"{sorted(hex(x) for x in ALL_AC - t['ac'])}; up to {t['zrl']} ZRLs in a block; {len(t['size'])} of 20 "
+                  f"signed AC sizes; {len(t['dc'])} of 23 signed DC categories", end="")
+        print()
+    for slot, t in enumerate(total):
+        assert t["ac"] <= ALL_AC
+        assert len(t["ac"]) >= 158, slot
+        assert ALL_AC - t["ac"] == MISSING_AC[slot], slot
+        assert t["zrl"] == 3, slot
+        assert t["late"], slot
+        assert t["size"] == {(n, sg) for n in range(1, 11) for sg in (1, -1)}, slot
+        assert t["dc"] == {(0, 0)} | {(n, sg) for n in range(1, 12) for sg in (1, -1)}, slot
+
+
+def test_three_zrls_occur_in_one_sweep_image_of_each_table():
+    """... so that encoding the sweep images one by one (as the GPU tests do) meets the third round of the ZRL loop."""
+    for slot, nm in ((0, "luma"), (1, "chroma")):
+        assert any(entropy_stats(case_coefficients(f"sweep_{nm}_q{q}"))[slot]["zrl"] == 3 for q in jc.SWEEP_QUALITIES)
+
+
+# --- the stuffing kernels' seams: conditions on Pillow's bytes ------------------------------------------------------
+
+@pytest.mark.parametrize("seed,restart,conditions", jc.SEAM_CASES, ids=lambda v: str(v) if isinstance(v, int) else None)
+def test_seam_frames_hold_their_conditions(seed, restart, conditions):
+    """If the installed libjpeg ever writes other bytes for these seeds, this fails: search again (seeds 0..399 at
+    restart intervals 0, 1, 2 held every condition) and replace jc.SEAM_CASES."""
+    img = jc.seam_frame(seed)
+    data = pillow(img, 100, 0, restart)
+    scan = jc.scan_of(data)
+    un, ffs = jc.unstuffed_data_ff(scan)
+    assert len(un) + len(ffs) == len(scan) and un.replace(b"\xff", b"\xff\x00").count(b"\xff\x00") >= len(ffs)
+    assert -(-len(un) // jc.SEAM_TILE) == 7
+    assert conditions <= jc.seam_conditions(data)
+    if "pair" in conditions:
+        assert restart in (1, 2)
+    assert ref.encode(img, 100, 0, restart) == data
+
+
+def test_seam_cases_cover_every_condition():
+    assert set().union(*(c for _, _, c in jc.SEAM_CASES)) == {"pair", "ones_rst", "ones_eoi", "tile_end", "tile_ffff"}
+
+
+def test_short_streams_are_as_short_as_the_gpu_tests_say():
+    """The streams put between long ones in one call.  A constant frame of the seam frames' size cannot be shorter
+    than a lane's 16 bytes (288 blocks of at least 4 bits are 144 bytes): it is shorter than a tile's first 11
+    lanes, and seven-tile frames surround it.  A constant 32 x 16 frame is shorter than one lane; the frames around
+    it (black and white noise, the most bytes a block takes here) stay inside one tile."""
+    H, W = jc.SEAM_SHAPE
+    assert len(jc.scan_of(pillow(jc.constant(H, W), 100, 0, 0))) == 168
+    H, W = jc.SHORT_SHAPE
+    for r in (0, 1):
+        n = len(jc.scan_of(pillow(jc.constant(H, W), 100, 0, r)))
+        assert n < 16 if r == 0 else n < 16 + 7 * 2 + 8  # seven RSTn markers and their padding
+    assert all(2048 < len(jc.scan_of(pillow(jc.binary_noise(H, W, s), 100, 0, 0))) < jc.SEAM_TILE for s in (0, 1))
+    for f in (jc.binary_noise(H, W, 0), jc.binary_noise(H, W, 1), jc.constant(H, W)):
+        assert all(ref.encode(f, 100, 0, r) == pillow(f, 100, 0, r) for r in (0, 1))
+
+
 @pytest.mark.parametrize("shape", [(37, 53), (1080, 1920)], ids=["37x53", "1080x1920"])
 def test_fm_jpeg_header_equals_pillow(shape):
     H, W = shape
@@ -99,6 +260,18 @@ def test_encoder_settings_rejected_before_any_device_call():
         with pytest.raises(_native.FMError):
             _native.MJpegEncoder(a["width"], a["height"], a["max_frames"], 0, a["quality"], a["subsampling"],
                                  a["restart_interval"])
+
+
+def test_encoder_refuses_frames_of_more_than_2_20_blocks_before_any_device_call():
+    """8192 x 8192 at 4:4:4 is 3 * 2^20 blocks: a frame's bit offsets are 32-bit, so FM_ENOTSUP, with a message."""
+    L = _native.load()
+    h = C.c_void_p()
+    assert L.fm_mjpeg_enc_create(0, 8192, 8192, 1, 95, 0, 0, C.byref(h)) == _native.FM_ENOTSUP
+    assert h.value and b"more than 2^20 blocks" in L.fm_mjpeg_enc_last_error(h)
+    L.fm_mjpeg_enc_destroy(h)
+    with pytest.raises(_native.FMError) as e:
+        _native.MJpegEncoder(8192, 8192, 1, 0, 95, 0, 0)
+    assert e.value.code == _native.FM_ENOTSUP
 
 
 # --- plumbing, with a stand-in encoder ------------------------------------------------------------------------
