@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "fm_internal.h"
+#include "fm_roi.h"
 
 namespace fm {
 hipError_t launch_pixel_pp(hipStream_t st, const PixelArgs& a, const double* bg_in, double* bg_out);
@@ -29,7 +30,8 @@ namespace {
 
 thread_local std::string g_last_error;
 
-enum class ResizeMode { Identity, Fast, General };
+using ResizeMode = AreaMode::Kind;
+constexpr fm_ctx* kNoCtx = nullptr;  // a failure before a context exists: fm_last_error(nullptr) has it
 
 }  // namespace
 
@@ -188,24 +190,19 @@ struct fm_ctx {
     }
 };
 
-namespace {
-
-int fail(fm_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
+namespace fm {
+// fm_host.h's failf for a context (FM_HIP_TRY(c, ...) too): the message is also the thread's last error
+int failf(fm_ctx* c, int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    vfailf(&g_last_error, code, fmt, ap);
     va_end(ap);
-    g_last_error = buf;
-    if (c) c->err = buf;
+    if (c) c->err = g_last_error;
     return code;
 }
+}  // namespace fm
 
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) return fail(ctx, FM_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
+namespace {
 
 // Device and page-locked memory of the context: every allocation is entered in c->dev_sizes /
 // c->pin_sizes (fm_footprint's totals), and ~fm_ctx frees whatever the two still hold.
@@ -213,7 +210,7 @@ template <class T>
 int dalloc(fm_ctx* c, T** p, size_t count) {
     if (count == 0) count = 1;
     hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) return fail(c, FM_ENOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+    if (e != hipSuccess) return failf(c, FM_ENOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
     c->dev_bytes += count * sizeof(T);
     c->dev_sizes[*p] = count * sizeof(T);
     return FM_OK;
@@ -258,27 +255,27 @@ int grow_pinned(fm_ctx* c, T** p, size_t* cap, size_t want, size_t count) {
     *p = nullptr;
     *cap = 0;
     hipError_t e = halloc(c, p, count * sizeof(T), hipHostMallocDefault);
-    if (e != hipSuccess) return fail(c, FM_ENOMEM, "hipHostMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+    if (e != hipSuccess) return failf(c, FM_ENOMEM, "hipHostMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
     *cap = want;
     return FM_OK;
 }
 
 int check_idle(fm_ctx* c) {
-    if (!c->inflight.empty()) return fail(c, FM_ESTATE, "a submit is in flight: call fm_wait first");
+    if (!c->inflight.empty()) return failf(c, FM_ESTATE, "a submit is in flight: call fm_wait first");
     return FM_OK;
 }
 
 int check_stream(fm_ctx* c, int stream) {
-    if (stream < 0 || stream >= c->p.n_streams) return fail(c, FM_EINVAL, "stream %d out of range", stream);
+    if (stream < 0 || stream >= c->p.n_streams) return failf(c, FM_EINVAL, "stream %d out of range", stream);
     return FM_OK;
 }
 
 // results of the last waited batch (device-side ones live until its slot is resubmitted)
 int check_frame(fm_ctx* c, int frame, int stream, bool device_data) {
     if (int rc = check_stream(c, stream)) return rc;
-    if (frame < 0 || frame >= c->ready) return fail(c, FM_EINVAL, "frame %d not in the last batch (%d frames)", frame, c->ready);
+    if (frame < 0 || frame >= c->ready) return failf(c, FM_EINVAL, "frame %d not in the last batch (%d frames)", frame, c->ready);
     if (device_data && (c->ready_slot < 0 || c->slots[c->ready_slot].gen != c->ready_gen))
-        return fail(c, FM_ESTATE, "the batch's device results were overwritten by a later submit");
+        return failf(c, FM_ESTATE, "the batch's device results were overwritten by a later submit");
     return FM_OK;
 }
 
@@ -287,12 +284,12 @@ int emit_all(fm_ctx* c, BatchSlot& B, size_t f, int count, std::vector<int32_t>&
     if (int rc = grow(c, &c->d_rec_all, &c->rec_all_cap, (size_t)count, (size_t)count * 5 + 1)) return rc;
     hipStream_t st = c->aux_stream;
     int32_t* cnt = c->d_rec_all + (size_t)count * 5;
-    HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(int32_t), st));
-    HIP_TRY(c, launch_emit_all(st, B.fa, (int)f, c->d_rec_all, cnt, count));
+    FM_HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(int32_t), st));
+    FM_HIP_TRY(c, launch_emit_all(st, B.fa, (int)f, c->d_rec_all, cnt, count));
     out.resize((size_t)count * 5 + 1);
-    HIP_TRY(c, hipMemcpyAsync(out.data(), c->d_rec_all, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (out.back() != count) return fail(c, FM_EHIP, "re-emit of frame %zu found %d contours, not %d", f, out.back(), count);
+    FM_HIP_TRY(c, hipMemcpyAsync(out.data(), c->d_rec_all, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(c, hipStreamSynchronize(st));
+    if (out.back() != count) return failf(c, FM_EHIP, "re-emit of frame %zu found %d contours, not %d", f, out.back(), count);
     out.pop_back();
     return FM_OK;
 }
@@ -304,30 +301,30 @@ int relabel_frame(fm_ctx* c, BatchSlot& B, size_t f, std::vector<int32_t>& out, 
     int32_t* dcnt = B.d_count + f;  // this frame's contour counter (the batch is finished)
     const uint8_t* mask = c->d_mask + f * c->work_plane;  // per-frame path: the batch's dilated masks
     if (c->use_fused) {
-        HIP_TRY(c, launch_expand_bits(st, B.d_dbits + f * c->ntiles * 64, B.d_candf + f * c->ntiles, c->d_mask, c->h,
+        FM_HIP_TRY(c, launch_expand_bits(st, B.d_dbits + f * c->ntiles * 64, B.d_candf + f * c->ntiles, c->d_mask, c->h,
                                       c->w, c->ntx));
         mask = c->d_mask;
     }
     for (int pass = 0; pass < 2; pass++) {
-        HIP_TRY(c, hipMemsetAsync(dcnt, 0, sizeof(int32_t), st));
-        HIP_TRY(c, hipMemsetAsync(c->d_outer, 0, c->work_plane, st));
+        FM_HIP_TRY(c, hipMemsetAsync(dcnt, 0, sizeof(int32_t), st));
+        FM_HIP_TRY(c, hipMemsetAsync(c->d_outer, 0, c->work_plane, st));
         // its own record buffer: the per-frame path's d_rec_dev holds [frames][max_contours] records
         // for every submit and must keep that size
         CclArgs ca{mask, c->d_label, c->d_outer, c->d_cid, dcnt, c->d_rec_one, 1, c->h, c->w, (int)c->rec_one_cap};
-        HIP_TRY(c, launch_ccl(st, ca, nullptr));
+        FM_HIP_TRY(c, launch_ccl(st, ca, nullptr));
         int32_t n = 0;
-        HIP_TRY(c, hipMemcpyAsync(&n, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
+        FM_HIP_TRY(c, hipMemcpyAsync(&n, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        FM_HIP_TRY(c, hipStreamSynchronize(st));
         if ((size_t)n <= c->rec_one_cap) {
             count = n;
             out.resize((size_t)n * 5);
-            HIP_TRY(c, hipMemcpyAsync(out.data(), c->d_rec_one, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
+            FM_HIP_TRY(c, hipMemcpyAsync(out.data(), c->d_rec_one, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            FM_HIP_TRY(c, hipStreamSynchronize(st));
             return FM_OK;
         }
         if (int rc = grow(c, &c->d_rec_one, &c->rec_one_cap, (size_t)n, (size_t)n * 5)) return rc;
     }
-    return fail(c, FM_EHIP, "pixel-level relabel of frame %zu did not converge", f);
+    return failf(c, FM_EHIP, "pixel-level relabel of frame %zu did not converge", f);
 }
 
 // FM_FLAG_CONTOUR_AREA: 2 x contourArea of every contour of the finished batch in slot B, traced
@@ -345,16 +342,16 @@ int contour_areas(fm_ctx* c, BatchSlot& B, size_t F) {
     if (int rc = grow(c, &c->d_area, &c->area_cap, n, n * 4)) return rc;
     hipStream_t st = c->aux_stream;
     std::vector<int32_t> a2(n);
-    HIP_TRY(c, hipMemcpyAsync(c->d_area, jobs.data(), n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, launch_contour_area(st, c->use_fused ? B.d_dbits : nullptr, c->use_fused ? B.d_candf : nullptr,
+    FM_HIP_TRY(c, hipMemcpyAsync(c->d_area, jobs.data(), n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(c, launch_contour_area(st, c->use_fused ? B.d_dbits : nullptr, c->use_fused ? B.d_candf : nullptr,
                                    c->use_fused ? nullptr : c->d_mask, c->ntiles, c->ntx, c->h, c->w, c->d_area, (int)n,
                                    c->d_area + n * 3));
-    HIP_TRY(c, hipMemcpyAsync(a2.data(), c->d_area + n * 3, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
+    FM_HIP_TRY(c, hipMemcpyAsync(a2.data(), c->d_area + n * 3, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(c, hipStreamSynchronize(st));
     size_t k = 0;
     for (size_t f = 0; f < F; f++)
         for (fm_contour& o : c->contours[f]) {
-            if (a2[k] < 0) return fail(c, FM_EHIP, "contour of frame %zu at (%d, %d) has no closed border", f, o.origin_x,
+            if (a2[k] < 0) return failf(c, FM_EHIP, "contour of frame %zu at (%d, %d) has no closed border", f, o.origin_x,
                                        o.origin_y);
             o.area2 = a2[k++];
         }
@@ -371,7 +368,7 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
     size_t n = 0;
     for (size_t f = 0; f < F; f++) n += c->contours[f].size();
     if (n == 0) return FM_OK;
-    if (n > 0x7fffffffull / 12) return fail(c, FM_ENOMEM, "%zu contours in one batch: too many to trace", n);
+    if (n > 0x7fffffffull / 12) return failf(c, FM_ENOMEM, "%zu contours in one batch: too many to trace", n);
     std::vector<int32_t> up(n * 9);  // jobs, then the three paths' lists
     std::vector<int32_t> path[kTracePaths];
     size_t k = 0;
@@ -393,25 +390,25 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
                  c->ntiles, c->ntx, c->h, c->w, d_jobs, d_jobs + n * 8,
                  {(int)path[0].size(), (int)path[1].size(), (int)path[2].size(), (int)path[3].size()}, d_res, nullptr, d_err};
     std::vector<int32_t> res(n * 3);
-    HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
-    HIP_TRY(c, launch_trace(st, ta, false, &c->timer));
-    HIP_TRY(c, hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
+    FM_HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(c, hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    FM_HIP_TRY(c, launch_trace(st, ta, false, &c->timer));
+    FM_HIP_TRY(c, hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(c, hipStreamSynchronize(st));
     size_t total = 0;
     k = 0;
     for (size_t f = 0; f < F; f++) {
         c->pts_off[f] = total;
         for (fm_contour& o : c->contours[f]) {
             const int32_t* r = &res[k * 3];
-            if (r[0] < 1) return fail(c, FM_EHIP, "contour of frame %zu at (%d, %d) has no closed border", f, o.origin_x,
+            if (r[0] < 1) return failf(c, FM_EHIP, "contour of frame %zu at (%d, %d) has no closed border", f, o.origin_x,
                                       o.origin_y);
             o.npts = r[0];
             o.area2 = r[1];
             c->trace_steps += r[2];
             up[k * 8 + 7] = (int32_t)total;
             total += (size_t)r[0];
-            if (total > 0x7fffffffull) return fail(c, FM_ENOMEM, "more than 2^31 contour points in one batch");
+            if (total > 0x7fffffffull) return failf(c, FM_ENOMEM, "more than 2^31 contour points in one batch");
             k++;
         }
     }
@@ -424,13 +421,13 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
     if (int rc = grow_pinned(c, &c->h_pts, &c->h_pts_cap, host_pts, host_pts * 2)) return rc;
     ta.pts = c->d_cpts;
     int32_t err = 0;
-    HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), n * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, launch_trace(st, ta, true, &c->timer));
-    HIP_TRY(c, hipMemcpyAsync(c->h_pts, c->d_cpts, total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&err, d_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
+    FM_HIP_TRY(c, hipMemcpyAsync(d_jobs, up.data(), n * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(c, launch_trace(st, ta, true, &c->timer));
+    FM_HIP_TRY(c, hipMemcpyAsync(c->h_pts, c->d_cpts, total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(c, hipMemcpyAsync(&err, d_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(c, hipStreamSynchronize(st));
     c->timer.collect();
-    if (err) return fail(c, FM_EHIP, "the emit pass of the contour trace disagreed with its count pass (code %d)", err);
+    if (err) return failf(c, FM_EHIP, "the emit pass of the contour trace disagreed with its count pass (code %d)", err);
     return FM_OK;
 }
 
@@ -448,39 +445,30 @@ const char* fm_last_error(const fm_ctx* ctx) { return ctx ? ctx->err.c_str() : g
 // so the two cannot disagree.
 static int plan_context(fm_ctx* c, const fm_params& p) {
     if (p.n_streams < 1 || p.src_w < 1 || p.src_h < 1 || p.box_size < 1 || p.max_batch < 1 || p.max_contours < 1)
-        return fail(nullptr, FM_EINVAL, "invalid geometry (streams %d, src %dx%d, box %d, batch %d, contours %d)",
+        return failf(kNoCtx, FM_EINVAL, "invalid geometry (streams %d, src %dx%d, box %d, batch %d, contours %d)",
                     p.n_streams, p.src_w, p.src_h, p.box_size, p.max_batch, p.max_contours);
     if (p.ksize < 1 || (p.ksize & 1) == 0 || p.ksize > kMaxK)
-        return fail(nullptr, FM_EINVAL, "ksize %d must be odd and in [1, %d]", p.ksize, kMaxK);
-    if (!(p.avg == p.avg)) return fail(nullptr, FM_EINVAL, "avg is NaN");
+        return failf(kNoCtx, FM_EINVAL, "ksize %d must be odd and in [1, %d]", p.ksize, kMaxK);
+    if (!(p.avg == p.avg)) return failf(kNoCtx, FM_EINVAL, "avg is NaN");
 
     c->p = p;
     c->w = p.box_size;
     c->h = (int)(p.src_h * ((double)p.box_size / (double)p.src_w));  // imutils.resize
-    if (c->h < 1) return fail(nullptr, FM_EINVAL, "work height is 0 (box %d, src %dx%d)", p.box_size, p.src_w, p.src_h);
-    if ((int64_t)c->h * c->w >= (1ll << 31) / 2) return fail(nullptr, FM_ENOTSUP, "work image too large");
+    if (c->h < 1) return failf(kNoCtx, FM_EINVAL, "work height is 0 (box %d, src %dx%d)", p.box_size, p.src_w, p.src_h);
+    if ((int64_t)c->h * c->w >= (1ll << 31) / 2) return failf(kNoCtx, FM_ENOTSUP, "work image too large");
 
     // resize mode (cv::resize: copy if same size; INTER_AREA needs scale >= 1)
-    if (c->h == p.src_h && c->w == p.src_w) {
-        c->rmode = ResizeMode::Identity;
-    } else {
-        const double sx = 1. / ((double)c->w / p.src_w), sy = 1. / ((double)c->h / p.src_h);
-        if (!(sx >= 1 && sy >= 1))
-            return fail(nullptr, FM_ENOTSUP, "box_size %d > frame width %d: INTER_AREA upscaling is bilinear in OpenCV, not supported",
-                        p.box_size, p.src_w);
-        const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
-        if (std::fabs(sx - isx) < 2.220446049250313e-16 && std::fabs(sy - isy) < 2.220446049250313e-16) {
-            c->rmode = ResizeMode::Fast;
-            c->fast_sx = isx;
-            c->fast_sy = isy;
-        } else {
-            c->rmode = ResizeMode::General;
-            if (!build_area_axis(p.src_w, c->w, sx, c->ax) || !build_area_axis(p.src_h, c->h, sy, c->ay))
-                return fail(nullptr, FM_ENOTSUP, "INTER_AREA table with non-consecutive taps");
-        }
-    }
-    if (!gaussian_taps(p.ksize, c->coef)) return fail(nullptr, FM_EINVAL, "bad ksize %d", p.ksize);
-    if (pixel_lds_bytes(p.ksize) > 160 * 1024) return fail(nullptr, FM_ENOTSUP, "ksize %d too large for the LDS tile", p.ksize);
+    const AreaMode m = area_resize_mode(p.src_w, p.src_h, c->w, c->h);
+    if (m.kind == AreaMode::Upscale)
+        return failf(kNoCtx, FM_ENOTSUP, "box_size %d > frame width %d: INTER_AREA upscaling is bilinear in OpenCV, not supported",
+                     p.box_size, p.src_w);
+    c->rmode = m.kind;
+    if (m.kind == AreaMode::Fast) c->fast_sx = m.isx, c->fast_sy = m.isy;
+    if (m.kind == AreaMode::General &&
+        (!build_area_axis(p.src_w, c->w, m.sx, c->ax) || !build_area_axis(p.src_h, c->h, m.sy, c->ay)))
+        return failf(kNoCtx, FM_ENOTSUP, "INTER_AREA table with non-consecutive taps");
+    if (!gaussian_taps(p.ksize, c->coef)) return failf(kNoCtx, FM_EINVAL, "bad ksize %d", p.ksize);
+    if (pixel_lds_bytes(p.ksize) > 160 * 1024) return failf(kNoCtx, FM_ENOTSUP, "ksize %d too large for the LDS tile", p.ksize);
 
     const int tiles = ((c->w + 63) / 64) * ((c->h + 63) / 64);
     c->use_fused = p.ksize <= fused_max_ksize() && fused_lds_bytes(p.ksize) <= 160 * 1024 &&
@@ -512,7 +500,7 @@ static const char* pixel_path_name(const fm_ctx* c) {
 }
 
 int fm_plan(const fm_params* prm, struct fm_plan* out) {
-    if (!prm || !out) return fail(nullptr, FM_EINVAL, "null argument");
+    if (!prm || !out) return failf(kNoCtx, FM_EINVAL, "null argument");
     std::memset(out, 0, sizeof *out);
     fm_ctx c;  // host fields only: nothing to release
     if (int rc = plan_context(&c, *prm)) return rc;
@@ -525,23 +513,23 @@ int fm_plan(const fm_params* prm, struct fm_plan* out) {
 }
 
 int fm_create(fm_ctx** out, const fm_params* prm) {
-    if (!out || !prm) return fail(nullptr, FM_EINVAL, "null argument");
+    if (!out || !prm) return failf(kNoCtx, FM_EINVAL, "null argument");
     *out = nullptr;
     const fm_params& p = *prm;
     std::unique_ptr<fm_ctx> c(new fm_ctx());
     if (int rc = plan_context(c.get(), p)) return rc;
 
     fm_ctx* cp = c.get();
-    HIP_TRY(cp, hipSetDevice(p.device));
+    FM_HIP_TRY(cp, hipSetDevice(p.device));
     // The pixel stream at high priority: it gets a hardware queue of its own instead of sharing one (in
     // order) with a contour-pass stream.  (Round 4 gave small work images' pixel stream 8 CUs of its own
     // -- k_pix5's chain / producer waves on two tiles were a latency chain the next resize starved; the
     // small-image path of round 5 runs a batch's frames in parallel over every CU instead.)
     {
         int lo = 0, hi = 0;
-        HIP_TRY(cp, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        FM_HIP_TRY(cp, hipDeviceGetStreamPriorityRange(&lo, &hi));
         if (dev_env("FM_PIX_PRIO_OFF")) hi = lo;
-        HIP_TRY(cp, hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, hi));
+        FM_HIP_TRY(cp, hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, hi));
     }
 #ifndef FM_CCL_QMODE_DEFAULT
 #define FM_CCL_QMODE_DEFAULT 2  // contour streams take their own hardware queues (A/B: +3 %)
@@ -558,10 +546,10 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     c->nccl = FM_NCCL_DEFAULT;
     if (const char* e = dev_env("FM_CCL_STREAMS")) c->nccl = std::max(1, std::min(kSlots, std::atoi(e)));
     if (ccl_qmode == 2)  // contour streams take hardware queues before the rarely used aux / input streams
-        for (int i = 0; i < c->nccl; i++) HIP_TRY(cp, hipStreamCreateWithFlags(&c->ccl_streams[i], hipStreamNonBlocking));
-    HIP_TRY(cp, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+        for (int i = 0; i < c->nccl; i++) FM_HIP_TRY(cp, hipStreamCreateWithFlags(&c->ccl_streams[i], hipStreamNonBlocking));
+    FM_HIP_TRY(cp, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
     // input stream: host-to-device copies and the resize run here, ahead of the pixel stream
-    if (!dev_env("FM_RESIZE_INLINE")) HIP_TRY(cp, hipStreamCreateWithFlags(&c->rs_stream, hipStreamNonBlocking));
+    if (!dev_env("FM_RESIZE_INLINE")) FM_HIP_TRY(cp, hipStreamCreateWithFlags(&c->rs_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
     c->timer.enabled = (p.flags & (FM_FLAG_PROFILE | FM_FLAG_PROFILE_PIX)) != 0;
     c->timer.pixel_only = !(p.flags & FM_FLAG_PROFILE);
@@ -594,7 +582,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         const size_t tf = frames * (size_t)c->ntiles;
         c->nquota = c->ntiles * kNodesPerTileFrame;
         const size_t nn = tf + tf * kNodesPerTileFrame + std::max(tf * kNodesShared, (size_t)c->ntiles * kTileMaxRuns);
-        if (nn >= (size_t)INT32_MAX) return fail(nullptr, FM_ENOTSUP, "batch too large for 32-bit node ids (%zu)", nn);
+        if (nn >= (size_t)INT32_MAX) return failf(kNoCtx, FM_ENOTSUP, "batch too large for 32-bit node ids (%zu)", nn);
         c->nnodes = (int)nn;
     }
     // Contour records: the fused path's mapped buffer holds the first rec_cap records of each frame (a
@@ -612,7 +600,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         if ((rc = dalloc(cp, &b.d_count, 3 * frames + 3))) return rc;
         // (k_frame_contours re-arms its slot-wide words at the end of each batch: they start at zero)
         if (hipMemset(b.d_count, 0, (3 * frames + 3) * sizeof(int32_t)) != hipSuccess)
-            return fail(cp, FM_EHIP, "hipMemset of the batch counters failed");
+            return failf(cp, FM_EHIP, "hipMemset of the batch counters failed");
         if ((p.flags & FM_FLAG_KEEP_PLANES) && (rc = dalloc(cp, &b.d_planes, px * 3))) return rc;
         if (c->use_fused) {
             if ((rc = dalloc(cp, &b.d_heavy, frames * c->ntiles)) ||
@@ -629,29 +617,29 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         }
         // contour records: mapped pinned host memory written directly by the kernels
         // (only the records that exist cross PCIe)
-        HIP_TRY(cp, halloc(cp, &b.h_rec, frames * (size_t)c->rec_cap * 5 * sizeof(int32_t), hipHostMallocMapped));
-        HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.d_rec, b.h_rec, 0));
-        HIP_TRY(cp, halloc(cp, &b.h_count, frames * sizeof(int32_t), hipHostMallocMapped));
-        HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_count, b.h_count, 0));
-        HIP_TRY(cp, halloc(cp, &b.h_overflow, frames * sizeof(int32_t), hipHostMallocMapped));
-        HIP_TRY(cp, halloc(cp, &b.h_stats, 2 * sizeof(int32_t), hipHostMallocMapped));
-        HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_stats, b.h_stats, 0));
-        HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_overflow, b.h_overflow, 0));
-        if (b.d_tflag) HIP_TRY(cp, hipMemset(b.d_tflag, 0, frames * c->ntiles * 8 * sizeof(uint32_t)));
-        HIP_TRY(cp, halloc(cp, &b.h_init, S, 0));
+        FM_HIP_TRY(cp, halloc(cp, &b.h_rec, frames * (size_t)c->rec_cap * 5 * sizeof(int32_t), hipHostMallocMapped));
+        FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.d_rec, b.h_rec, 0));
+        FM_HIP_TRY(cp, halloc(cp, &b.h_count, frames * sizeof(int32_t), hipHostMallocMapped));
+        FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_count, b.h_count, 0));
+        FM_HIP_TRY(cp, halloc(cp, &b.h_overflow, frames * sizeof(int32_t), hipHostMallocMapped));
+        FM_HIP_TRY(cp, halloc(cp, &b.h_stats, 2 * sizeof(int32_t), hipHostMallocMapped));
+        FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_stats, b.h_stats, 0));
+        FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_overflow, b.h_overflow, 0));
+        if (b.d_tflag) FM_HIP_TRY(cp, hipMemset(b.d_tflag, 0, frames * c->ntiles * 8 * sizeof(uint32_t)));
+        FM_HIP_TRY(cp, halloc(cp, &b.h_init, S, 0));
         if (i < c->nccl && ccl_qmode != 2) {
             if (ccl_qmode == 1) {
                 int lo = 0, hi = 0;
-                HIP_TRY(cp, hipDeviceGetStreamPriorityRange(&lo, &hi));
-                HIP_TRY(cp, hipStreamCreateWithPriority(&c->ccl_streams[i], hipStreamNonBlocking, hi));
+                FM_HIP_TRY(cp, hipDeviceGetStreamPriorityRange(&lo, &hi));
+                FM_HIP_TRY(cp, hipStreamCreateWithPriority(&c->ccl_streams[i], hipStreamNonBlocking, hi));
             } else {
-                HIP_TRY(cp, hipStreamCreateWithFlags(&c->ccl_streams[i], hipStreamNonBlocking));
+                FM_HIP_TRY(cp, hipStreamCreateWithFlags(&c->ccl_streams[i], hipStreamNonBlocking));
             }
         }
         b.ccl_stream = c->ccl_streams[i % c->nccl];
         if (i < c->nccl) c->timer.extra.push_back(b.ccl_stream);  // fold_stamps waits for it too
         for (hipEvent_t* ev : {&b.ev_pix, &b.ev_done, &b.ev_rs, &b.ev_lab, &b.ev_in})
-            HIP_TRY(cp, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+            FM_HIP_TRY(cp, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     }
     // pixel-level CCL: the whole batch on the v1 path, one frame for the fused path's overflow fallback
     const size_t ccl_px = c->use_fused ? c->work_plane : px;
@@ -661,18 +649,18 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         (rc = dalloc(cp, &c->d_rec_one, (size_t)p.max_contours * 5)))
         return rc;
     c->rec_one_cap = (size_t)p.max_contours;
-    HIP_TRY(cp, halloc(cp, &c->h_err, sizeof(int32_t), hipHostMallocMapped));
-    HIP_TRY(cp, hipHostGetDevicePointer((void**)&c->dh_err, c->h_err, 0));
+    FM_HIP_TRY(cp, halloc(cp, &c->h_err, sizeof(int32_t), hipHostMallocMapped));
+    FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&c->dh_err, c->h_err, 0));
     *c->h_err = 0;
-    HIP_TRY(cp, hipMemset(c->d_has_keep, 0, S));
-    HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * sizeof(double)));
-    HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * sizeof(double)));
+    FM_HIP_TRY(cp, hipMemset(c->d_has_keep, 0, S));
+    FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * sizeof(double)));
+    FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * sizeof(double)));
     if (c->rmode == ResizeMode::General) {
         auto up = [&](auto** d, const auto& v) -> int {
             int r = dalloc(cp, d, v.size());
             if (r) return r;
             hipError_t e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-            return e == hipSuccess ? 0 : fail(cp, FM_EHIP, "hipMemcpy tables: %s", hipGetErrorString(e));
+            return e == hipSuccess ? 0 : failf(cp, FM_EHIP, "hipMemcpy tables: %s", hipGetErrorString(e));
         };
         if ((rc = up(&c->d_xofs, c->ax.ofs)) || (rc = up(&c->d_xcnt, c->ax.cnt)) || (rc = up(&c->d_xwt, c->ax.wt)) ||
             (rc = up(&c->d_yofs, c->ay.ofs)) || (rc = up(&c->d_ycnt, c->ay.cnt)) || (rc = up(&c->d_ywt, c->ay.wt)))
@@ -687,7 +675,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         if (const char* e = dev_env("FM_PTS_RING")) c->pts_ring = std::max(1, std::min(256, std::atoi(e)));
         const size_t n = (size_t)S * c->ntiles * 36 * c->pts_ring;
         if ((rc = dalloc(cp, &c->d_pts, n))) return rc;
-        HIP_TRY(cp, hipMemset(c->d_pts, 0, n * sizeof(uint64_t)));
+        FM_HIP_TRY(cp, hipMemset(c->d_pts, 0, n * sizeof(uint64_t)));
     }
     if (dev_env("FM_TS") && c->use_fused) {
         if ((rc = dalloc(cp, &c->d_ts, frames * c->ntiles * 16))) return rc;
@@ -696,7 +684,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     }
     // the initialising hipMemset calls run on the null stream, which does not order the
     // context's non-blocking streams: finish them before the first submit can read the buffers
-    HIP_TRY(cp, hipDeviceSynchronize());
+    FM_HIP_TRY(cp, hipDeviceSynchronize());
     *out = c.release();
     return FM_OK;
 }
@@ -731,45 +719,45 @@ void fm_destroy(fm_ctx* c) {
 }
 
 int fm_host_alloc(fm_ctx* c, size_t bytes, void** out) {
-    if (!c || !out) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
     *out = nullptr;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    HIP_TRY(c, hipHostMalloc(out, bytes, hipHostMallocPortable));
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipHostMalloc(out, bytes, hipHostMallocPortable));
     return FM_OK;
 }
 
 int fm_host_free(fm_ctx* c, void* ptr) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if (ptr) HIP_TRY(c, hipHostFree(ptr));
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (ptr) FM_HIP_TRY(c, hipHostFree(ptr));
     return FM_OK;
 }
 
-int fm_max_inflight(const fm_ctx* c) { return c ? c->nslots : fail(nullptr, FM_EINVAL, "null context"); }
+int fm_max_inflight(const fm_ctx* c) { return c ? c->nslots : failf(kNoCtx, FM_EINVAL, "null context"); }
 
 int fm_work_size(const fm_ctx* c, int* h, int* w) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (h) *h = c->h;
     if (w) *w = c->w;
     return FM_OK;
 }
 
 int fm_set_mask(fm_ctx* c, int stream, const uint8_t* keep) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
-    HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const uint8_t flag = keep ? 1 : 0;
     if (keep)
-        HIP_TRY(c, hipMemcpyAsync(c->d_keep + (size_t)stream * c->work_plane, keep, c->work_plane,
+        FM_HIP_TRY(c, hipMemcpyAsync(c->d_keep + (size_t)stream * c->work_plane, keep, c->work_plane,
                                   hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_has_keep + stream, &flag, 1, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    FM_HIP_TRY(c, hipMemcpyAsync(c->d_has_keep + stream, &flag, 1, hipMemcpyHostToDevice, c->stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->has_keep[stream] = flag;
     return FM_OK;
 }
 
 int fm_reset_stream(fm_ctx* c, int stream) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     c->bg_init[stream] = 0;
@@ -777,7 +765,7 @@ int fm_reset_stream(fm_ctx* c, int stream) {
 }
 
 int fm_set_hip_stream(fm_ctx* c, void* s) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (int rc = check_idle(c)) return rc;
     c->stream = s ? (hipStream_t)s : c->own_stream;
     c->timer.stream = c->stream;
@@ -816,7 +804,7 @@ int pick_input_stream(fm_ctx* c, const BatchInput& in, int si, hipStream_t* rs) 
     // the pixel stream waits for its batch's event, so the order of the batches is unchanged.
     if (FM_RS_TWO && c->rs_stream && in.kind != InputKind::Jpeg && c->rmode != ResizeMode::Identity && (si & 1)) {
         if (!c->rs_stream2) {
-            HIP_TRY(c, hipStreamCreateWithFlags(&c->rs_stream2, hipStreamNonBlocking));
+            FM_HIP_TRY(c, hipStreamCreateWithFlags(&c->rs_stream2, hipStreamNonBlocking));
             c->timer.stream3 = c->rs_stream2;
         }
         *rs = c->rs_stream2;
@@ -839,9 +827,9 @@ int stage_yuv(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, siz
     if (in.kind == InputKind::YuvList) {
         if (!B.d_ytab)
             if (int rc = dalloc(c, &B.d_ytab, cap)) return rc;
-        if (!B.h_ytab) HIP_TRY(c, halloc(c, &B.h_ytab, cap * sizeof(uint8_t*), hipHostMallocDefault));
+        if (!B.h_ytab) FM_HIP_TRY(c, halloc(c, &B.h_ytab, cap * sizeof(uint8_t*), hipHostMallocDefault));
         std::copy(in.ptrs, in.ptrs + F, B.h_ytab);  // (the slot is idle: its last batch was waited for)
-        HIP_TRY(c, hipMemcpyAsync(B.d_ytab, B.h_ytab, F * sizeof(uint8_t*), hipMemcpyHostToDevice, rs));
+        FM_HIP_TRY(c, hipMemcpyAsync(B.d_ytab, B.h_ytab, F * sizeof(uint8_t*), hipMemcpyHostToDevice, rs));
         ya.srcs = B.d_ytab;
     } else if (!in.on_device) {
         const size_t bytes = (F - 1) * y.stride + y.extent;
@@ -849,7 +837,7 @@ int stage_yuv(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, siz
             const size_t want = std::max(bytes, (cap - 1) * y.stride + y.extent);
             if (int rc = grow(c, &B.d_yuv, &B.yuv_cap, want, want)) return rc;
         }
-        HIP_TRY(c, hipMemcpyAsync(B.d_yuv, in.frames, bytes, hipMemcpyHostToDevice, rs));
+        FM_HIP_TRY(c, hipMemcpyAsync(B.d_yuv, in.frames, bytes, hipMemcpyHostToDevice, rs));
         ya.src = B.d_yuv;
     }
     ya.frame_stride = y.stride;
@@ -860,7 +848,7 @@ int stage_yuv(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, siz
     ya.W = c->p.src_w;
     ya.H = c->p.src_h;
     ya.F = (int)F;
-    HIP_TRY(c, c->timer.timed(rs, "yuv2bgr", [&](uint64_t* ks, uint64_t*) {
+    FM_HIP_TRY(c, c->timer.timed(rs, "yuv2bgr", [&](uint64_t* ks, uint64_t*) {
         ya.kstamp = ks;
         return launch_yuv2bgr(rs, ya);
     }));
@@ -879,17 +867,17 @@ int stage_input(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, c
     const size_t F = (size_t)in.n * S, fb = c->src_frame_bytes;
     switch (in.kind) {
         case InputKind::Bgr:
-            HIP_TRY(c, hipMemcpyAsync(B.d_in, in.frames, F * fb, hipMemcpyHostToDevice, rs));
+            FM_HIP_TRY(c, hipMemcpyAsync(B.d_in, in.frames, F * fb, hipMemcpyHostToDevice, rs));
             break;
         case InputKind::BgrStreams:  // stream s's frames -> rows s, S + s, 2S + s, ... of the [t][s] batch layout
             for (int s = 0; s < S; s++)
-                HIP_TRY(c, hipMemcpy2DAsync(B.d_in + (size_t)s * fb, (size_t)S * fb, in.ptrs[s], fb, fb, (size_t)in.n,
+                FM_HIP_TRY(c, hipMemcpy2DAsync(B.d_in + (size_t)s * fb, (size_t)S * fb, in.ptrs[s], fb, fb, (size_t)in.n,
                                             in.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, rs));
             break;
         case InputKind::Jpeg: {  // the decode side (§8(f)-3): JPEGs -> BGR frames in the batch's device buffer
             const int rc = fm_mjpeg_enqueue(in.dec, in.ptrs, in.sizes, (int)F, B.d_in, rs);
-            HIP_TRY(c, hipSetDevice(c->p.device));
-            if (rc) return fail(c, rc, "JPEG decode: %s", fm_mjpeg_last_error(in.dec));
+            FM_HIP_TRY(c, hipSetDevice(c->p.device));
+            if (rc) return failf(c, rc, "JPEG decode: %s", fm_mjpeg_last_error(in.dec));
             break;
         }
         case InputKind::Yuv:
@@ -903,12 +891,12 @@ int stage_input(fm_ctx* c, BatchSlot& B, const BatchInput& in, hipStream_t rs, c
 int resize_input(fm_ctx* c, BatchSlot& B, hipStream_t rs, const uint8_t* src, size_t F, const uint8_t** work) {
     *work = c->rmode == ResizeMode::Identity ? src : B.d_work;
     if (c->rmode == ResizeMode::General)
-        HIP_TRY(c, c->timer.timed(rs, "resize_area", [&](uint64_t* ks, uint64_t*) {
+        FM_HIP_TRY(c, c->timer.timed(rs, "resize_area", [&](uint64_t* ks, uint64_t*) {
             return launch_resize_area(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->d_xofs, c->d_xcnt,
                                       c->d_xwt, c->ax.max_taps, c->d_yofs, c->d_ycnt, c->d_ywt, c->ay.max_taps, nullptr, ks);
         }));
     else if (c->rmode == ResizeMode::Fast)
-        HIP_TRY(c, c->timer.timed(rs, "resize_area_fast", [&](uint64_t* ks, uint64_t*) {
+        FM_HIP_TRY(c, c->timer.timed(rs, "resize_area_fast", [&](uint64_t* ks, uint64_t*) {
             return launch_resize_area_fast(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->fast_sx,
                                            c->fast_sy, ks);
         }));
@@ -977,9 +965,9 @@ FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool a
 int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
     hipStream_t ps = c->stream;
     const int n = fa.T;
-    if (c->d_ts) HIP_TRY(c, hipMemsetAsync(c->d_ts, 0, (size_t)n * fa.S * c->ntiles * 16 * sizeof(uint64_t), ps));
+    if (c->d_ts) FM_HIP_TRY(c, hipMemsetAsync(c->d_ts, 0, (size_t)n * fa.S * c->ntiles * 16 * sizeof(uint64_t), ps));
     if (!c->use_pix) {
-        HIP_TRY(c, launch_fused(ps, fa, &c->timer));
+        FM_HIP_TRY(c, launch_fused(ps, fa, &c->timer));
         c->bg_cur ^= 1;
         return FM_OK;
     }
@@ -993,15 +981,15 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
         fp.bg_out = c->d_bg[c->bg_cur ^ 1];
         if (!init) fp.init = nullptr;
         if (c->use_small)  // not stamping (FM_FLAG_PROFILE, or the stamp ring full): the pair timed by events
-            HIP_TRY(c, c->timer.timed(ps, init ? "small_blur_init" : "small_blur", [&](uint64_t* k1, uint64_t* k2) {
+            FM_HIP_TRY(c, c->timer.timed(ps, init ? "small_blur_init" : "small_blur", [&](uint64_t* k1, uint64_t* k2) {
                 return launch_small(ps, fp, B.d_sblur, k1, k2);
             }, true, init ? "small_scan_init" : "small_scan", init ? "small_init" : "small"));
         else if (c->use_wide)
-            HIP_TRY(c, c->timer.timed(ps, init ? "wide_blur_init" : "wide_blur", [&](uint64_t* k1, uint64_t* k2) {
+            FM_HIP_TRY(c, c->timer.timed(ps, init ? "wide_blur_init" : "wide_blur", [&](uint64_t* k1, uint64_t* k2) {
                 return launch_wide(ps, fp, B.d_wblur, k1, k2);
             }, true, init ? "wide_scan_init" : "wide_scan", init ? "wide_init" : "wide"));
         else
-            HIP_TRY(c, c->timer.timed(ps, name, [&](uint64_t* ks, uint64_t*) {
+            FM_HIP_TRY(c, c->timer.timed(ps, name, [&](uint64_t* ks, uint64_t*) {
                 fp.kstamp = ks;
                 return launch_pix(ps, fp, planes, init);
             }));
@@ -1025,12 +1013,12 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
 int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
     hipStream_t ps = c->stream, cs = c->serial ? ps : B.ccl_stream;
     const size_t F = (size_t)fa.T * fa.S;
-    HIP_TRY(c, hipEventRecord(B.ev_pix, ps));
-    HIP_TRY(c, hipStreamWaitEvent(cs, B.ev_pix, 0));
+    FM_HIP_TRY(c, hipEventRecord(B.ev_pix, ps));
+    FM_HIP_TRY(c, hipStreamWaitEvent(cs, B.ev_pix, 0));
     if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
         FusedArgs fc = fa;
         // stamped by the dev build only; FM_FLAG_PROFILE: events around it (a contour stream: never in the pixel-only mode)
-        HIP_TRY(c, c->timer.timed(cs, "frame_contours", [&](uint64_t* ks, uint64_t*) {
+        FM_HIP_TRY(c, c->timer.timed(cs, "frame_contours", [&](uint64_t* ks, uint64_t*) {
             fc.kstamp = ks;
             // the slot-wide words (shared pool, heavy tally, frames done) sit at indices that depend on the batch's
             // frame count; the last workgroup re-arms them for a batch of the same size, so a slot whose batch size
@@ -1049,11 +1037,11 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
         // (+1.5 %, 388.1 vs 382.3 k, 4 alternating rounds, round 3)
         hipEvent_t gate_wait = nullptr;
         if (!c->serial && c->lab_prev >= 0 && c->lab_prev != si) gate_wait = c->slots[c->lab_prev].ev_lab;
-        HIP_TRY(c, launch_tile_ccl(cs, fa, c->use_pix, &c->timer, gate_wait, B.ev_lab));
+        FM_HIP_TRY(c, launch_tile_ccl(cs, fa, c->use_pix, &c->timer, gate_wait, B.ev_lab));
         c->lab_prev = si;
     }
     B.fa = fa;
-    HIP_TRY(c, hipEventRecord(B.ev_done, cs));
+    FM_HIP_TRY(c, hipEventRecord(B.ev_done, cs));
     return FM_OK;
 }
 
@@ -1063,7 +1051,7 @@ int run_per_frame(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool any_
     const int S = c->p.n_streams;
     const size_t F = (size_t)n * S;
     const long long npx = (long long)c->work_plane;
-    HIP_TRY(c, hipMemsetAsync(B.d_count, 0, (2 * F + 1) * sizeof(int32_t), ps));
+    FM_HIP_TRY(c, hipMemsetAsync(B.d_count, 0, (2 * F + 1) * sizeof(int32_t), ps));
     PixelArgs a{};
     a.bg = nullptr;
     a.keep = c->d_keep;
@@ -1088,41 +1076,41 @@ int run_per_frame(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool any_
             a.blur_out = B.d_planes + F * c->work_plane + (size_t)t * step_px;
             a.delta_out = B.d_planes + 2 * F * c->work_plane + (size_t)t * step_px;
         }
-        HIP_TRY(c, c->timer.timed(ps, "pixel", [&](uint64_t*, uint64_t*) {
+        FM_HIP_TRY(c, c->timer.timed(ps, "pixel", [&](uint64_t*, uint64_t*) {
             return launch_pixel_pp(ps, a, c->d_bg[c->bg_cur], c->d_bg[c->bg_cur ^ 1]);
         }, false));
         c->bg_cur ^= 1;
     }
-    HIP_TRY(c, hipMemsetAsync(c->d_outer, 0, F * c->work_plane, ps));
+    FM_HIP_TRY(c, hipMemsetAsync(c->d_outer, 0, F * c->work_plane, ps));
     CclArgs ca{c->d_mask, c->d_label, c->d_outer, c->d_cid, B.d_count, c->d_rec_dev, (int)F, c->h, c->w, c->p.max_contours};
-    HIP_TRY(c, launch_ccl(ps, ca, &c->timer));
-    HIP_TRY(c, hipMemcpyAsync(B.h_rec, c->d_rec_dev, F * c->p.max_contours * 5 * sizeof(int32_t), hipMemcpyDeviceToHost,
+    FM_HIP_TRY(c, launch_ccl(ps, ca, &c->timer));
+    FM_HIP_TRY(c, hipMemcpyAsync(B.h_rec, c->d_rec_dev, F * c->p.max_contours * 5 * sizeof(int32_t), hipMemcpyDeviceToHost,
                               ps));
-    HIP_TRY(c, hipMemsetAsync(B.d_count + F, 0, F * sizeof(int32_t), ps));
-    HIP_TRY(c, hipMemcpyAsync(B.h_overflow, B.d_count + F, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
-    HIP_TRY(c, hipMemcpyAsync(B.h_count, B.d_count, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
-    HIP_TRY(c, hipEventRecord(B.ev_done, ps));
+    FM_HIP_TRY(c, hipMemsetAsync(B.d_count + F, 0, F * sizeof(int32_t), ps));
+    FM_HIP_TRY(c, hipMemcpyAsync(B.h_overflow, B.d_count + F, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
+    FM_HIP_TRY(c, hipMemcpyAsync(B.h_count, B.d_count, F * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
+    FM_HIP_TRY(c, hipEventRecord(B.ev_done, ps));
     return FM_OK;
 }
 
 // One batch into the next slot: its input staged and resized on an input stream, the pixel kernels on the
 // pixel stream, the contour pass on the slot's stream.  fm_wait takes the slots in submission order.
 int submit(fm_ctx* c, BatchInput in) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if ((int)c->inflight.size() >= c->nslots)
-        return fail(c, FM_ESTATE, "%d batch(es) already in flight: call fm_wait first", (int)c->inflight.size());
+        return failf(c, FM_ESTATE, "%d batch(es) already in flight: call fm_wait first", (int)c->inflight.size());
     const int S = c->p.n_streams, n = in.n;
     if (in.kind == InputKind::BgrStreams) {
         for (int s = 0; s < S; s++)
-            if (!in.ptrs[s]) return fail(c, FM_EINVAL, "null frames for stream %d", s);
+            if (!in.ptrs[s]) return failf(c, FM_EINVAL, "null frames for stream %d", s);
         if (in.on_device && S == 1) {  // one stream: [n][1] is the contiguous layout, read in place
             in.kind = InputKind::Bgr;
             in.frames = in.ptrs[0];
         }
     }
     if ((in.kind == InputKind::Bgr && !in.frames) || n < 1 || n > c->p.max_batch)
-        return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d] or null frames", n, c->p.max_batch);
-    HIP_TRY(c, hipSetDevice(c->p.device));
+        return failf(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d] or null frames", n, c->p.max_batch);
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const int si = c->next_slot;
     BatchSlot& B = c->slots[si];
     hipStream_t ps = c->stream, rs = nullptr;
@@ -1135,22 +1123,22 @@ int submit(fm_ctx* c, BatchInput in) {
     // before it touches the input.  (The context's own stream only ever carries this context's work, which
     // the input stream runs ahead of: no wait there.)
     if (rs != ps && ps != c->own_stream) {
-        HIP_TRY(c, hipEventRecord(B.ev_in, ps));
-        HIP_TRY(c, hipStreamWaitEvent(rs, B.ev_in, 0));
+        FM_HIP_TRY(c, hipEventRecord(B.ev_in, ps));
+        FM_HIP_TRY(c, hipStreamWaitEvent(rs, B.ev_in, 0));
     }
     if ((rc = stage_input(c, B, in, rs, &src, &staged)) ||
         (rc = resize_input(c, B, rs, src, (size_t)n * S, &work)))
         return rc;
     if (rs != ps && (staged || c->rmode != ResizeMode::Identity)) {  // something ran on the input stream
-        HIP_TRY(c, hipEventRecord(B.ev_rs, rs));
-        HIP_TRY(c, hipStreamWaitEvent(ps, B.ev_rs, 0));
+        FM_HIP_TRY(c, hipEventRecord(B.ev_rs, rs));
+        FM_HIP_TRY(c, hipStreamWaitEvent(ps, B.ev_rs, 0));
     }
     bool any_init = false;
     for (int s = 0; s < S; s++) {
         B.h_init[s] = c->bg_init[s] ? 0 : 1;
         any_init |= B.h_init[s] != 0;
     }
-    if (any_init) HIP_TRY(c, hipMemcpyAsync(c->d_init, B.h_init, S, hipMemcpyHostToDevice, ps));
+    if (any_init) FM_HIP_TRY(c, hipMemcpyAsync(c->d_init, B.h_init, S, hipMemcpyHostToDevice, ps));
     if (c->use_fused) {
         const FusedArgs fa = fused_args(c, B, work, n, any_init);
         if ((rc = run_pixel(c, B, fa, any_init)) || (rc = run_contours(c, B, si, fa))) return rc;
@@ -1172,23 +1160,23 @@ int fm_submit(fm_ctx* c, const uint8_t* frames, int n, int on_device) {
 }
 
 int fm_submit_streams(fm_ctx* c, const uint8_t* const* bgr, int n, int on_device) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if (!bgr) return fail(c, FM_EINVAL, "null stream pointer array");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (!bgr) return failf(c, FM_EINVAL, "null stream pointer array");
     return submit(c, {InputKind::BgrStreams, n, on_device != 0, nullptr, bgr});
 }
 
 int fm_submit_jpeg(fm_ctx* c, fm_mjpeg* dec, const uint8_t* const* jpegs, const size_t* sizes, int n) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if (!dec || !jpegs || !sizes) return fail(c, FM_EINVAL, "null decoder or JPEG arrays");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (!dec || !jpegs || !sizes) return failf(c, FM_EINVAL, "null decoder or JPEG arrays");
     // the decoder writes n * S frames of its own size into the batch's input buffer (sized for this
     // context's frames): refuse any mismatch before anything is enqueued
     int dw = 0, dh = 0, ddev = -1, dmax = 0;
-    if (fm_mjpeg_geometry(dec, &dw, &dh, &ddev, &dmax)) return fail(c, FM_EINVAL, "bad decoder");
+    if (fm_mjpeg_geometry(dec, &dw, &dh, &ddev, &dmax)) return failf(c, FM_EINVAL, "bad decoder");
     if (dw != c->p.src_w || dh != c->p.src_h || ddev != c->p.device)
-        return fail(c, FM_EINVAL, "decoder for %dx%d frames on device %d, context for %dx%d on device %d", dw, dh, ddev,
+        return failf(c, FM_EINVAL, "decoder for %dx%d frames on device %d, context for %dx%d on device %d", dw, dh, ddev,
                     c->p.src_w, c->p.src_h, c->p.device);
     if (n >= 1 && (long long)n * c->p.n_streams > dmax)
-        return fail(c, FM_EINVAL, "decoder takes %d frames per call, the batch has %lld", dmax,
+        return failf(c, FM_EINVAL, "decoder takes %d frames per call, the batch has %lld", dmax,
                     (long long)n * c->p.n_streams);
     return submit(c, {InputKind::Jpeg, n, false, nullptr, jpegs, dec, sizes});
 }
@@ -1225,29 +1213,29 @@ static const char* yuv_resolve(int W, int H, const fm_yuv_layout* L, YuvSrc& y) 
 
 int fm_yuv_frame_bytes(int width, int height, const fm_yuv_layout* layout, size_t* bytes) {
     if (bytes) *bytes = 0;
-    if (!bytes) return fail(nullptr, FM_EINVAL, "null argument");
+    if (!bytes) return failf(kNoCtx, FM_EINVAL, "null argument");
     YuvSrc y{};
-    if (const char* why = yuv_resolve(width, height, layout, y)) return fail(nullptr, FM_EINVAL, "%s", why);
+    if (const char* why = yuv_resolve(width, height, layout, y)) return failf(kNoCtx, FM_EINVAL, "%s", why);
     *bytes = y.extent;
     return FM_OK;
 }
 
 int fm_submit_yuv(fm_ctx* c, const uint8_t* frames, int n, const fm_yuv_layout* layout, int on_device) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if (!frames) return fail(c, FM_EINVAL, "null frames");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (!frames) return failf(c, FM_EINVAL, "null frames");
     YuvSrc y{};
-    if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return fail(c, FM_EINVAL, "%s", why);
+    if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return failf(c, FM_EINVAL, "%s", why);
     return submit(c, {InputKind::Yuv, n, on_device != 0, frames, nullptr, nullptr, nullptr, y});
 }
 
 int fm_submit_yuv_list(fm_ctx* c, const uint8_t* const* frames, int n, const fm_yuv_layout* layout) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    if (!frames) return fail(c, FM_EINVAL, "null frame address array");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (!frames) return failf(c, FM_EINVAL, "null frame address array");
     YuvSrc y{};
-    if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return fail(c, FM_EINVAL, "%s", why);
-    if (n < 1 || n > c->p.max_batch) return fail(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d]", n, c->p.max_batch);
+    if (const char* why = yuv_resolve(c->p.src_w, c->p.src_h, layout, y)) return failf(c, FM_EINVAL, "%s", why);
+    if (n < 1 || n > c->p.max_batch) return failf(c, FM_EINVAL, "n_frames %d outside [1, max_batch=%d]", n, c->p.max_batch);
     for (size_t i = 0; i < (size_t)n * c->p.n_streams; i++)
-        if (!frames[i]) return fail(c, FM_EINVAL, "null address for frame %zu", i);
+        if (!frames[i]) return failf(c, FM_EINVAL, "null address for frame %zu", i);
     return submit(c, {InputKind::YuvList, n, true, nullptr, frames, nullptr, nullptr, y});
 }
 
@@ -1280,7 +1268,7 @@ int fetch_whole_frames(fm_ctx* c, BatchSlot& B, size_t F, WholeFrames& whole) {
 // FM_TS (profiling): mean cycles between consecutive stamps of each labelled tile
 int fold_phase_stamps(fm_ctx* c, size_t F) {
     std::vector<uint64_t> ts(F * c->ntiles * 16);
-    HIP_TRY(c, hipMemcpy(ts.data(), c->d_ts, ts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    FM_HIP_TRY(c, hipMemcpy(ts.data(), c->d_ts, ts.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < F * c->ntiles; i++) {
         const uint64_t* t = &ts[i * 16];
         if (!t[1]) continue;
@@ -1331,9 +1319,9 @@ void records_to_contours(fm_ctx* c, const BatchSlot& B, size_t F, const WholeFra
 }  // namespace
 
 int fm_wait(fm_ctx* c) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (c->inflight.empty()) return FM_OK;
-    HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const int si = c->inflight.front();
     c->inflight.erase(c->inflight.begin());
     BatchSlot& B = c->slots[si];
@@ -1343,7 +1331,7 @@ int fm_wait(fm_ctx* c) {
     hipError_t e = hipEventSynchronize(B.ev_done);
     if (e != hipSuccess) {
         B.n = 0;
-        return fail(c, FM_EHIP, "hipEventSynchronize: %s", hipGetErrorString(e));
+        return failf(c, FM_EHIP, "hipEventSynchronize: %s", hipGetErrorString(e));
     }
 #ifdef FM_DEV_SWITCHES
     const auto hw1 = std::chrono::steady_clock::now();
@@ -1351,7 +1339,7 @@ int fm_wait(fm_ctx* c) {
     const int n = B.n;
     const size_t F = (size_t)n * c->p.n_streams;
 #ifdef FM_BOUNDS_CHECK
-    if (*c->h_err) return fail(c, FM_EHIP, "contour-pass bounds check failed: codes 0x%x", *c->h_err);
+    if (*c->h_err) return failf(c, FM_EHIP, "contour-pass bounds check failed: codes 0x%x", *c->h_err);
 #endif
     if (c->use_fused) {
         c->stats[0] = B.h_stats[0];
@@ -1395,17 +1383,17 @@ int fm_wait(fm_ctx* c) {
     return FM_OK;
 }
 
-int fm_last_fallbacks(const fm_ctx* c) { return c ? c->fallbacks : fail(nullptr, FM_EINVAL, "null context"); }
+int fm_last_fallbacks(const fm_ctx* c) { return c ? c->fallbacks : failf(kNoCtx, FM_EINVAL, "null context"); }
 
 int fm_last_ccl_stats(const fm_ctx* c, int32_t* shared_nodes, int32_t* heavy_tiles) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (shared_nodes) *shared_nodes = c->stats[0];
     if (heavy_tiles) *heavy_tiles = c->stats[1];
     return FM_OK;
 }
 
 int fm_last_trace_stats(const fm_ctx* c, int32_t* staged, int32_t* unstaged, int64_t* steps) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (staged) *staged = c->trace_n[0];
     if (unstaged) *unstaged = c->trace_n[1];
     if (steps) *steps = c->trace_steps;
@@ -1414,28 +1402,28 @@ int fm_last_trace_stats(const fm_ctx* c, int32_t* staged, int32_t* unstaged, int
 
 int fm_get_contour_points(fm_ctx* c, int frame, int stream, int32_t* xy, size_t cap, size_t* total) {
     if (total) *total = 0;
-    if (!c || !total) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !total) return failf(c, FM_EINVAL, "null argument");
     if (!(c->p.flags & FM_FLAG_CONTOUR_POINTS))
-        return fail(c, FM_ESTATE, "points not traced: create with FM_FLAG_CONTOUR_POINTS");
-    if (c->pts_off.empty()) return fail(c, FM_ESTATE, "no traced batch: call fm_wait first");
+        return failf(c, FM_ESTATE, "points not traced: create with FM_FLAG_CONTOUR_POINTS");
+    if (c->pts_off.empty()) return failf(c, FM_ESTATE, "no traced batch: call fm_wait first");
     if (int rc = check_frame(c, frame, stream, false)) return rc;
     const size_t f = (size_t)frame * c->p.n_streams + stream;
     const size_t first = c->pts_off[f], n = c->pts_off[f + 1] - first;
     *total = n;
-    if (cap < n) return fail(c, FM_EINVAL, "%zu points, room for %zu: call again with *total", n, cap);
-    if (n && !xy) return fail(c, FM_EINVAL, "null point buffer");
+    if (cap < n) return failf(c, FM_EINVAL, "%zu points, room for %zu: call again with *total", n, cap);
+    if (n && !xy) return failf(c, FM_EINVAL, "null point buffer");
     if (n) std::memcpy(xy, c->h_pts + first * 2, n * 2 * sizeof(int32_t));
     return FM_OK;
 }
 
 int fm_get_counts(fm_ctx* c, int32_t* counts) {
-    if (!c || !counts) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !counts) return failf(c, FM_EINVAL, "null argument");
     std::memcpy(counts, c->ready_counts.data(), c->ready_counts.size() * sizeof(int32_t));
     return FM_OK;
 }
 
 int fm_get_contours(fm_ctx* c, int frame, int stream, fm_contour* out, int cap) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (int rc = check_frame(c, frame, stream, false)) return rc;
     const size_t f = (size_t)frame * c->p.n_streams + stream;
     const auto& v = c->contours[f];
@@ -1445,98 +1433,98 @@ int fm_get_contours(fm_ctx* c, int frame, int stream, fm_contour* out, int cap) 
 }
 
 int fm_read_mask(fm_ctx* c, int frame, int stream, uint8_t* out) {
-    if (!c || !out) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
     if (int rc = check_frame(c, frame, stream, true)) return rc;
-    HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const size_t f = (size_t)frame * c->p.n_streams + stream;
     hipStream_t st = c->aux_stream;
     if (c->use_fused) {
         const BatchSlot& B = c->slots[c->ready_slot];
-        HIP_TRY(c, launch_expand_bits(st, B.d_dbits + f * c->ntiles * 64, B.d_candf + f * c->ntiles, c->d_mask, c->h, c->w,
+        FM_HIP_TRY(c, launch_expand_bits(st, B.d_dbits + f * c->ntiles * 64, B.d_candf + f * c->ntiles, c->d_mask, c->h, c->w,
                                       c->ntx));
-        HIP_TRY(c, hipMemcpyAsync(out, c->d_mask, c->work_plane, hipMemcpyDeviceToHost, st));
+        FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_mask, c->work_plane, hipMemcpyDeviceToHost, st));
     } else {
-        HIP_TRY(c, hipMemcpyAsync(out, c->d_mask + f * c->work_plane, c->work_plane, hipMemcpyDeviceToHost, st));
+        FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_mask + f * c->work_plane, c->work_plane, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(c, hipStreamSynchronize(st));
+    FM_HIP_TRY(c, hipStreamSynchronize(st));
     return FM_OK;
 }
 
 int fm_read_plane(fm_ctx* c, int plane, int frame, int stream, uint8_t* out) {
-    if (!c || !out) return fail(c, FM_EINVAL, "null argument");
-    if (plane < 0 || plane > FM_PLANE_SMALL) return fail(c, FM_EINVAL, "plane %d", plane);
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
+    if (plane < 0 || plane > FM_PLANE_SMALL) return failf(c, FM_EINVAL, "plane %d", plane);
     if (plane == FM_PLANE_SMALL && c->rmode == ResizeMode::Identity)
-        return fail(c, FM_ESTATE, "no resize (box_size = frame width): the frame is the work image");
+        return failf(c, FM_ESTATE, "no resize (box_size = frame width): the frame is the work image");
     if (plane != FM_PLANE_SMALL && !(c->p.flags & FM_FLAG_KEEP_PLANES))
-        return fail(c, FM_ESTATE, "planes not kept: create with FM_FLAG_KEEP_PLANES");
+        return failf(c, FM_ESTATE, "planes not kept: create with FM_FLAG_KEEP_PLANES");
     if (int rc = check_frame(c, frame, stream, true)) return rc;
-    HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const BatchSlot& B = c->slots[c->ready_slot];
     const size_t f = (size_t)frame * c->p.n_streams + stream;
     if (plane == FM_PLANE_SMALL) {  // the INTER_AREA output, [T][S][h][w][3]
-        HIP_TRY(c, hipMemcpyAsync(out, B.d_work + f * c->work_plane * 3, c->work_plane * 3, hipMemcpyDeviceToHost,
+        FM_HIP_TRY(c, hipMemcpyAsync(out, B.d_work + f * c->work_plane * 3, c->work_plane * 3, hipMemcpyDeviceToHost,
                                   c->aux_stream));
-        HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
+        FM_HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
         return FM_OK;
     }
     const size_t Fcur = (size_t)c->ready * c->p.n_streams;
-    HIP_TRY(c, hipMemcpyAsync(out, B.d_planes + ((size_t)plane * Fcur + f) * c->work_plane, c->work_plane,
+    FM_HIP_TRY(c, hipMemcpyAsync(out, B.d_planes + ((size_t)plane * Fcur + f) * c->work_plane, c->work_plane,
                               hipMemcpyDeviceToHost, c->aux_stream));
-    HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
     return FM_OK;
 }
 
 int fm_read_frame(fm_ctx* c, int frame, int stream, uint8_t* out) {
-    if (!c || !out) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
     if (int rc = check_frame(c, frame, stream, true)) return rc;
     const BatchSlot& B = c->slots[c->ready_slot];
-    if (!B.src) return fail(c, FM_ESTATE, "no source frames for the last waited batch");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    HIP_TRY(c, hipMemcpyAsync(out, B.src + ((size_t)frame * c->p.n_streams + stream) * c->src_frame_bytes,
+    if (!B.src) return failf(c, FM_ESTATE, "no source frames for the last waited batch");
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipMemcpyAsync(out, B.src + ((size_t)frame * c->p.n_streams + stream) * c->src_frame_bytes,
                               c->src_frame_bytes, hipMemcpyDeviceToHost, c->aux_stream));
-    HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
     return FM_OK;
 }
 
 int fm_frame_device(fm_ctx* c, int frame, int stream, const uint8_t** out) {
-    if (!c || !out) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
     if (int rc = check_frame(c, frame, stream, true)) return rc;
     const BatchSlot& B = c->slots[c->ready_slot];
-    if (!B.src) return fail(c, FM_ESTATE, "no source frames for the last waited batch");
+    if (!B.src) return failf(c, FM_ESTATE, "no source frames for the last waited batch");
     *out = B.src + ((size_t)frame * c->p.n_streams + stream) * c->src_frame_bytes;
     return FM_OK;
 }
 
 int fm_read_background(fm_ctx* c, int stream, double* out) {
-    if (!c || !out) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
-    if (!c->bg_init[stream]) return fail(c, FM_ESTATE, "stream %d has no background yet", stream);
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, c->work_plane * sizeof(double),
+    if (!c->bg_init[stream]) return failf(c, FM_ESTATE, "stream %d has no background yet", stream);
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, c->work_plane * sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FM_OK;
 }
 
 int fm_write_background(fm_ctx* c, int stream, const double* in) {
-    if (!c || !in) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !in) return failf(c, FM_EINVAL, "null argument");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    HIP_TRY(c, hipMemcpyAsync(c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, in, c->work_plane * sizeof(double),
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipMemcpyAsync(c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, in, c->work_plane * sizeof(double),
                               hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bg_init[stream] = 1;
     return FM_OK;
 }
 
 int fm_kernel_time_stats(fm_ctx* c, const char** names, double* ms, int64_t* launches, double* stamped_ms,
                          int64_t* stamped, double* ms_sq, double* busy_ms, int64_t* unstamped, int cap) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    if (c->timer.fold_stamps() != 0) return fail(c, FM_EHIP, "reading the launch stamps failed");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    if (c->timer.fold_stamps() != 0) return failf(c, FM_EHIP, "reading the launch stamps failed");
     const auto& T = c->timer;
     const int n = (int)T.names.size();
     for (int i = 0; i < std::min(n, cap); i++) {
@@ -1557,24 +1545,24 @@ int fm_kernel_times(fm_ctx* c, const char** names, double* ms, int64_t* launches
 }
 
 int fm_kernel_time_spread(fm_ctx* c, double* ms_sq, int cap) {
-    if (!c || !ms_sq) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !ms_sq) return failf(c, FM_EINVAL, "null argument");
     return fm_kernel_time_stats(c, nullptr, nullptr, nullptr, nullptr, nullptr, ms_sq, nullptr, nullptr, cap);
 }
 
 int fm_kernel_time_busy(fm_ctx* c, double* busy_ms, int cap) {
-    if (!c || !busy_ms) return fail(c, FM_EINVAL, "null argument");
+    if (!c || !busy_ms) return failf(c, FM_EINVAL, "null argument");
     return fm_kernel_time_stats(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, busy_ms, nullptr, cap);
 }
 
 int fm_reset_kernel_times(fm_ctx* c) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
-    HIP_TRY(c, hipSetDevice(c->p.device));
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
     c->timer.reset();
     return FM_OK;
 }
 
 int fm_footprint(const fm_ctx* c, size_t* device_bytes, size_t* pinned_bytes) {
-    if (!c) return fail(nullptr, FM_EINVAL, "null context");
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
     if (device_bytes) *device_bytes = c->dev_bytes;
     if (pinned_bytes) *pinned_bytes = c->pinned_bytes;
     return FM_OK;

@@ -28,7 +28,6 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +37,7 @@
 
 #include "../../include/find_motion_amd.h"
 #include "fm_internal.h"
+#include "fm_roi.h"
 
 namespace fm {
 namespace haar {
@@ -587,37 +587,26 @@ using namespace fm::haar;
 
 struct fm_haar {
     int device = 0;
-    hipStream_t stream = nullptr;
+    fm::Stream stream;  // (before the buffers used on it: they are released first)
     std::string err;
     int win_w = 0, win_h = 0, n_stages = 0, has_tilted = 0;
     // device cascade
-    void* d_blob = nullptr;
+    fm::DevBuf<uint8_t> d_blob;
     CascadeDev cd{};
     // grow-only work buffers
-    uint8_t *d_src = nullptr, *d_gray = nullptr, *d_rimg = nullptr;
-    uint32_t *d_S = nullptr, *d_Q = nullptr, *d_T = nullptr;
-    int8_t* d_res = nullptr;
-    int *d_live = nullptr, *d_nlive = nullptr;
-    size_t cap_live = 0;
-    int2* d_taps = nullptr;
-    uint8_t *d_raw = nullptr, *d_roi = nullptr;  // fm_haar_detect_frames: source frames, ROI frames
-    const uint8_t** d_fptr = nullptr;             // fm_haar_detect_frame_list: the frames' device addresses
-    const uint8_t** h_fptr = nullptr;             // their page-locked staging copy (an asynchronous DMA)
-    size_t cap_fptr = 0;
-    int32_t *d_axo = nullptr, *d_axc = nullptr, *d_ayo = nullptr, *d_ayc = nullptr;
-    float *d_axw = nullptr, *d_ayw = nullptr;
-    int area_key[4] = {0, 0, 0, 0};  // (W, H, w, h) the area tables are for
-    fm::AreaAxis ax, ay;
-    size_t cap_raw = 0, cap_roi = 0;
-    size_t cap_src = 0, cap_gray = 0, cap_rimg = 0, cap_S = 0, cap_Q = 0, cap_T = 0, cap_res = 0, cap_taps = 0;
+    fm::DevBuf<uint8_t> d_src, d_gray, d_rimg;
+    fm::DevBuf<uint32_t> d_S, d_Q, d_T;
+    fm::DevBuf<int8_t> d_res;
+    fm::DevBuf<int> d_live, d_nlive;
+    fm::DevBuf<int2> d_taps;
+    fm::RoiStage roi{true};  // fm_haar_detect_frames: source frames -> ROI frames
     std::vector<int8_t> h_res;
-    int *d_ccnt = nullptr, *d_cand = nullptr;  // k_hwalk: per image candidate count, candidate lists
-    int *h_ccnt = nullptr, *h_cand = nullptr;  // their page-locked host copies
-    size_t cap_cand = 0;
+    fm::DevBuf<int> d_ccnt, d_cand;  // k_hwalk: per image candidate count, candidate lists
+    fm::PinBuf<int> h_ccnt, h_cand;  // their page-locked host copies
     std::vector<int32_t> cand;  // last call's candidates of image 0 (x, y, w, h)
     double last_ms = 0.;
     int last_sweep = 0;  // the last detection's window sweep: 0 none, 1 k_hdetect, 2 k_heval + k_heval_tail
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    fm::Event e0, e1;
     // FM_HAAR_TIMES (dev build): host seconds per phase over all calls -- resize setup, geometry + launches,
     // result copy + wait, post-pass -- printed at destroy
     bool times = false;
@@ -630,36 +619,18 @@ struct fm_haar {
     std::vector<std::vector<int32_t>> out;  // grouped rects (x, y, w, h) of each image of the last detection
     Geo pend_g{};
     double pend_tA = 0., pend_tB = 0.;
+
+    ~fm_haar() {
+        if (times && ncalls)
+            std::fprintf(stderr, "[fm_haar] %lld calls, host ms per call: resize setup %.3f, geometry + launches %.3f, "
+                         "copy + wait %.3f, post-pass %.3f\n", ncalls, 1e3 * tph[0] / ncalls, 1e3 * tph[1] / ncalls,
+                         1e3 * tph[2] / ncalls, 1e3 * tph[3] / ncalls);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 static inline double hnow() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-static int hfail(fm_haar* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define HH(h, x)                                                                       \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) return hfail(h, FM_EHIP, "%s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-static int grow(fm_haar* h, T** p, size_t& cap, size_t count) {
-    if (count <= cap && *p) return 0;
-    if (*p) HH(h, hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    HH(h, hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
-    cap = count;
-    return 0;
 }
 
 static inline int rne_d(double v) { return (int)std::nearbyint(v); }
@@ -699,29 +670,29 @@ int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
     h->times = fm::dev_env("FM_HAAR_TIMES") != nullptr;  // (dev build only)
     if (!d || d->win_w < 3 || d->win_h < 3 || d->n_stages < 1 || d->n_trees < 1 || d->n_nodes < 1 ||
         d->n_features < 1 || d->n_leaves != d->n_trees + d->n_nodes)
-        return hfail(h, FM_EINVAL, "bad cascade description (window >= 3x3, stages/trees/nodes/features >= 1, "
+        return fm::failf(&h->err, FM_EINVAL, "bad cascade description (window >= 3x3, stages/trees/nodes/features >= 1, "
                                    "leaves == trees + nodes)");
     int tsum = 0;
     for (int s = 0; s < d->n_stages; ++s) {
-        if (d->stage_ntrees[s] < 1) return hfail(h, FM_EINVAL, "stage %d has no trees", s);
+        if (d->stage_ntrees[s] < 1) return fm::failf(&h->err, FM_EINVAL, "stage %d has no trees", s);
         tsum += d->stage_ntrees[s];
     }
-    if (tsum != d->n_trees) return hfail(h, FM_EINVAL, "stage tree counts sum to %d, not n_trees %d", tsum, d->n_trees);
+    if (tsum != d->n_trees) return fm::failf(&h->err, FM_EINVAL, "stage tree counts sum to %d, not n_trees %d", tsum, d->n_trees);
     int nsum = 0;
     for (int t = 0; t < d->n_trees; ++t) {
-        if (d->tree_nodes[t] < 1) return hfail(h, FM_EINVAL, "tree %d has no nodes", t);
+        if (d->tree_nodes[t] < 1) return fm::failf(&h->err, FM_EINVAL, "tree %d has no nodes", t);
         nsum += d->tree_nodes[t];
     }
-    if (nsum != d->n_nodes) return hfail(h, FM_EINVAL, "tree node counts sum to %d, not n_nodes %d", nsum, d->n_nodes);
+    if (nsum != d->n_nodes) return fm::failf(&h->err, FM_EINVAL, "tree node counts sum to %d, not n_nodes %d", nsum, d->n_nodes);
     // node links stay inside their tree; features inside the window
     for (int t = 0, o = 0; t < d->n_trees; o += d->tree_nodes[t], ++t)
         for (int k = 0; k < d->tree_nodes[t]; ++k) {
             const int l = d->node_left[o + k], r = d->node_right[o + k], f = d->node_feature[o + k];
             if (l >= d->tree_nodes[t] || r >= d->tree_nodes[t] || l < -d->tree_nodes[t] || r < -d->tree_nodes[t] ||
                 f < 0 || f >= d->n_features)
-                return hfail(h, FM_EINVAL, "tree %d node %d: link or feature out of range", t, k);
+                return fm::failf(&h->err, FM_EINVAL, "tree %d node %d: link or feature out of range", t, k);
             if ((l > 0 && l <= k) || (r > 0 && r <= k))
-                return hfail(h, FM_EINVAL, "tree %d node %d: links must point forward", t, k);
+                return fm::failf(&h->err, FM_EINVAL, "tree %d node %d: links must point forward", t, k);
         }
     int tilted = 0;
     for (int i = 0; i < d->n_features; ++i) {
@@ -734,21 +705,21 @@ int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
             const bool ok = !tl ? (x >= 0 && y >= 0 && w >= 0 && hh >= 0 && x + w <= d->win_w && y + hh <= d->win_h)
                                 : (w >= 0 && hh >= 0 && x - hh >= 0 && x + w <= d->win_w && y >= 0 &&
                                    y + w + hh <= d->win_h);
-            if (!ok) return hfail(h, FM_EINVAL, "feature %d rect %d outside the %dx%d window", i, j, d->win_w, d->win_h);
+            if (!ok) return fm::failf(&h->err, FM_EINVAL, "feature %d rect %d outside the %dx%d window", i, j, d->win_w, d->win_h);
         }
     }
     h->device = device;
-    HH(h, hipSetDevice(device));
+    FM_HIP_TRY(&h->err, hipSetDevice(device));
     {   // the detector's stream at the pixel stream's (high) priority: a motion engine on the same device
         // always has a pixel launch queued at high priority, and at normal priority the cascade's
         // launches waited behind them (configs[4]: a 1 ms call took 4.4 ms of wall time).  With the detection
         // asynchronous (round 5) the priority no longer matters: 63.6-63.9 k frames/s either way.
         int lo = 0, hi = 0;
-        HH(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HH(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, hi));
+        FM_HIP_TRY(&h->err, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        FM_HIP_TRY(&h->err, hipStreamCreateWithPriority(h->stream.put(), hipStreamNonBlocking, hi));
     }
-    HH(h, hipEventCreate(&h->e0));
-    HH(h, hipEventCreate(&h->e1));
+    FM_HIP_TRY(&h->err, hipEventCreate(h->e0.put()));
+    FM_HIP_TRY(&h->err, hipEventCreate(h->e1.put()));
     h->win_w = d->win_w;
     h->win_h = d->win_h;
     h->n_stages = d->n_stages;
@@ -832,9 +803,9 @@ int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
         std::memcpy(&blob[tot], recs.data(), recs.size() * sizeof(StumpRec));
         tot = blob.size();
     }
-    HH(h, hipMalloc(&h->d_blob, tot));
-    HH(h, hipMemcpy(h->d_blob, blob.data(), tot, hipMemcpyHostToDevice));
-    auto* b = (uint8_t*)h->d_blob;
+    FM_HIP_TRY(&h->err, h->d_blob.reserve(tot));
+    FM_HIP_TRY(&h->err, hipMemcpy(h->d_blob, blob.data(), tot, hipMemcpyHostToDevice));
+    const uint8_t* b = h->d_blob;
     h->cd = CascadeDev{d->win_w, d->win_h, d->n_stages, tilted, stumps,
                        (const int*)(b + off[0]), (const int*)(b + off[1]), (const float*)(b + off[2]),
                        (const int*)(b + off[3]), (const int*)(b + off[4]), (const Node*)(b + off[5]),
@@ -843,27 +814,7 @@ int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
     return FM_OK;
 }
 
-void fm_haar_destroy(fm_haar* h) {
-    if (!h) return;
-    if (h->times && h->ncalls)
-        std::fprintf(stderr, "[fm_haar] %lld calls, host ms per call: resize setup %.3f, geometry + launches %.3f, "
-                     "copy + wait %.3f, post-pass %.3f\n", h->ncalls, 1e3 * h->tph[0] / h->ncalls,
-                     1e3 * h->tph[1] / h->ncalls, 1e3 * h->tph[2] / h->ncalls, 1e3 * h->tph[3] / h->ncalls);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_blob, (void*)h->d_src, (void*)h->d_gray, (void*)h->d_rimg, (void*)h->d_S,
-                    (void*)h->d_Q, (void*)h->d_T, (void*)h->d_res, (void*)h->d_taps, (void*)h->d_raw, (void*)h->d_fptr, (void*)h->d_live, (void*)h->d_nlive,
-                    (void*)h->d_roi, (void*)h->d_axo, (void*)h->d_axc, (void*)h->d_ayo, (void*)h->d_ayc,
-                    (void*)h->d_axw, (void*)h->d_ayw})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)h->d_ccnt, (void*)h->d_cand})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)h->h_ccnt, (void*)h->h_cand, (void*)h->h_fptr})
-        if (p) (void)hipHostFree(p);
-    if (h->e0) (void)hipEventDestroy(h->e0);
-    if (h->e1) (void)hipEventDestroy(h->e1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void fm_haar_destroy(fm_haar* h) { delete h; }
 
 const char* fm_haar_last_error(const fm_haar* h) { return h ? h->err.c_str() : "null detector"; }
 
@@ -881,9 +832,9 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
                                double scale_factor, int min_neighbors, int min_w, int min_h, int max_w, int max_h) {
     if (!h || !h->d_blob) return FM_EINVAL;
     if (!images || n < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3) || !(scale_factor > 1.0))
-        return hfail(h, FM_EINVAL, "bad arguments (n >= 1, 1 or 3 channels, scale_factor > 1)");
-    if (h->pending) return hfail(h, FM_ESTATE, "a detection is already queued: collect it first");
-    HH(h, hipSetDevice(h->device));
+        return fm::failf(&h->err, FM_EINVAL, "bad arguments (n >= 1, 1 or 3 channels, scale_factor > 1)");
+    if (h->pending) return fm::failf(&h->err, FM_ESTATE, "a detection is already queued: collect it first");
+    FM_HIP_TRY(&h->err, hipSetDevice(h->device));
     const double tA = h->times ? hnow() : 0.;
     h->out.assign(n, {});
     h->pend_n = n;
@@ -912,7 +863,7 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
         sc.push_back(s);
     }
     if (sc.empty()) return FM_OK;
-    if ((int)sc.size() > MAXSC) return hfail(h, FM_ENOTSUP, "%zu scales (max %d)", sc.size(), MAXSC);
+    if ((int)sc.size() > MAXSC) return fm::failf(&h->err, FM_ENOTSUP, "%zu scales (max %d)", sc.size(), MAXSC);
     Geo g{};
     g.n = (int)sc.size();
     int ww0 = 0;
@@ -954,21 +905,21 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
         linear_exact_taps(H, g.sh[s], taps);
     }
     const size_t npx = (size_t)n * H * W;
-    int rc;
-    if ((rc = grow(h, &h->d_gray, h->cap_gray, npx)) || (rc = grow(h, &h->d_rimg, h->cap_rimg, (size_t)n * g.P)) ||
-        (rc = grow(h, &h->d_taps, h->cap_taps, taps.size())) || (rc = grow(h, &h->d_res, h->cap_res, (size_t)n * g.NW)))
-        return rc;
-    if ((rc = grow(h, &h->d_S, h->cap_S, (size_t)n * g.I)) || (rc = grow(h, &h->d_Q, h->cap_Q, (size_t)n * g.I)) ||
-        (h->has_tilted && (rc = grow(h, &h->d_T, h->cap_T, (size_t)n * g.I))))
-        return rc;
+    FM_HIP_TRY(&h->err, h->d_gray.reserve(npx));
+    FM_HIP_TRY(&h->err, h->d_rimg.reserve((size_t)n * g.P));
+    FM_HIP_TRY(&h->err, h->d_taps.reserve(taps.size()));
+    FM_HIP_TRY(&h->err, h->d_res.reserve((size_t)n * g.NW));
+    FM_HIP_TRY(&h->err, h->d_S.reserve((size_t)n * g.I));
+    FM_HIP_TRY(&h->err, h->d_Q.reserve((size_t)n * g.I));
+    if (h->has_tilted) FM_HIP_TRY(&h->err, h->d_T.reserve((size_t)n * g.I));
     const uint8_t* src = images;
     if (!on_device) {
-        if ((rc = grow(h, &h->d_src, h->cap_src, npx * channels))) return rc;
-        HH(h, hipMemcpyAsync(h->d_src, images, npx * channels, hipMemcpyHostToDevice, h->stream));
+        FM_HIP_TRY(&h->err, h->d_src.reserve(npx * channels));
+        FM_HIP_TRY(&h->err, hipMemcpyAsync(h->d_src, images, npx * channels, hipMemcpyHostToDevice, h->stream));
         src = h->d_src;
     }
-    HH(h, hipMemcpyAsync(h->d_taps, taps.data(), taps.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    HH(h, hipEventRecord(h->e0, h->stream));
+    FM_HIP_TRY(&h->err, hipMemcpyAsync(h->d_taps, taps.data(), taps.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->e0, h->stream));
     k_hgray<<<(unsigned)((npx + 255) / 256), 256, 0, h->stream>>>(src, h->d_gray, (long long)npx, channels);
     const long long np = (long long)n * g.P;
     k_hresize<<<(unsigned)((np + 255) / 256), 256, 0, h->stream>>>(h->d_gray, h->d_rimg, h->d_taps, g, W, H, n);
@@ -1007,9 +958,9 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
             goto swept;
         }
         h->last_sweep = 2;
-        if ((rc = grow(h, &h->d_live, h->cap_live, (size_t)nw))) return rc;
-        if (!h->d_nlive) HH(h, hipMalloc((void**)&h->d_nlive, sizeof(int)));
-        HH(h, hipMemsetAsync(h->d_nlive, 0, sizeof(int), h->stream));
+        FM_HIP_TRY(&h->err, h->d_live.reserve((size_t)nw));
+        FM_HIP_TRY(&h->err, h->d_nlive.reserve(1));
+        FM_HIP_TRY(&h->err, hipMemsetAsync(h->d_nlive, 0, sizeof(int), h->stream));
         k_heval<<<(unsigned)((nw + 255) / 256), 256, 0, h->stream>>>(h->d_S, h->d_Q, h->d_T, h->d_res, h->d_live,
                                                                      h->d_nlive, split, h->cd, g, n);
         // a thread per possible survivor (grid-stride only past 16384 blocks): a smaller fixed grid
@@ -1020,29 +971,18 @@ static int detect_enqueue_impl(fm_haar* h, const uint8_t* images, int n, int H, 
                                                       h->cd, g, n);
     }
 swept:
-    HH(h, hipGetLastError());
-    HH(h, hipEventRecord(h->e1, h->stream));
+    FM_HIP_TRY(&h->err, hipGetLastError());
+    FM_HIP_TRY(&h->err, hipEventRecord(h->e1, h->stream));
     // candidates: the row walk on the device, then only the per-image lists cross PCIe (page-locked)
-    if ((size_t)n > h->cap_cand) {
-        for (void* p : {(void*)h->d_ccnt, (void*)h->d_cand})
-            if (p) HH(h, hipFree(p));
-        for (void* p : {(void*)h->h_ccnt, (void*)h->h_cand})
-            if (p) HH(h, hipHostFree(p));
-        h->d_ccnt = h->d_cand = h->h_ccnt = h->h_cand = nullptr;
-        h->cap_cand = 0;
-        HH(h, hipMalloc((void**)&h->d_ccnt, (size_t)n * sizeof(int)));
-        HH(h, hipMalloc((void**)&h->d_cand, (size_t)n * kCandCap * sizeof(int)));
-        HH(h, hipHostMalloc((void**)&h->h_ccnt, (size_t)n * sizeof(int), 0));
-        HH(h, hipHostMalloc((void**)&h->h_cand, (size_t)n * kCandCap * sizeof(int), 0));
-        h->cap_cand = (size_t)n;
-    }
-    HH(h, hipMemsetAsync(h->d_ccnt, 0, (size_t)n * sizeof(int), h->stream));
+    FM_HIP_TRY(&h->err, fm::reserve_all((size_t)n, (size_t)n, h->d_ccnt, h->h_ccnt));
+    FM_HIP_TRY(&h->err, fm::reserve_all((size_t)n * kCandCap, (size_t)n * kCandCap, h->d_cand, h->h_cand));
+    FM_HIP_TRY(&h->err, hipMemsetAsync(h->d_ccnt, 0, (size_t)n * sizeof(int), h->stream));
     if (nw > 0 && g.NR > 0)
         k_hwalk<<<(unsigned)(((long long)n * g.NR + 63) / 64), 64, 0, h->stream>>>(h->d_res, h->d_ccnt, h->d_cand, g, n);
-    HH(h, hipGetLastError());
+    FM_HIP_TRY(&h->err, hipGetLastError());
     const double tB = h->times ? hnow() : 0.;
-    HH(h, hipMemcpyAsync(h->h_ccnt, h->d_ccnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HH(h, hipMemcpyAsync(h->h_cand, h->d_cand, (size_t)n * kCandCap * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    FM_HIP_TRY(&h->err, hipMemcpyAsync(h->h_ccnt, h->d_ccnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    FM_HIP_TRY(&h->err, hipMemcpyAsync(h->h_cand, h->d_cand, (size_t)n * kCandCap * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     h->pend_sc = sc;
     h->pend_g = g;
     h->pend_tA = tA;
@@ -1072,16 +1012,16 @@ static int detect_finish(fm_haar* h) {
     if (sc.empty()) return FM_OK;  // no scale (or an image smaller than the window): no detections
     const double tA = h->pend_tA, tB = h->pend_tB;
     const long long nw = (long long)n * g.NW;
-    HH(h, hipStreamSynchronize(h->stream));
+    FM_HIP_TRY(&h->err, hipStreamSynchronize(h->stream));
     bool overflow = false;
     for (int i = 0; i < n; ++i) overflow |= h->h_ccnt[i] > kCandCap;
     if (overflow) {  // some image has more accepted windows than a list holds: walk the whole grid here
         h->h_res.resize((size_t)nw);
-        HH(h, hipMemcpy(h->h_res.data(), h->d_res, (size_t)nw, hipMemcpyDeviceToHost));
+        FM_HIP_TRY(&h->err, hipMemcpy(h->h_res.data(), h->d_res, (size_t)nw, hipMemcpyDeviceToHost));
     }
     const double tC = h->times ? hnow() : 0.;
     float ms = 0.f;
-    HH(h, hipEventElapsedTime(&ms, h->e0, h->e1));
+    FM_HIP_TRY(&h->err, hipEventElapsedTime(&ms, h->e0, h->e1));
     h->last_ms = ms;
 
     // per image: the row scan with the stage-0 skip, then groupRectangles (eps 0.2); images are
@@ -1228,7 +1168,7 @@ int fm_haar_detect(fm_haar* h, const uint8_t* images, int n, int H, int W, int c
                    double scale_factor, int min_neighbors, int min_w, int min_h, int max_w, int max_h,
                    int32_t* rects, int cap, int32_t* counts) {
     if (!h || !h->d_blob) return FM_EINVAL;
-    if (cap < 0 || !counts || (cap > 0 && !rects)) return hfail(h, FM_EINVAL, "bad arguments (counts[n], rects[n][cap])");
+    if (cap < 0 || !counts || (cap > 0 && !rects)) return fm::failf(&h->err, FM_EINVAL, "bad arguments (counts[n], rects[n][cap])");
     if (int rc = detect_finish(h)) return rc;  // (a queued detection the caller never collected)
     if (int rc = detect_enqueue(h, images, n, H, W, channels, on_device, scale_factor, min_neighbors, min_w, min_h,
                                 max_w, max_h))
@@ -1260,102 +1200,21 @@ static int detect_frames_impl(fm_haar* h, const uint8_t* frames, const uint8_t* 
                               int cap, int32_t* counts, int* roi_h_out, bool async = false) {
     if (!h || !h->d_blob) return FM_EINVAL;
     if (h->pending) {
-        if (async) return hfail(h, FM_ESTATE, "a detection is already queued: collect it first");
+        if (async) return fm::failf(&h->err, FM_ESTATE, "a detection is already queued: collect it first");
         if (int rc = detect_finish(h)) return rc;  // (queued and never collected)
     }
     if ((!frames && !list) || n < 1 || H < 1 || W < 1 || roi_w < 1)
-        return hfail(h, FM_EINVAL, "bad arguments (n >= 1, frame and ROI sizes >= 1)");
-    const int rw = roi_w, rh = (int)(H * ((double)roi_w / (double)W));  // imutils.resize(raw, width=roi_w)
-    if (roi_h_out) *roi_h_out = rh;
-    if (rh < 1) return hfail(h, FM_EINVAL, "ROI height 0 for a %dx%d frame", W, H);
-    const double sx = 1. / ((double)rw / W), sy = 1. / ((double)rh / H);
-    const bool identity = rw == W && rh == H;
-    if (!identity && !(sx >= 1 && sy >= 1))
-        return hfail(h, FM_ENOTSUP, "frame width %d < ROI width %d: INTER_AREA upscaling is not supported", W, rw);
-    HH(h, hipSetDevice(h->device));
+        return fm::failf(&h->err, FM_EINVAL, "bad arguments (n >= 1, frame and ROI sizes >= 1)");
+    FM_HIP_TRY(&h->err, hipSetDevice(h->device));
     const double t0 = h->times ? hnow() : 0.;
-    const size_t fb = (size_t)H * W * 3;
-    const uint8_t* src = frames;
-    int rc;
-    // a frame list: the resize reads each frame where it lies (k_resize_area_nt's address table) when
-    // it can; otherwise the frames are gathered on the detector's stream first
-    const uint8_t* const* dlist = nullptr;
-    if (list) {
-        // from page-locked memory: a pageable source made this small copy cost ~0.5 ms of host time per
-        // call beside a busy pixel stream (FM_HAAR_TIMES); the previous call's copy is done (each call
-        // ends with a stream synchronize)
-        if ((size_t)n > h->cap_fptr) {
-            if (h->h_fptr) HH(h, hipHostFree((void*)h->h_fptr));
-            h->h_fptr = nullptr;
-            size_t cap = h->cap_fptr;
-            if ((rc = grow(h, &h->d_fptr, cap, (size_t)n))) return rc;
-            HH(h, hipHostMalloc((void**)&h->h_fptr, (size_t)n * sizeof(const uint8_t*), 0));
-            h->cap_fptr = cap;
-        }
-        std::memcpy((void*)h->h_fptr, list, (size_t)n * sizeof(const uint8_t*));
-        HH(h, hipMemcpyAsync(h->d_fptr, h->h_fptr, (size_t)n * sizeof(const uint8_t*), hipMemcpyHostToDevice, h->stream));
-        dlist = h->d_fptr;
-    }
-    auto gather = [&]() -> int {
-        int r = grow(h, &h->d_raw, h->cap_raw, n * fb);
-        if (r) return r;
-        for (int i = 0; i < n; i++)
-            HH(h, hipMemcpyAsync(h->d_raw + (size_t)i * fb, list[i], fb, hipMemcpyDeviceToDevice, h->stream));
-        src = h->d_raw;
-        dlist = nullptr;
-        return FM_OK;
-    };
-    if (!list && !on_device) {
-        if ((rc = grow(h, &h->d_raw, h->cap_raw, n * fb))) return rc;
-        HH(h, hipMemcpyAsync(h->d_raw, frames, n * fb, hipMemcpyHostToDevice, h->stream));
-        src = h->d_raw;
-    }
-    const uint8_t* roi = src;
-    if (!identity) {
-        if ((rc = grow(h, &h->d_roi, h->cap_roi, (size_t)n * rh * rw * 3))) return rc;
-        const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
-        if (std::fabs(sx - isx) < 2.220446049250313e-16 && std::fabs(sy - isy) < 2.220446049250313e-16) {
-            if (dlist && (rc = gather())) return rc;
-            HH(h, fm::launch_resize_area_fast(h->stream, src, h->d_roi, n, H, W, rh, rw, isx, isy));
-        } else {
-            if (h->area_key[0] != W || h->area_key[1] != H || h->area_key[2] != rw || h->area_key[3] != rh) {
-                if (!fm::build_area_axis(W, rw, sx, h->ax) || !fm::build_area_axis(H, rh, sy, h->ay))
-                    return hfail(h, FM_ENOTSUP, "INTER_AREA table with non-consecutive taps");
-                HH(h, hipStreamSynchronize(h->stream));
-                for (void* p : {(void*)h->d_axo, (void*)h->d_axc, (void*)h->d_ayo, (void*)h->d_ayc, (void*)h->d_axw,
-                                (void*)h->d_ayw})
-                    if (p) HH(h, hipFree(p));
-                HH(h, hipMalloc((void**)&h->d_axo, h->ax.ofs.size() * 4));
-                HH(h, hipMalloc((void**)&h->d_axc, h->ax.cnt.size() * 4));
-                HH(h, hipMalloc((void**)&h->d_axw, h->ax.wt.size() * 4));
-                HH(h, hipMalloc((void**)&h->d_ayo, h->ay.ofs.size() * 4));
-                HH(h, hipMalloc((void**)&h->d_ayc, h->ay.cnt.size() * 4));
-                HH(h, hipMalloc((void**)&h->d_ayw, h->ay.wt.size() * 4));
-                HH(h, hipMemcpy(h->d_axo, h->ax.ofs.data(), h->ax.ofs.size() * 4, hipMemcpyHostToDevice));
-                HH(h, hipMemcpy(h->d_axc, h->ax.cnt.data(), h->ax.cnt.size() * 4, hipMemcpyHostToDevice));
-                HH(h, hipMemcpy(h->d_axw, h->ax.wt.data(), h->ax.wt.size() * 4, hipMemcpyHostToDevice));
-                HH(h, hipMemcpy(h->d_ayo, h->ay.ofs.data(), h->ay.ofs.size() * 4, hipMemcpyHostToDevice));
-                HH(h, hipMemcpy(h->d_ayc, h->ay.cnt.data(), h->ay.cnt.size() * 4, hipMemcpyHostToDevice));
-                HH(h, hipMemcpy(h->d_ayw, h->ay.wt.data(), h->ay.wt.size() * 4, hipMemcpyHostToDevice));
-                h->area_key[0] = W;
-                h->area_key[1] = H;
-                h->area_key[2] = rw;
-                h->area_key[3] = rh;
-            }
-            const bool direct = dlist && ((h->ax.max_taps + 1) & ~1) <= 32 && fb < (1u << 31);
-            if (dlist && !direct && (rc = gather())) return rc;
-            HH(h, fm::launch_resize_area(h->stream, src, h->d_roi, n, H, W, rh, rw, h->d_axo, h->d_axc, h->d_axw,
-                                         h->ax.max_taps, h->d_ayo, h->d_ayc, h->d_ayw, h->ay.max_taps, dlist));
-        }
-        roi = h->d_roi;
-    } else if (dlist && (rc = gather())) {
-        return rc;
-    } else if (list) {
-        roi = src;
-    }
+    const uint8_t* roi = nullptr;
+    int rh = 0;
+    const int rc = h->roi.run(&h->err, h->stream, frames, list, n, H, W, on_device != 0, roi_w, &roi, &rh);
+    if (roi_h_out) *roi_h_out = rh;
+    if (rc) return rc;
     if (h->times) h->tph[0] += hnow() - t0;
-    if (async) return detect_enqueue(h, roi, n, rh, rw, 3, 1, scale_factor, min_neighbors, 0, 0, 0, 0);
-    return fm_haar_detect(h, roi, n, rh, rw, 3, 1, scale_factor, min_neighbors, 0, 0, 0, 0, rects, cap, counts);
+    if (async) return detect_enqueue(h, roi, n, rh, roi_w, 3, 1, scale_factor, min_neighbors, 0, 0, 0, 0);
+    return fm_haar_detect(h, roi, n, rh, roi_w, 3, 1, scale_factor, min_neighbors, 0, 0, 0, 0, rects, cap, counts);
 }
 
 extern "C" {
@@ -1369,27 +1228,27 @@ int fm_haar_detect_frames(fm_haar* h, const uint8_t* frames, int n, int H, int W
 int fm_haar_detect_frame_list(fm_haar* h, const uint8_t* const* frames, int n, int H, int W, int roi_w,
                               double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts,
                               int* roi_h_out) {
-    if (!frames) return h ? hfail(h, FM_EINVAL, "null frame list") : FM_EINVAL;
+    if (!frames) return h ? fm::failf(&h->err, FM_EINVAL, "null frame list") : FM_EINVAL;
     for (int i = 0; i < n; i++)
-        if (!frames[i]) return hfail(h, FM_EINVAL, "frame %d: null address", i);
+        if (!frames[i]) return fm::failf(&h->err, FM_EINVAL, "frame %d: null address", i);
     return detect_frames_impl(h, nullptr, frames, n, H, W, 1, roi_w, scale_factor, min_neighbors, rects, cap, counts,
                               roi_h_out);
 }
 
 int fm_haar_detect_frame_list_async(fm_haar* h, const uint8_t* const* frames, int n, int H, int W, int roi_w,
                                     double scale_factor, int min_neighbors, int* roi_h_out) {
-    if (!frames) return h ? hfail(h, FM_EINVAL, "null frame list") : FM_EINVAL;
+    if (!frames) return h ? fm::failf(&h->err, FM_EINVAL, "null frame list") : FM_EINVAL;
     for (int i = 0; i < n; i++)
-        if (!frames[i]) return hfail(h, FM_EINVAL, "frame %d: null address", i);
+        if (!frames[i]) return fm::failf(&h->err, FM_EINVAL, "frame %d: null address", i);
     return detect_frames_impl(h, nullptr, frames, n, H, W, 1, roi_w, scale_factor, min_neighbors, nullptr, 0, nullptr,
                               roi_h_out, true);
 }
 
 int fm_haar_collect(fm_haar* h, int32_t* rects, int cap, int32_t* counts, int n) {
     if (!h) return FM_EINVAL;
-    if (cap < 0 || !counts || (cap > 0 && !rects)) return hfail(h, FM_EINVAL, "bad arguments (counts[n], rects[n][cap])");
+    if (cap < 0 || !counts || (cap > 0 && !rects)) return fm::failf(&h->err, FM_EINVAL, "bad arguments (counts[n], rects[n][cap])");
     if (int rc = detect_finish(h)) return rc;
-    if (n != (int)h->out.size()) return hfail(h, FM_ESTATE, "%d images asked for, the last detection had %zu", n, h->out.size());
+    if (n != (int)h->out.size()) return fm::failf(&h->err, FM_ESTATE, "%d images asked for, the last detection had %zu", n, h->out.size());
     detect_copy(h, rects, cap, counts);
     return FM_OK;
 }

@@ -25,7 +25,6 @@
 // would take as RGB (Adobe transform 0 or ids 'R','G','B' without JFIF) included.  Streams Pillow's
 // default encoder never writes are pinned by tests/test_gpu_jpeg_streams.py.
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -36,6 +35,7 @@
 #include <thread>
 #include <vector>
 
+#include "fm_host.h"
 #include "fm_internal.h"
 
 namespace fm {
@@ -981,80 +981,51 @@ struct fm_mjpeg {
     bool have_geom = false;
     JpegGeom g{};
     int tsel[kMaxComp][2] = {};      // (td, ta) of each component in the scan
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    fm::Stream st;  // (streams before the buffers used on them: the buffers are released first)
+    fm::Event e0, e1;
     // device buffers of one call, two sets used in turn, each with its own stream: a call's Huffman
     // pass (latency-bound, few waves) runs beside the previous call's IDCT and colour kernels
     struct DevSet {
-        hipStream_t st = nullptr;
-        hipEvent_t done = nullptr;         // the call's kernels are finished (the caller's stream waits for it)
-        uint8_t* d_stream = nullptr;
-        size_t stream_cap = 0;
-        Seg* d_segs = nullptr;
-        size_t segs_cap = 0;
-        uint32_t* d_chunk0 = nullptr;      // [nseg + 1] first chunk of each segment
-        size_t chunk0_cap = 0;
-        TileState* d_ts = nullptr;         // look-back records, one per tile of 64 chunks (+ the tile counter)
-        size_t ts_cap = 0;
-        HuffDev* d_tabs = nullptr;         // [n_sets][4]
-        size_t tabs_cap = 0;
-        uint16_t* d_qt = nullptr;          // [max_frames][3][64] natural order
-        int16_t* d_coef = nullptr;         // [max_frames][frame_blocks][64]
-        uint32_t* d_msk = nullptr;         // [max_frames][frame_blocks]: non-zero 16-B pieces of each block
-        uint8_t* d_planes = nullptr;       // [max_frames][frame_plane]
+        fm::Stream st;
+        fm::Event done;                    // the call's kernels are finished (the caller's stream waits for it)
+        fm::DevBuf<uint8_t> d_stream;
+        fm::DevBuf<Seg> d_segs;
+        fm::DevBuf<uint32_t> d_chunk0;     // [nseg + 1] first chunk of each segment
+        fm::DevBuf<TileState> d_ts;        // look-back records, one per tile of 64 chunks (+ the tile counter)
+        fm::DevBuf<HuffDev> d_tabs;        // [n_sets][4]
+        fm::DevBuf<uint16_t> d_qt;         // [max_frames][3][64] natural order
+        fm::DevBuf<int16_t> d_coef;        // [max_frames][frame_blocks][64]
+        fm::DevBuf<uint32_t> d_msk;        // [max_frames][frame_blocks]: non-zero 16-B pieces of each block
+        fm::DevBuf<uint8_t> d_planes;      // [max_frames][frame_plane]
     } ds[2];
     int CB = 512, OV = 512;            // chunk and speculation lengths in bits (fm_mjpeg_tune)
-    uint64_t* d_stamps = nullptr;      // dev build, FM_JPEG_STAMPS: per-tile phase stamps of k_jpeg_huff
-    size_t stamps_cap = 0;
+    fm::DevBuf<uint64_t> d_stamps;     // dev build, FM_JPEG_STAMPS: per-tile phase stamps of k_jpeg_huff
     size_t stamps_n = 0;
-    uint8_t* d_out = nullptr;          // device BGR when the caller wants host output
+    fm::DevBuf<uint8_t> d_out;         // device BGR when the caller wants host output
     // pinned host staging, two sets used in turn: a call refills the set whose uploads (two calls
     // back) are done, so host parsing overlaps the previous call's transfers and kernels
     struct HostSet {
-        uint8_t* stream = nullptr;
-        size_t stream_cap = 0;
-        Seg* segs = nullptr;
-        size_t segs_cap = 0;
-        uint32_t* chunk0 = nullptr;
-        size_t chunk0_cap = 0;
-        HuffDev* tabs = nullptr;
-        size_t tabs_cap = 0;
-        uint16_t* qt = nullptr;
-        hipEvent_t done = nullptr;  // the set's uploads are finished
+        fm::PinBuf<uint8_t> stream;
+        fm::PinBuf<Seg> segs;
+        fm::PinBuf<uint32_t> chunk0;
+        fm::PinBuf<HuffDev> tabs;
+        fm::PinBuf<uint16_t> qt;
+        fm::Event done;  // the set's uploads are finished
         bool used = false;
     } hs[2];
     int cur = 0;  // the next call's host and device sets
     float last_ms = 0.f;
     bool timing = false;
+
+    ~fm_mjpeg() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (auto& S : ds)
+            if (S.st) (void)hipStreamSynchronize(S.st);
+        delete pool;
+    }
 };
 
 namespace {
-
-int jfail(fm_mjpeg* d, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (d) d->err = buf;
-    return code;
-}
-
-#define JHIP(d, expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return jfail(d, FM_EHIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-
-int pfail(std::string& err, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
 
 struct HuffHost {
     uint8_t bits[17] = {};
@@ -1114,21 +1085,21 @@ void add_std_huff(ParsedJpeg& J) {
 }
 
 int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg& J) {
-    if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return pfail(err, FM_EINVAL, "frame %d: no SOI", idx);
+    if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return fm::failf(&err, FM_EINVAL, "frame %d: no SOI", idx);
     size_t i = 2;
     bool sof = false;
     bool jfif = false, adobe = false;  // jdmarker.c get_interesting_appn: APP0 'JFIF', APP14 'Adobe'
     int adobe_transform = 0;
     while (i + 4 <= n) {
-        if (p[i] != 0xFF) return pfail(err, FM_EINVAL, "frame %d: marker expected at byte %zu", idx, i);
+        if (p[i] != 0xFF) return fm::failf(&err, FM_EINVAL, "frame %d: marker expected at byte %zu", idx, i);
         while (i < n && p[i] == 0xFF) i++;
         if (i >= n) break;
         const int m = p[i++];
         if (m == 0xD9) break;
         if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-        if (i + 2 > n) return pfail(err, FM_EINVAL, "frame %d: truncated marker", idx);
+        if (i + 2 > n) return fm::failf(&err, FM_EINVAL, "frame %d: truncated marker", idx);
         const size_t len = ((size_t)p[i] << 8) | p[i + 1];
-        if (len < 2 || i + len > n) return pfail(err, FM_EINVAL, "frame %d: bad segment length", idx);
+        if (len < 2 || i + len > n) return fm::failf(&err, FM_EINVAL, "frame %d: bad segment length", idx);
         const uint8_t* s = p + i + 2;
         const size_t sl = len - 2;
         if (m == 0xDB) {
@@ -1136,7 +1107,7 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
             while (q < sl) {
                 const int pq = s[q] >> 4, tq = s[q] & 15;
                 q++;
-                if (tq > 3 || q + (pq ? 128 : 64) > sl) return pfail(err, FM_EINVAL, "frame %d: bad DQT", idx);
+                if (tq > 3 || q + (pq ? 128 : 64) > sl) return fm::failf(&err, FM_EINVAL, "frame %d: bad DQT", idx);
                 for (int k = 0; k < 64; k++) J.qt[tq][kZig[k]] = pq ? (uint16_t)((s[q + 2 * k] << 8) | s[q + 2 * k + 1]) : s[q + k];
                 J.qt_present[tq] = true;
                 q += pq ? 128 : 64;
@@ -1145,26 +1116,26 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
             size_t q = 0;
             while (q < sl) {
                 const int tc = s[q] >> 4, th = s[q] & 15;
-                if (tc > 1 || th > 3 || q + 17 > sl) return pfail(err, FM_EINVAL, "frame %d: bad DHT", idx);
+                if (tc > 1 || th > 3 || q + 17 > sl) return fm::failf(&err, FM_EINVAL, "frame %d: bad DHT", idx);
                 HuffHost& t = J.ht[tc][th];
                 int cnt = 0;
                 for (int l = 1; l <= 16; l++) {
                     t.bits[l] = s[q + l];
                     cnt += s[q + l];
                 }
-                if (cnt > 256 || q + 17 + cnt > sl) return pfail(err, FM_EINVAL, "frame %d: bad DHT counts", idx);
+                if (cnt > 256 || q + 17 + cnt > sl) return fm::failf(&err, FM_EINVAL, "frame %d: bad DHT counts", idx);
                 memcpy(t.vals, s + q + 17, cnt);
                 t.n = cnt;
                 t.present = true;
                 q += 17 + cnt;
             }
         } else if (m == 0xC0 || m == 0xC1) {
-            if (sl < 6 || s[0] != 8) return pfail(err, FM_ENOTSUP, "frame %d: only 8-bit samples", idx);
+            if (sl < 6 || s[0] != 8) return fm::failf(&err, FM_ENOTSUP, "frame %d: only 8-bit samples", idx);
             J.H = (s[1] << 8) | s[2];
             J.W = (s[3] << 8) | s[4];
             J.nc = s[5];
             if ((J.nc != 1 && J.nc != 3) || sl < 6 + 3 * (size_t)J.nc)
-                return pfail(err, FM_ENOTSUP, "frame %d: %d components (1 or 3 supported)", idx, J.nc);
+                return fm::failf(&err, FM_ENOTSUP, "frame %d: %d components (1 or 3 supported)", idx, J.nc);
             for (int c = 0; c < J.nc; c++) {
                 J.cid[c] = s[6 + 3 * c];
                 J.ch[c] = s[7 + 3 * c] >> 4;
@@ -1173,7 +1144,7 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
             }
             sof = true;
         } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-            return pfail(err, FM_ENOTSUP, "frame %d: SOF%d (progressive / lossless / arithmetic) not supported", idx,
+            return fm::failf(&err, FM_ENOTSUP, "frame %d: SOF%d (progressive / lossless / arithmetic) not supported", idx,
                          m - 0xC0);
         } else if (m == 0xE0) {
             if (sl >= 14 && !memcmp(s, "JFIF\0", 5)) jfif = true;
@@ -1183,27 +1154,27 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
                 adobe_transform = s[11];
             }
         } else if (m == 0xDD) {
-            if (sl < 2) return pfail(err, FM_EINVAL, "frame %d: bad DRI", idx);
+            if (sl < 2) return fm::failf(&err, FM_EINVAL, "frame %d: bad DRI", idx);
             J.dri = (s[0] << 8) | s[1];
         } else if (m == 0xDA) {
-            if (!sof) return pfail(err, FM_EINVAL, "frame %d: SOS before SOF", idx);
+            if (!sof) return fm::failf(&err, FM_EINVAL, "frame %d: SOS before SOF", idx);
             J.ns = s[0];
             if (J.ns != J.nc || sl < 1 + 2 * (size_t)J.ns + 3)
-                return pfail(err, FM_ENOTSUP, "frame %d: non-interleaved multi-scan JPEG not supported", idx);
+                return fm::failf(&err, FM_ENOTSUP, "frame %d: non-interleaved multi-scan JPEG not supported", idx);
             for (int k = 0; k < J.ns; k++) {
                 J.sid[k] = s[1 + 2 * k];
                 J.std_[k] = s[2 + 2 * k] >> 4;
                 J.sta[k] = s[2 + 2 * k] & 15;
                 // T.81 B.2.3: the scan's components in the frame's order (libjpeg refuses any other)
                 if (J.sid[k] != J.cid[k])
-                    return pfail(err, FM_EINVAL, "frame %d: scan component %d is not the frame's component %d", idx, k, k);
+                    return fm::failf(&err, FM_EINVAL, "frame %d: scan component %d is not the frame's component %d", idx, k, k);
             }
             // libjpeg's colour space of three components (jdapimin.c default_decompress_parms): JFIF says
             // YCbCr; else Adobe's transform byte (0: RGB); else the ids 'R','G','B' say RGB.  The planes
             // of an RGB stream are not converted: left to the host decoder.
             if (J.nc == 3 && !jfif &&
                 (adobe ? adobe_transform == 0 : (J.cid[0] == 'R' && J.cid[1] == 'G' && J.cid[2] == 'B')))
-                return pfail(err, FM_ENOTSUP, "frame %d: RGB-coded JPEG (no YCbCr transform) not supported", idx);
+                return fm::failf(&err, FM_ENOTSUP, "frame %d: RGB-coded JPEG (no YCbCr transform) not supported", idx);
             J.scan_begin = i + len;
             // the scan ends at the first marker that is neither stuffing (FF 00) nor RSTn; any run of
             // 0xFF fill bytes may precede a marker (T.81 B.1.1.2) and is skipped, as libjpeg's
@@ -1232,7 +1203,7 @@ int parse_jpeg(std::string& err, int idx, const uint8_t* p, size_t n, ParsedJpeg
         }
         i += len;
     }
-    return pfail(err, FM_EINVAL, "frame %d: no scan", idx);
+    return fm::failf(&err, FM_EINVAL, "frame %d: no scan", idx);
 }
 
 void build_table(const HuffHost& h, HuffDev& t, bool dc) {
@@ -1265,32 +1236,17 @@ void build_table(const HuffHost& h, HuffDev& t, bool dc) {
     memcpy(t.vals, h.vals, sizeof t.vals);
 }
 
-template <typename T>
-int grow_dev(fm_mjpeg* d, T** p, size_t& cap, size_t need) {
-    if (need <= cap) return FM_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    const size_t nc = std::max(need, cap * 3 / 2 + 1);
-    JHIP(d, hipMalloc((void**)p, nc * sizeof(T)));
-    cap = nc;
-    return FM_OK;
-}
-
-template <typename T>
-int grow_host(fm_mjpeg* d, T** p, size_t& cap, size_t need) {
-    if (need <= cap) return FM_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    const size_t nc = std::max(need, cap * 3 / 2 + 1);
-    JHIP(d, hipHostMalloc((void**)p, nc * sizeof(T), hipHostMallocDefault));
-    cap = nc;
+// Grow-only staging of a call, at least half as much again when it grows (contents are not kept).
+template <class B>
+int grow(fm_mjpeg* d, B& b, size_t need) {
+    FM_HIP_TRY(&d->err, b.reserve(need, std::max(need, b.capacity() * 3 / 2 + 1)));
     return FM_OK;
 }
 
 // frame geometry from the first frame: component grids, planes, buffers
 int setup_geometry(fm_mjpeg* d, const ParsedJpeg& J) {
     if (J.W != d->W || J.H != d->H)
-        return jfail(d, FM_EINVAL, "JPEG is %dx%d, the decoder was created for %dx%d", J.W, J.H, d->W, d->H);
+        return fm::failf(&d->err, FM_EINVAL, "JPEG is %dx%d, the decoder was created for %dx%d", J.W, J.H, d->W, d->H);
     JpegGeom& g = d->g;
     g = JpegGeom{};
     g.W = J.W;
@@ -1306,10 +1262,10 @@ int setup_geometry(fm_mjpeg* d, const ParsedJpeg& J) {
         const bool ok = J.ch[1] == 1 && J.cv[1] == 1 && J.ch[2] == 1 && J.cv[2] == 1 &&
                         ((J.ch[0] == 1 && J.cv[0] == 1) || (J.ch[0] == 2 && J.cv[0] == 1) || (J.ch[0] == 2 && J.cv[0] == 2));
         if (!ok)
-            return jfail(d, FM_ENOTSUP, "sampling Y %dx%d Cb %dx%d Cr %dx%d not supported", J.ch[0], J.cv[0], J.ch[1],
+            return fm::failf(&d->err, FM_ENOTSUP, "sampling Y %dx%d Cb %dx%d Cr %dx%d not supported", J.ch[0], J.cv[0], J.ch[1],
                          J.cv[1], J.ch[2], J.cv[2]);
     } else if (J.ch[0] < 1 || J.cv[0] < 1 || J.ch[0] > 4 || J.cv[0] > 4) {
-        return jfail(d, FM_EINVAL, "bad sampling factors");
+        return fm::failf(&d->err, FM_EINVAL, "bad sampling factors");
     }
     g.interleaved = J.nc > 1;
     if (g.interleaved) {
@@ -1348,16 +1304,16 @@ int setup_geometry(fm_mjpeg* d, const ParsedJpeg& J) {
     }
     const size_t nb = (size_t)d->max_frames * blocks * 64;
     for (auto& S : d->ds) {
-        JHIP(d, hipMalloc((void**)&S.d_coef, nb * sizeof(int16_t)));
-        JHIP(d, hipMemsetAsync(S.d_coef, 0, nb * sizeof(int16_t), d->st));
-        JHIP(d, hipMalloc((void**)&S.d_msk, (size_t)d->max_frames * blocks * sizeof(uint32_t)));
-        JHIP(d, hipMemsetAsync(S.d_msk, 0, (size_t)d->max_frames * blocks * sizeof(uint32_t), d->st));
-        JHIP(d, hipMalloc((void**)&S.d_planes, (size_t)d->max_frames * g.frame_plane));
-        JHIP(d, hipMalloc((void**)&S.d_qt, (size_t)d->max_frames * kMaxComp * 64 * sizeof(uint16_t)));
+        FM_HIP_TRY(&d->err, S.d_coef.reserve(nb));
+        FM_HIP_TRY(&d->err, hipMemsetAsync(S.d_coef, 0, nb * sizeof(int16_t), d->st));
+        FM_HIP_TRY(&d->err, S.d_msk.reserve((size_t)d->max_frames * blocks));
+        FM_HIP_TRY(&d->err, hipMemsetAsync(S.d_msk, 0, (size_t)d->max_frames * blocks * sizeof(uint32_t), d->st));
+        FM_HIP_TRY(&d->err, S.d_planes.reserve((size_t)d->max_frames * g.frame_plane));
+        FM_HIP_TRY(&d->err, S.d_qt.reserve((size_t)d->max_frames * kMaxComp * 64));
     }
     for (auto& H : d->hs)
-        JHIP(d, hipHostMalloc((void**)&H.qt, (size_t)d->max_frames * kMaxComp * 64 * sizeof(uint16_t), hipHostMallocDefault));
-    JHIP(d, hipStreamSynchronize(d->st));
+        FM_HIP_TRY(&d->err, H.qt.reserve((size_t)d->max_frames * kMaxComp * 64));
+    FM_HIP_TRY(&d->err, hipStreamSynchronize(d->st));
     d->have_geom = true;
     return FM_OK;
 }
@@ -1371,59 +1327,35 @@ int fm_mjpeg_create(int device, int width, int height, int max_frames, fm_mjpeg*
     fm_mjpeg* d = new fm_mjpeg();
     *out = d;
     if (width < 1 || height < 1 || max_frames < 1)
-        return jfail(d, FM_EINVAL, "bad geometry %dx%d, max_frames %d", width, height, max_frames);
+        return fm::failf(&d->err, FM_EINVAL, "bad geometry %dx%d, max_frames %d", width, height, max_frames);
     d->device = device;
     d->W = width;
     d->H = height;
     d->max_frames = max_frames;
-    JHIP(d, hipSetDevice(device));
-    JHIP(d, hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
-    JHIP(d, hipEventCreate(&d->e0));
-    JHIP(d, hipEventCreate(&d->e1));
+    FM_HIP_TRY(&d->err, hipSetDevice(device));
+    FM_HIP_TRY(&d->err, hipStreamCreateWithFlags(d->st.put(), hipStreamNonBlocking));
+    FM_HIP_TRY(&d->err, hipEventCreate(d->e0.put()));
+    FM_HIP_TRY(&d->err, hipEventCreate(d->e1.put()));
     for (auto& H : d->hs) {
-        JHIP(d, hipHostMalloc((void**)&H.tabs, 4 * sizeof(HuffDev), hipHostMallocDefault));
-        H.tabs_cap = 4;
-        JHIP(d, hipEventCreateWithFlags(&H.done, hipEventDisableTiming));
+        FM_HIP_TRY(&d->err, H.tabs.reserve(4));
+        FM_HIP_TRY(&d->err, hipEventCreateWithFlags(H.done.put(), hipEventDisableTiming));
     }
     for (auto& S : d->ds) {
-        JHIP(d, hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-        JHIP(d, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+        FM_HIP_TRY(&d->err, hipStreamCreateWithFlags(S.st.put(), hipStreamNonBlocking));
+        FM_HIP_TRY(&d->err, hipEventCreateWithFlags(S.done.put(), hipEventDisableTiming));
     }
     d->pool = new FramePool(std::max(0, std::min(7, (int)std::thread::hardware_concurrency() - 1)));
     return FM_OK;
 }
 
-void fm_mjpeg_destroy(fm_mjpeg* d) {
-    if (!d) return;
-    if (d->st) (void)hipStreamSynchronize(d->st);
-    for (auto& S : d->ds) {
-        if (S.st) (void)hipStreamSynchronize(S.st);
-        for (void* p : {(void*)S.d_stream, (void*)S.d_segs, (void*)S.d_tabs, (void*)S.d_qt, (void*)S.d_coef, (void*)S.d_msk,
-                        (void*)S.d_planes, (void*)S.d_chunk0, (void*)S.d_ts})
-            if (p) (void)hipFree(p);
-        if (S.done) (void)hipEventDestroy(S.done);
-        if (S.st) (void)hipStreamDestroy(S.st);
-    }
-    for (void* p : {(void*)d->d_out, (void*)d->d_stamps})
-        if (p) (void)hipFree(p);
-    for (auto& H : d->hs) {
-        for (void* p : {(void*)H.stream, (void*)H.segs, (void*)H.tabs, (void*)H.qt, (void*)H.chunk0})
-            if (p) (void)hipHostFree(p);
-        if (H.done) (void)hipEventDestroy(H.done);
-    }
-    delete d->pool;
-    if (d->e0) (void)hipEventDestroy(d->e0);
-    if (d->e1) (void)hipEventDestroy(d->e1);
-    if (d->st) (void)hipStreamDestroy(d->st);
-    delete d;
-}
+void fm_mjpeg_destroy(fm_mjpeg* d) { delete d; }
 
 const char* fm_mjpeg_last_error(const fm_mjpeg* d) { return d ? d->err.c_str() : "null decoder"; }
 
 int fm_mjpeg_tune(fm_mjpeg* d, int chunk_bits, int spec_bits) {
     if (!d) return FM_EINVAL;
     if (chunk_bits < 64 || chunk_bits > (1 << 24) || spec_bits < 0 || spec_bits > (1 << 24))
-        return jfail(d, FM_EINVAL, "chunk_bits %d / spec_bits %d outside [64, 2^24] / [0, 2^24]", chunk_bits, spec_bits);
+        return fm::failf(&d->err, FM_EINVAL, "chunk_bits %d / spec_bits %d outside [64, 2^24] / [0, 2^24]", chunk_bits, spec_bits);
     d->CB = chunk_bits;
     d->OV = spec_bits;
     return FM_OK;
@@ -1447,9 +1379,9 @@ int fm_mjpeg_geometry(const fm_mjpeg* d, int* width, int* height, int* device, i
 int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* sizes, int n, uint8_t* out, hipStream_t st) {
     if (!d) return FM_EINVAL;
     if (!jpegs || !sizes || !out || n < 1 || n > d->max_frames)
-        return jfail(d, FM_EINVAL, "n %d outside [1, max_frames=%d] or null buffers", n, d->max_frames);
-    if (!d->pool) return jfail(d, FM_ESTATE, "decoder not initialised (fm_mjpeg_create failed)");
-    JHIP(d, hipSetDevice(d->device));
+        return fm::failf(&d->err, FM_EINVAL, "n %d outside [1, max_frames=%d] or null buffers", n, d->max_frames);
+    if (!d->pool) return fm::failf(&d->err, FM_ESTATE, "decoder not initialised (fm_mjpeg_create failed)");
+    FM_HIP_TRY(&d->err, hipSetDevice(d->device));
     // The call runs on its device set's stream (the set of the call before the previous one: stream
     // order reuses its buffers) and the caller's stream waits for it at the end; work queued on the
     // caller's stream before the call is not waited for (the output buffer must be free already).
@@ -1458,16 +1390,16 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
     auto& H = d->hs[d->cur];
     auto& S = d->ds[d->cur];
     st = S.st;
-    if (H.used) JHIP(d, hipEventSynchronize(H.done));
+    if (H.used) FM_HIP_TRY(&d->err, hipEventSynchronize(H.done));
     std::vector<ParsedJpeg> P(n);
     for (int i = 0; i < n; i++)
-        if (!jpegs[i]) return jfail(d, FM_EINVAL, "frame %d: null", i);
+        if (!jpegs[i]) return fm::failf(&d->err, FM_EINVAL, "frame %d: null", i);
     {   // marker parsing, frames in parallel (errors reported for the first failing frame)
         std::vector<int> prc(n, FM_OK);
         std::vector<std::string> perr(n);
         d->pool->run(n, [&](int i) { prc[i] = parse_jpeg(perr[i], i, jpegs[i], sizes[i], P[i]); });
         for (int i = 0; i < n; i++)
-            if (prc[i]) return jfail(d, prc[i], "%s", perr[i].c_str());
+            if (prc[i]) return fm::failf(&d->err, prc[i], "%s", perr[i].c_str());
     }
     if (!d->have_geom)
         if (int rc = setup_geometry(d, P[0])) return rc;
@@ -1483,26 +1415,26 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
     std::vector<TabSet> fsets(n);
     for (int i = 0; i < n; i++) {
         const ParsedJpeg& J = P[i];
-        if (J.W != g.W || J.H != g.H) return jfail(d, FM_EINVAL, "frame %d: geometry differs", i);
+        if (J.W != g.W || J.H != g.H) return fm::failf(&d->err, FM_EINVAL, "frame %d: geometry differs", i);
         // a later frame coded with other components or sampling than the decoder's layout: FM_ENOTSUP, the
         // status on which the decode-ahead feeder decodes the batch on the host (a stream may switch)
-        if (J.nc != g.nc) return jfail(d, FM_ENOTSUP, "frame %d: %d components, the decoder's layout has %d", i, J.nc, g.nc);
+        if (J.nc != g.nc) return fm::failf(&d->err, FM_ENOTSUP, "frame %d: %d components, the decoder's layout has %d", i, J.nc, g.nc);
         TabSet& ts_ = fsets[i];
         int ids[2][2] = {{-1, -1}, {-1, -1}};
         for (int c = 0; c < g.nc; c++) {
             if (J.ch[c] != g.comp[c].h || J.cv[c] != g.comp[c].v)
-                return jfail(d, FM_ENOTSUP, "frame %d: sampling differs from the decoder's layout", i);
-            if (!J.qt_present[J.ctq[c]]) return jfail(d, FM_EINVAL, "frame %d: missing DQT %d", i, J.ctq[c]);
+                return fm::failf(&d->err, FM_ENOTSUP, "frame %d: sampling differs from the decoder's layout", i);
+            if (!J.qt_present[J.ctq[c]]) return fm::failf(&d->err, FM_EINVAL, "frame %d: missing DQT %d", i, J.ctq[c]);
             int k = 0;
             while (k < J.ns && J.sid[k] != J.cid[c]) k++;
-            if (k == J.ns) return jfail(d, FM_EINVAL, "frame %d: component %d not in the scan", i, J.cid[c]);
+            if (k == J.ns) return fm::failf(&d->err, FM_EINVAL, "frame %d: component %d not in the scan", i, J.cid[c]);
             for (int t = 0; t < 2; t++) {
                 const int id = (t ? J.sta[k] : J.std_[k]) & 3;
-                if (!J.ht[t][id].present) return jfail(d, FM_EINVAL, "frame %d: missing DHT", i);
+                if (!J.ht[t][id].present) return fm::failf(&d->err, FM_EINVAL, "frame %d: missing DHT", i);
                 int sl = ids[t][0] == id ? 0 : ids[t][1] == id ? 1 : -1;
                 if (sl < 0) {
                     sl = ids[t][0] < 0 ? 0 : ids[t][1] < 0 ? 1 : -1;
-                    if (sl < 0) return jfail(d, FM_ENOTSUP, "frame %d: more than two %s tables in the scan", i, t ? "AC" : "DC");
+                    if (sl < 0) return fm::failf(&d->err, FM_ENOTSUP, "frame %d: more than two %s tables in the scan", i, t ? "AC" : "DC");
                     ids[t][sl] = id;
                 }
                 ts_.slot[c][t] = sl;
@@ -1527,7 +1459,7 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
     for (int i = 0; i < n; i++)
         if (i == 0 || !same_set(fsets[i], fsets[run_first.back()])) run_first.push_back(i);
     const int nruns = (int)run_first.size();
-    if (int rc = grow_host(d, &H.tabs, H.tabs_cap, (size_t)nruns * 4)) return rc;
+    if (int rc = grow(d, H.tabs, (size_t)nruns * 4)) return rc;
     for (int r = 0; r < nruns; r++) {
         const TabSet& ts_ = fsets[run_first[r]];
         for (int t = 0; t < 2; t++)
@@ -1542,7 +1474,7 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
     // size), frames in parallel
     std::vector<size_t> base(n + 1, 0);
     for (int i = 0; i < n; i++) base[i + 1] = base[i] + P[i].scan_end - P[i].scan_begin + kSegPad * (P[i].nrst + 1);
-    if (int rc = grow_host(d, &H.stream, H.stream_cap, base[n] + 16)) return rc;
+    if (int rc = grow(d, H.stream, base[n] + 16)) return rc;
     const long long nmcu = (long long)g.mcux * g.mcuy;
     std::vector<std::vector<Seg>> fsegs(n);
     std::vector<int> frc(n, FM_OK);
@@ -1587,19 +1519,19 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
     std::vector<Seg> segs;
     segs.reserve(n);
     for (int i = 0; i < n; i++) {
-        if (frc[i]) return jfail(d, FM_EINVAL, "frame %d: restart markers do not cover the %lld MCUs", i, nmcu);
+        if (frc[i]) return fm::failf(&d->err, FM_EINVAL, "frame %d: restart markers do not cover the %lld MCUs", i, nmcu);
         segs.insert(segs.end(), fsegs[i].begin(), fsegs[i].end());
     }
     size_t w = base[n];
     memset(H.stream + w, 0, 16);
     w += 16;
-    if (w >= (size_t)UINT32_MAX) return jfail(d, FM_ENOTSUP, "compressed batch too large");
-    if (int rc = grow_host(d, &H.segs, H.segs_cap, segs.size())) return rc;
+    if (w >= (size_t)UINT32_MAX) return fm::failf(&d->err, FM_ENOTSUP, "compressed batch too large");
+    if (int rc = grow(d, H.segs, segs.size())) return rc;
     memcpy(H.segs, segs.data(), segs.size() * sizeof(Seg));
     // chunks of CB bits per segment (at least one), 64 per tile
     // each run's chunks start on a tile boundary (tiles never span runs: no look-back between them)
     const int nseg = (int)segs.size();
-    if (int rc = grow_host(d, &H.chunk0, H.chunk0_cap, (size_t)nseg + 1)) return rc;
+    if (int rc = grow(d, H.chunk0, (size_t)nseg + 1)) return rc;
     std::vector<int> run_seg(nruns + 1, nseg);        // first segment of each run
     std::vector<size_t> run_chunk(nruns + 1), run_end(nruns), run_tile(nruns + 1);
     {
@@ -1622,29 +1554,29 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
     run_chunk[nruns] = nchunks;
     run_tile[nruns] = ntiles;
     H.chunk0[nseg] = (uint32_t)nchunks;
-    if (nchunks >= (size_t)INT32_MAX / 2) return jfail(d, FM_ENOTSUP, "compressed batch too large");
-    if (int rc = grow_dev(d, &S.d_stream, S.stream_cap, w + kStreamSlack)) return rc;  // look-ahead reads
-    if (int rc = grow_dev(d, &S.d_segs, S.segs_cap, segs.size())) return rc;
-    if (int rc = grow_dev(d, &S.d_chunk0, S.chunk0_cap, (size_t)nseg + 1)) return rc;
-    if (int rc = grow_dev(d, &S.d_ts, S.ts_cap, ntiles + nruns)) return rc;  // + one tile counter per run
+    if (nchunks >= (size_t)INT32_MAX / 2) return fm::failf(&d->err, FM_ENOTSUP, "compressed batch too large");
+    if (int rc = grow(d, S.d_stream, w + kStreamSlack)) return rc;  // look-ahead reads
+    if (int rc = grow(d, S.d_segs, segs.size())) return rc;
+    if (int rc = grow(d, S.d_chunk0, (size_t)nseg + 1)) return rc;
+    if (int rc = grow(d, S.d_ts, ntiles + nruns)) return rc;  // + one tile counter per run
 #ifdef FM_DEV_SWITCHES
     if (getenv("FM_JPEG_STAMPS")) {
-        if (int rc = grow_dev(d, &d->d_stamps, d->stamps_cap, ntiles * 6)) return rc;
+        if (int rc = grow(d, d->d_stamps, ntiles * 6)) return rc;
         d->stamps_n = ntiles;
-        JHIP(d, hipMemsetAsync(d->d_stamps, 0, ntiles * 6 * sizeof(uint64_t), st));
+        FM_HIP_TRY(&d->err, hipMemsetAsync(d->d_stamps, 0, ntiles * 6 * sizeof(uint64_t), st));
     }
 #endif
-    if (int rc = grow_dev(d, &S.d_tabs, S.tabs_cap, (size_t)nruns * 4)) return rc;
-    JHIP(d, hipMemcpyAsync(S.d_stream, H.stream, w, hipMemcpyHostToDevice, st));
-    JHIP(d, hipMemcpyAsync(S.d_segs, H.segs, segs.size() * sizeof(Seg), hipMemcpyHostToDevice, st));
-    JHIP(d, hipMemcpyAsync(S.d_chunk0, H.chunk0, ((size_t)nseg + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    JHIP(d, hipMemsetAsync(S.d_ts, 0, (ntiles + nruns) * sizeof(TileState), st));  // flags + the tile counters
-    JHIP(d, hipMemcpyAsync(S.d_tabs, H.tabs, (size_t)nruns * 4 * sizeof(HuffDev), hipMemcpyHostToDevice, st));
-    JHIP(d, hipMemcpyAsync(S.d_qt, H.qt, (size_t)n * kMaxComp * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    JHIP(d, hipEventRecord(H.done, st));
+    if (int rc = grow(d, S.d_tabs, (size_t)nruns * 4)) return rc;
+    FM_HIP_TRY(&d->err, hipMemcpyAsync(S.d_stream, H.stream, w, hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&d->err, hipMemcpyAsync(S.d_segs, H.segs, segs.size() * sizeof(Seg), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&d->err, hipMemcpyAsync(S.d_chunk0, H.chunk0, ((size_t)nseg + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&d->err, hipMemsetAsync(S.d_ts, 0, (ntiles + nruns) * sizeof(TileState), st));  // flags + the tile counters
+    FM_HIP_TRY(&d->err, hipMemcpyAsync(S.d_tabs, H.tabs, (size_t)nruns * 4 * sizeof(HuffDev), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&d->err, hipMemcpyAsync(S.d_qt, H.qt, (size_t)n * kMaxComp * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&d->err, hipEventRecord(H.done, st));
     H.used = true;
     d->cur ^= 1;
-    if (d->timing) JHIP(d, hipEventRecord(d->e0, st));
+    if (d->timing) FM_HIP_TRY(&d->err, hipEventRecord(d->e0, st));
     for (int r = 0; r < nruns; r++) {
         const int nt = (int)(run_tile[r + 1] - run_tile[r]);
         if (nt == 0) continue;
@@ -1666,9 +1598,9 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
                            d->CB, d->OV, S.d_ts + run_tile[r], reinterpret_cast<uint32_t*>(S.d_ts + ntiles + r),
                            S.d_coef, S.d_msk, d->d_stamps ? d->d_stamps + 6 * run_tile[r] : nullptr);
     }
-    JHIP(d, hipGetLastError());
+    FM_HIP_TRY(&d->err, hipGetLastError());
     const long long nb = (long long)n * g.frame_blocks;
-    if (nb >= INT32_MAX / 2) return jfail(d, FM_ENOTSUP, "too many coefficient blocks in one call");
+    if (nb >= INT32_MAX / 2) return fm::failf(&d->err, FM_ENOTSUP, "too many coefficient blocks in one call");
     // colour bands: as many rows as keep the staging within 48 KB of LDS
 #ifndef FM_JP_FUSEY
 #define FM_JP_FUSEY 1
@@ -1696,7 +1628,7 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
         }
         if (lds <= 48 * 1024 || rb == 1) break;
     }
-    if (lds > 64 * 1024) return jfail(d, FM_ENOTSUP, "frame width %d too large for the colour kernel", g.W);
+    if (lds > 64 * 1024) return fm::failf(&d->err, FM_ENOTSUP, "frame width %d too large for the colour kernel", g.W);
     int mode = 0;
     if (g.nc == 3) {
         const int hf = g.hmax / g.comp[1].h, vf = g.vmax / g.comp[1].v;
@@ -1727,10 +1659,10 @@ int fm_mjpeg_enqueue(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* siz
         }
 #undef FM_JP_COLOR
     }
-    JHIP(d, hipGetLastError());
-    if (d->timing) JHIP(d, hipEventRecord(d->e1, st));
-    JHIP(d, hipEventRecord(S.done, st));
-    JHIP(d, hipStreamWaitEvent(cst, S.done, 0));
+    FM_HIP_TRY(&d->err, hipGetLastError());
+    if (d->timing) FM_HIP_TRY(&d->err, hipEventRecord(d->e1, st));
+    FM_HIP_TRY(&d->err, hipEventRecord(S.done, st));
+    FM_HIP_TRY(&d->err, hipStreamWaitEvent(cst, S.done, 0));
     return FM_OK;
 }
 
@@ -1742,17 +1674,17 @@ int fm_mjpeg_decode(fm_mjpeg* d, const uint8_t* const* jpegs, const size_t* size
     uint8_t* dst = out;
     const size_t fb = (size_t)d->W * d->H * 3;
     if (!out_on_device) {
-        if (!d->d_out) JHIP(d, hipMalloc((void**)&d->d_out, (size_t)d->max_frames * fb));
+        FM_HIP_TRY(&d->err, d->d_out.reserve((size_t)d->max_frames * fb));
         dst = d->d_out;
     }
     if (int rc = fm_mjpeg_enqueue(d, jpegs, sizes, n, dst, d->st)) return rc;
-    if (!out_on_device) JHIP(d, hipMemcpyAsync(out, dst, (size_t)n * fb, hipMemcpyDeviceToHost, d->st));
-    JHIP(d, hipStreamSynchronize(d->st));
-    JHIP(d, hipEventElapsedTime(&d->last_ms, d->e0, d->e1));
+    if (!out_on_device) FM_HIP_TRY(&d->err, hipMemcpyAsync(out, dst, (size_t)n * fb, hipMemcpyDeviceToHost, d->st));
+    FM_HIP_TRY(&d->err, hipStreamSynchronize(d->st));
+    FM_HIP_TRY(&d->err, hipEventElapsedTime(&d->last_ms, d->e0, d->e1));
 #ifdef FM_DEV_SWITCHES
     if (const char* path = getenv("FM_JPEG_STAMPS")) {
         std::vector<uint64_t> h(d->stamps_n * 6);
-        JHIP(d, hipMemcpy(h.data(), d->d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
+        FM_HIP_TRY(&d->err, hipMemcpy(h.data(), d->d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
         if (FILE* fp = fopen(path, "wb")) {
             fwrite(h.data(), 8, h.size(), fp);
             fclose(fp);

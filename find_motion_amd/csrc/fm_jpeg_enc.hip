@@ -28,12 +28,12 @@
 // Sizes are known before anything is written: the unstuffed stream's after k_enc_scan, the output's after
 // k_enc_ffcount; the buffers are grown to them (or the call fails) before the kernels that write them run.
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "fm_host.h"
 #include "fm_internal.h"
 
 namespace fm {
@@ -585,80 +585,42 @@ struct fm_mjpeg_enc {
     size_t frame_bytes = 0;
     std::vector<uint8_t> header;
     std::string err;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    fm::Stream st;  // (before the buffers used on it: they are released first)
+    fm::Event e0, e1;
     float last_ms = 0.f;
     int last_n = 0;                       // frames of the last successful call
     // device
-    EncHuff* d_huff = nullptr;
-    const uint8_t** d_list = nullptr;     // [max_frames] frame addresses
-    uint8_t* d_in = nullptr;              // staging for host frames (allocated by the first host call)
-    int16_t* d_coef = nullptr;            // [max_frames][nblk][64]
-    uint32_t* d_bits = nullptr;           // [max_frames][nblk] code lengths, then bit offsets
-    uint32_t* d_fbits = nullptr;          // [max_frames]
-    FrameInfo* d_fi = nullptr;            // [max_frames]
-    TileInfo* d_ti = nullptr;             // [ti_cap]
-    uint32_t* d_tcount = nullptr;         // [ti_cap]
-    uint8_t* d_u = nullptr;               // unstuffed streams
-    uint8_t* d_out = nullptr;             // stuffed scans
-    size_t u_cap = 0, out_cap = 0, ti_cap = 0;
+    fm::DevBuf<EncHuff> d_huff;
+    fm::DevBuf<const uint8_t*> d_list;    // [max_frames] frame addresses
+    fm::DevBuf<uint8_t> d_in;             // staging for host frames (allocated by the first host call)
+    fm::DevBuf<int16_t> d_coef;           // [max_frames][nblk][64]
+    fm::DevBuf<uint32_t> d_bits;          // [max_frames][nblk] code lengths, then bit offsets
+    fm::DevBuf<uint32_t> d_fbits;         // [max_frames]
+    fm::DevBuf<FrameInfo> d_fi;           // [max_frames]
+    fm::DevBuf<TileInfo> d_ti;            // one per tile; grows with d_tcount, h_ti and h_tcount
+    fm::DevBuf<uint32_t> d_tcount;
+    fm::DevBuf<uint8_t> d_u;              // unstuffed streams
+    fm::DevBuf<uint8_t> d_out;            // stuffed scans
     // pinned host
-    const uint8_t** h_list = nullptr;
-    uint32_t* h_fbits = nullptr;
-    FrameInfo* h_fi = nullptr;
-    TileInfo* h_ti = nullptr;
-    uint32_t* h_tcount = nullptr;
+    fm::PinBuf<const uint8_t*> h_list;
+    fm::PinBuf<uint32_t> h_fbits;
+    fm::PinBuf<FrameInfo> h_fi;
+    fm::PinBuf<TileInfo> h_ti;
+    fm::PinBuf<uint32_t> h_tcount;
     std::vector<uint32_t> scan_len;       // stuffed scan bytes per frame of the last call
+
+    ~fm_mjpeg_enc() {
+        if (st) (void)hipStreamSynchronize(st);
+    }
 };
 
 namespace {
 
-int efail(fm_mjpeg_enc* e, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (e) e->err = buf;
-    return code;
-}
-
-#define EHIP(e, expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return efail(e, FM_EHIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-
-// Make a device buffer hold at least `need` bytes (contents are not kept).
-int grow(fm_mjpeg_enc* e, uint8_t** p, size_t* cap, size_t need, const char* what) {
-    if (need <= *cap) return FM_OK;
-    if (*p) EHIP(e, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4;
-    if (hipMalloc((void**)p, want) != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        return efail(e, FM_ENOMEM, "%s: %zu bytes of device memory not available", what, want);
-    }
-    *cap = want;
-    return FM_OK;
-}
-
-int grow_tiles(fm_mjpeg_enc* e, size_t need) {
-    if (need <= e->ti_cap) return FM_OK;
-    if (e->d_ti) EHIP(e, hipFree(e->d_ti));
-    if (e->d_tcount) EHIP(e, hipFree(e->d_tcount));
-    if (e->h_ti) EHIP(e, hipHostFree(e->h_ti));
-    if (e->h_tcount) EHIP(e, hipHostFree(e->h_tcount));
-    e->d_ti = nullptr, e->d_tcount = nullptr, e->h_ti = nullptr, e->h_tcount = nullptr, e->ti_cap = 0;
-    const size_t want = need + need / 4 + 64;
-    EHIP(e, hipMalloc((void**)&e->d_ti, want * sizeof(TileInfo)));
-    EHIP(e, hipMalloc((void**)&e->d_tcount, want * sizeof(uint32_t)));
-    EHIP(e, hipHostMalloc((void**)&e->h_ti, want * sizeof(TileInfo), hipHostMallocDefault));
-    EHIP(e, hipHostMalloc((void**)&e->h_tcount, want * sizeof(uint32_t), hipHostMallocDefault));
-    e->ti_cap = want;
-    return FM_OK;
+// Make a device buffer hold at least `need` bytes, a quarter more when it grows (contents are not kept).
+int grow(fm_mjpeg_enc* e, fm::DevBuf<uint8_t>& b, size_t need, size_t count, const char* what) {
+    if (b.reserve(need, count) == hipSuccess) return FM_OK;
+    (void)hipGetLastError();
+    return fm::failf(&e->err, FM_ENOMEM, "%s: %zu bytes of device memory not available", what, count);
 }
 
 // Encode the n frames whose device addresses are in e->h_list.
@@ -666,18 +628,18 @@ int encode_list(fm_mjpeg_enc* e, int n) {
     const EncGeom& g = e->g;
     hipStream_t st = e->st;
     e->last_n = 0;
-    EHIP(e, hipMemcpyAsync(e->d_list, e->h_list, n * sizeof(uint8_t*), hipMemcpyHostToDevice, st));
-    EHIP(e, hipEventRecord(e->e0, st));
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->d_list, e->h_list, n * sizeof(uint8_t*), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&e->err, hipEventRecord(e->e0, st));
     const long long total = (long long)n * g.nblk;
     const unsigned nbg = (unsigned)((total + kThreads - 1) / kThreads);
     k_enc_dct<<<dim3((g.nmcu + kGroup - 1) / kGroup, n), kThreads, 0, st>>>(e->d_list, g, e->q, e->d_coef);
-    EHIP(e, hipGetLastError());
+    FM_HIP_TRY(&e->err, hipGetLastError());
     k_enc_bits<<<nbg, kThreads, 0, st>>>(e->d_coef, g, e->d_huff, e->d_bits, total);
-    EHIP(e, hipGetLastError());
+    FM_HIP_TRY(&e->err, hipGetLastError());
     k_enc_scan<<<n, kThreads, 0, st>>>(e->d_bits, g, e->d_fbits);
-    EHIP(e, hipGetLastError());
-    EHIP(e, hipMemcpyAsync(e->h_fbits, e->d_fbits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    EHIP(e, hipStreamSynchronize(st));
+    FM_HIP_TRY(&e->err, hipGetLastError());
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->h_fbits, e->d_fbits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(&e->err, hipStreamSynchronize(st));
     // the unstuffed streams' sizes are known: lay them out, one run of whole tiles per frame
     size_t u_total = 0, ntiles = 0;
     for (int f = 0; f < n; f++) {
@@ -690,20 +652,20 @@ int encode_list(fm_mjpeg_enc* e, int n) {
         u_total += t * kTile;
         ntiles += t;
     }
-    if (int rc = grow(e, &e->d_u, &e->u_cap, u_total, "unstuffed stream")) return rc;
-    if (int rc = grow_tiles(e, ntiles)) return rc;
+    if (int rc = grow(e, e->d_u, u_total, u_total + u_total / 4, "unstuffed stream")) return rc;
+    FM_HIP_TRY(&e->err, fm::reserve_all(ntiles, ntiles + ntiles / 4 + 64, e->d_ti, e->d_tcount, e->h_ti, e->h_tcount));
     size_t k = 0;
     for (int f = 0; f < n; f++)
         for (uint32_t t = 0; t < (e->h_fi[f].ubytes + kTile - 1) / kTile; t++) e->h_ti[k++] = TileInfo{(uint32_t)f, t, 0, 0};
-    EHIP(e, hipMemcpyAsync(e->d_fi, e->h_fi, n * sizeof(FrameInfo), hipMemcpyHostToDevice, st));
-    EHIP(e, hipMemcpyAsync(e->d_ti, e->h_ti, ntiles * sizeof(TileInfo), hipMemcpyHostToDevice, st));
-    EHIP(e, hipMemsetAsync(e->d_u, 0, u_total, st));  // k_enc_emit ORs into zeros: cleared for every call
-    k_enc_emit<<<nbg, kThreads, 0, st>>>(e->d_coef, g, e->d_huff, e->d_bits, e->d_fi, (uint32_t*)e->d_u, total);
-    EHIP(e, hipGetLastError());
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->d_fi, e->h_fi, n * sizeof(FrameInfo), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->d_ti, e->h_ti, ntiles * sizeof(TileInfo), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&e->err, hipMemsetAsync(e->d_u, 0, u_total, st));  // k_enc_emit ORs into zeros: cleared for every call
+    k_enc_emit<<<nbg, kThreads, 0, st>>>(e->d_coef, g, e->d_huff, e->d_bits, e->d_fi, (uint32_t*)e->d_u.get(), total);
+    FM_HIP_TRY(&e->err, hipGetLastError());
     k_enc_ffcount<<<(unsigned)ntiles, kThreads, 0, st>>>(e->d_u, g, e->d_bits, e->d_fi, e->d_ti, e->d_tcount);
-    EHIP(e, hipGetLastError());
-    EHIP(e, hipMemcpyAsync(e->h_tcount, e->d_tcount, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    EHIP(e, hipStreamSynchronize(st));
+    FM_HIP_TRY(&e->err, hipGetLastError());
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->h_tcount, e->d_tcount, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    FM_HIP_TRY(&e->err, hipStreamSynchronize(st));
     // the output's sizes are known: each tile's offset in its frame's scan, each frame's place in the buffer
     size_t o_total = 0;
     k = 0;
@@ -719,23 +681,23 @@ int encode_list(fm_mjpeg_enc* e, int n) {
         e->scan_len[f] = at;
         o_total += ((size_t)at + 15) & ~(size_t)15;
     }
-    if (int rc = grow(e, &e->d_out, &e->out_cap, o_total, "output")) return rc;
-    EHIP(e, hipMemcpyAsync(e->d_fi, e->h_fi, n * sizeof(FrameInfo), hipMemcpyHostToDevice, st));
-    EHIP(e, hipMemcpyAsync(e->d_ti, e->h_ti, ntiles * sizeof(TileInfo), hipMemcpyHostToDevice, st));
+    if (int rc = grow(e, e->d_out, o_total, o_total + o_total / 4, "output")) return rc;
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->d_fi, e->h_fi, n * sizeof(FrameInfo), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(e->d_ti, e->h_ti, ntiles * sizeof(TileInfo), hipMemcpyHostToDevice, st));
     k_enc_stuff<<<(unsigned)ntiles, kThreads, 0, st>>>(e->d_u, g, e->d_bits, e->d_fi, e->d_ti, e->d_out);
-    EHIP(e, hipGetLastError());
-    EHIP(e, hipEventRecord(e->e1, st));
-    EHIP(e, hipStreamSynchronize(st));
-    EHIP(e, hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
+    FM_HIP_TRY(&e->err, hipGetLastError());
+    FM_HIP_TRY(&e->err, hipEventRecord(e->e1, st));
+    FM_HIP_TRY(&e->err, hipStreamSynchronize(st));
+    FM_HIP_TRY(&e->err, hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
     e->last_n = n;
     return FM_OK;
 }
 
 int check_call(fm_mjpeg_enc* e, const void* frames, int n) {
     if (!e) return FM_EINVAL;
-    if (!e->d_coef) return efail(e, FM_ESTATE, "the encoder was not created");
-    if (!frames) return efail(e, FM_EINVAL, "null frames");
-    if (n < 1 || n > e->max_frames) return efail(e, FM_EINVAL, "%d frames, the encoder takes 1..%d per call", n, e->max_frames);
+    if (!e->d_coef) return fm::failf(&e->err, FM_ESTATE, "the encoder was not created");
+    if (!frames) return fm::failf(&e->err, FM_EINVAL, "null frames");
+    if (n < 1 || n > e->max_frames) return fm::failf(&e->err, FM_EINVAL, "%d frames, the encoder takes 1..%d per call", n, e->max_frames);
     return FM_OK;
 }
 
@@ -760,7 +722,7 @@ int fm_mjpeg_enc_create(int device, int width, int height, int max_frames, int q
     fm_mjpeg_enc* e = new fm_mjpeg_enc();
     *out = e;
     if (!valid_settings(width, height, quality, subsampling, restart_interval) || max_frames < 1 || max_frames > 65535)
-        return efail(e, FM_EINVAL, "bad settings: %dx%d, max_frames %d, quality %d (1..100), subsampling %d (0..2), "
+        return fm::failf(&e->err, FM_EINVAL, "bad settings: %dx%d, max_frames %d, quality %d (1..100), subsampling %d (0..2), "
                      "restart interval %d (0..65535)", width, height, max_frames, quality, subsampling, restart_interval);
     EncGeom& g = e->g;
     g.W = width, g.H = height;
@@ -770,7 +732,7 @@ int fm_mjpeg_enc_create(int device, int width, int height, int max_frames, int q
     const long long nmcu = (long long)g.mcux * mcuy;
     g.bpm = g.hs * g.vs + 2;
     if (nmcu * g.bpm > (1 << 20))  // a frame's bit offsets stay below 2^32 at the worst case of ~3500 bits a block
-        return efail(e, FM_ENOTSUP, "%dx%d: more than 2^20 blocks per frame", width, height);
+        return fm::failf(&e->err, FM_ENOTSUP, "%dx%d: more than 2^20 blocks per frame", width, height);
     g.nmcu = (int)nmcu, g.nblk = g.nmcu * g.bpm;
     g.ybw = (width + 7) / 8, g.ybh = (height + 7) / 8;
     g.crows = (height + g.vs - 1) / g.vs;
@@ -784,56 +746,38 @@ int fm_mjpeg_enc_create(int device, int width, int height, int max_frames, int q
     e->device = device, e->max_frames = max_frames;
     e->frame_bytes = (size_t)width * height * 3;
     e->header = make_header(width, height, quality, subsampling, restart_interval);
-    EHIP(e, hipSetDevice(device));
-    EHIP(e, hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
-    EHIP(e, hipEventCreate(&e->e0));
-    EHIP(e, hipEventCreate(&e->e1));
+    FM_HIP_TRY(&e->err, hipSetDevice(device));
+    FM_HIP_TRY(&e->err, hipStreamCreateWithFlags(e->st.put(), hipStreamNonBlocking));
+    FM_HIP_TRY(&e->err, hipEventCreate(e->e0.put()));
+    FM_HIP_TRY(&e->err, hipEventCreate(e->e1.put()));
     EncHuff H;
     build_huff(H);
     const size_t nb = (size_t)max_frames * g.nblk;
-    EHIP(e, hipMalloc((void**)&e->d_huff, sizeof H));
-    EHIP(e, hipMemcpy(e->d_huff, &H, sizeof H, hipMemcpyHostToDevice));
-    EHIP(e, hipMalloc((void**)&e->d_list, max_frames * sizeof(uint8_t*)));
-    EHIP(e, hipMalloc((void**)&e->d_bits, nb * sizeof(uint32_t)));
-    EHIP(e, hipMalloc((void**)&e->d_fbits, max_frames * sizeof(uint32_t)));
-    EHIP(e, hipMalloc((void**)&e->d_fi, max_frames * sizeof(FrameInfo)));
-    EHIP(e, hipHostMalloc((void**)&e->h_list, max_frames * sizeof(uint8_t*), hipHostMallocDefault));
-    EHIP(e, hipHostMalloc((void**)&e->h_fbits, max_frames * sizeof(uint32_t), hipHostMallocDefault));
-    EHIP(e, hipHostMalloc((void**)&e->h_fi, max_frames * sizeof(FrameInfo), hipHostMallocDefault));
-    EHIP(e, hipMalloc((void**)&e->d_coef, nb * 64 * sizeof(int16_t)));  // last: check_call tests it
+    FM_HIP_TRY(&e->err, e->d_huff.reserve(1));
+    FM_HIP_TRY(&e->err, hipMemcpy(e->d_huff, &H, sizeof H, hipMemcpyHostToDevice));
+    FM_HIP_TRY(&e->err, e->d_list.reserve(max_frames));
+    FM_HIP_TRY(&e->err, e->d_bits.reserve(nb));
+    FM_HIP_TRY(&e->err, e->d_fbits.reserve(max_frames));
+    FM_HIP_TRY(&e->err, e->d_fi.reserve(max_frames));
+    FM_HIP_TRY(&e->err, e->h_list.reserve(max_frames));
+    FM_HIP_TRY(&e->err, e->h_fbits.reserve(max_frames));
+    FM_HIP_TRY(&e->err, e->h_fi.reserve(max_frames));
+    FM_HIP_TRY(&e->err, e->d_coef.reserve(nb * 64));  // last: check_call tests it
     return FM_OK;
 }
 
-void fm_mjpeg_enc_destroy(fm_mjpeg_enc* e) {
-    if (!e) return;
-    if (e->st) (void)hipStreamSynchronize(e->st);
-    for (void* p : {(void*)e->d_huff, (void*)e->d_list, (void*)e->d_in, (void*)e->d_coef, (void*)e->d_bits, (void*)e->d_fbits,
-                    (void*)e->d_fi, (void*)e->d_ti, (void*)e->d_tcount, (void*)e->d_u, (void*)e->d_out})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)e->h_list, (void*)e->h_fbits, (void*)e->h_fi, (void*)e->h_ti, (void*)e->h_tcount})
-        if (p) (void)hipHostFree(p);
-    if (e->e0) (void)hipEventDestroy(e->e0);
-    if (e->e1) (void)hipEventDestroy(e->e1);
-    if (e->st) (void)hipStreamDestroy(e->st);
-    delete e;
-}
+void fm_mjpeg_enc_destroy(fm_mjpeg_enc* e) { delete e; }
 
 const char* fm_mjpeg_enc_last_error(const fm_mjpeg_enc* e) { return e ? e->err.c_str() : "null encoder"; }
 
 int fm_mjpeg_encode(fm_mjpeg_enc* e, const uint8_t* frames, int n, int on_device) {
     if (int rc = check_call(e, frames, n)) return rc;
-    EHIP(e, hipSetDevice(e->device));
+    FM_HIP_TRY(&e->err, hipSetDevice(e->device));
     const uint8_t* base = frames;
     if (!on_device) {
-        if (!e->d_in) {
-            const size_t want = (size_t)e->max_frames * e->frame_bytes;
-            if (hipMalloc((void**)&e->d_in, want) != hipSuccess) {
-                e->d_in = nullptr;
-                (void)hipGetLastError();
-                return efail(e, FM_ENOMEM, "frame staging: %zu bytes of device memory not available", want);
-            }
-        }
-        EHIP(e, hipMemcpyAsync(e->d_in, frames, (size_t)n * e->frame_bytes, hipMemcpyHostToDevice, e->st));
+        const size_t want = (size_t)e->max_frames * e->frame_bytes;
+        if (int rc = grow(e, e->d_in, want, want, "frame staging")) return rc;
+        FM_HIP_TRY(&e->err, hipMemcpyAsync(e->d_in, frames, (size_t)n * e->frame_bytes, hipMemcpyHostToDevice, e->st));
         base = e->d_in;
     }
     for (int i = 0; i < n; i++) e->h_list[i] = base + (size_t)i * e->frame_bytes;
@@ -843,8 +787,8 @@ int fm_mjpeg_encode(fm_mjpeg_enc* e, const uint8_t* frames, int n, int on_device
 int fm_mjpeg_encode_frame_list(fm_mjpeg_enc* e, const uint8_t* const* frames, int n) {
     if (int rc = check_call(e, frames, n)) return rc;
     for (int i = 0; i < n; i++)
-        if (!frames[i]) return efail(e, FM_EINVAL, "null frame %d", i);
-    EHIP(e, hipSetDevice(e->device));
+        if (!frames[i]) return fm::failf(&e->err, FM_EINVAL, "null frame %d", i);
+    FM_HIP_TRY(&e->err, hipSetDevice(e->device));
     for (int i = 0; i < n; i++) e->h_list[i] = frames[i];
     return encode_list(e, n);
 }
@@ -852,14 +796,14 @@ int fm_mjpeg_encode_frame_list(fm_mjpeg_enc* e, const uint8_t* const* frames, in
 int fm_mjpeg_enc_get(fm_mjpeg_enc* e, int frame, uint8_t* out, size_t cap, size_t* len) {
     if (len) *len = 0;
     if (!e) return FM_EINVAL;
-    if (frame < 0 || frame >= e->last_n) return efail(e, FM_ESTATE, "frame %d: the last call encoded %d", frame, e->last_n);
+    if (frame < 0 || frame >= e->last_n) return fm::failf(&e->err, FM_ESTATE, "frame %d: the last call encoded %d", frame, e->last_n);
     const size_t hl = e->header.size(), sl = e->scan_len[frame], need = hl + sl + 2;
     if (len) *len = need;
-    if (!out || cap < need) return efail(e, FM_EINVAL, "frame %d needs %zu bytes, the buffer holds %zu", frame, need, cap);
+    if (!out || cap < need) return fm::failf(&e->err, FM_EINVAL, "frame %d needs %zu bytes, the buffer holds %zu", frame, need, cap);
     std::memcpy(out, e->header.data(), hl);
-    EHIP(e, hipSetDevice(e->device));
-    EHIP(e, hipMemcpyAsync(out + hl, e->d_out + e->h_fi[frame].obase, sl, hipMemcpyDeviceToHost, e->st));
-    EHIP(e, hipStreamSynchronize(e->st));
+    FM_HIP_TRY(&e->err, hipSetDevice(e->device));
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(out + hl, e->d_out + e->h_fi[frame].obase, sl, hipMemcpyDeviceToHost, e->st));
+    FM_HIP_TRY(&e->err, hipStreamSynchronize(e->st));
     out[hl + sl] = 0xFF;
     out[hl + sl + 1] = 0xD9;
     return FM_OK;
@@ -867,12 +811,12 @@ int fm_mjpeg_enc_get(fm_mjpeg_enc* e, int frame, uint8_t* out, size_t cap, size_
 
 int fm_mjpeg_enc_coefficients(fm_mjpeg_enc* e, int frame, int16_t* out, size_t cap) {
     if (!e) return FM_EINVAL;
-    if (frame < 0 || frame >= e->last_n) return efail(e, FM_ESTATE, "frame %d: the last call encoded %d", frame, e->last_n);
+    if (frame < 0 || frame >= e->last_n) return fm::failf(&e->err, FM_ESTATE, "frame %d: the last call encoded %d", frame, e->last_n);
     const size_t need = (size_t)e->g.nblk * 64;
-    if (!out || cap < need) return efail(e, FM_EINVAL, "frame %d has %zu coefficients, the buffer holds %zu", frame, need, cap);
-    EHIP(e, hipSetDevice(e->device));
-    EHIP(e, hipMemcpyAsync(out, e->d_coef + (size_t)frame * need, need * sizeof(int16_t), hipMemcpyDeviceToHost, e->st));
-    EHIP(e, hipStreamSynchronize(e->st));
+    if (!out || cap < need) return fm::failf(&e->err, FM_EINVAL, "frame %d has %zu coefficients, the buffer holds %zu", frame, need, cap);
+    FM_HIP_TRY(&e->err, hipSetDevice(e->device));
+    FM_HIP_TRY(&e->err, hipMemcpyAsync(out, e->d_coef + (size_t)frame * need, need * sizeof(int16_t), hipMemcpyDeviceToHost, e->st));
+    FM_HIP_TRY(&e->err, hipStreamSynchronize(e->st));
     return (int)std::min<size_t>(need, 0x7fffffff);
 }
 

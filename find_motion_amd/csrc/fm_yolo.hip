@@ -15,7 +15,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -24,6 +23,7 @@
 
 #include "../../include/find_motion_amd.h"
 #include "fm_internal.h"
+#include "fm_roi.h"
 
 namespace fm {
 namespace yolo {
@@ -234,10 +234,10 @@ struct Layer {
     int alias = -1;                 // >= 0: the route whose buffer this layer writes into
     int alias_c = 0;                // at this channel
     bool in_place = false;          // a route whose sources wrote into its buffer
-    float* buf = nullptr;           // owned activations [max_frames][C][H][W] (null: a view of another layer's)
+    DevBuf<float> buf;              // owned activations [max_frames][C][H][W] (empty: a view of another layer's)
     View v{nullptr, 0};
-    float* wp = nullptr;  // conv: packed weights
-    float* bias = nullptr;
+    DevBuf<float> wp;  // conv: packed weights
+    DevBuf<float> bias;
     int K = 0, Kpad = 0, Mpad = 0, WM = 2;
 };
 
@@ -248,57 +248,29 @@ using namespace fm::yolo;
 
 struct fm_yolo {
     int device = 0;
-    hipStream_t stream = nullptr;
+    fm::Stream stream;  // (before the buffers used on it: they are released first)
     std::string err;
     int channels = 3, net_w = 0, net_h = 0, classes = 0, max_frames = 0;
     float zero_thresh = 0.f;
     std::vector<Layer> L;
     std::vector<int> heads;
     int total_rows = 0;
-    float* d_blob = nullptr;
-    float* d_anchors = nullptr;
-    float* d_lut = nullptr;
-    float* d_cand = nullptr;
-    int* d_cnt = nullptr;
-    // frames -> ROI -> blob
-    uint8_t *d_raw = nullptr, *d_roi = nullptr;
-    size_t cap_raw = 0, cap_roi = 0;
-    int32_t *d_axo = nullptr, *d_axc = nullptr, *d_ayo = nullptr, *d_ayc = nullptr;
-    float *d_axw = nullptr, *d_ayw = nullptr;
-    int area_key[4] = {0, 0, 0, 0};  // (W, H, w, h) the area tables are for
-    fm::AreaAxis ax, ay;
-    int4 *d_xt = nullptr, *d_yt = nullptr;
+    fm::DevBuf<float> d_blob, d_anchors, d_lut, d_cand;
+    fm::DevBuf<int> d_cnt;
+    fm::RoiStage roi{false};  // frames -> ROI (-> blob)
+    fm::DevBuf<int4> d_xt, d_yt;
     int lin_key[2] = {0, 0};  // (rw, rh) the linear tables are for
     int last_n = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    fm::Event ev[4];
     double ms[3] = {0., 0., 0.};
+
+    ~fm_yolo() {
+        if (stream || d_blob) {
+            (void)hipSetDevice(device);
+            if (stream) (void)hipStreamSynchronize(stream);
+        }
+    }
 };
-
-static int yfail(fm_yolo* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define YH(h, x)                                                                       \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) return yfail(h, FM_EHIP, "%s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-static int ygrow(fm_yolo* h, T** p, size_t& cap, size_t count) {
-    if (count <= cap && *p) return 0;
-    if (*p) YH(h, hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    YH(h, hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
-    cap = count;
-    return 0;
-}
 
 static inline unsigned nblk(long long total, int bs = 256) { return (unsigned)((total + bs - 1) / bs); }
 
@@ -329,13 +301,13 @@ static void linear8u_taps(int ssize, int dsize, std::vector<int4>& out) {
 
 // Shapes, aliasing and every consistency check: no HIP call.
 static int plan(fm_yolo* h, const fm_yolo_desc* d) {
-    if (!d->layers || d->n_layers < 1) return yfail(h, FM_EINVAL, "no layers");
+    if (!d->layers || d->n_layers < 1) return fm::failf(&h->err, FM_EINVAL, "no layers");
     if (d->net_w < 1 || d->net_h < 1 || d->channels < 1 || d->classes < 0 || d->max_frames < 1)
-        return yfail(h, FM_EINVAL, "net_w, net_h, channels and max_frames must be >= 1, classes >= 0");
-    if (!(d->zero_thresh >= 0.f && d->zero_thresh < 1.f)) return yfail(h, FM_EINVAL, "zero_thresh outside [0, 1)");
+        return fm::failf(&h->err, FM_EINVAL, "net_w, net_h, channels and max_frames must be >= 1, classes >= 0");
+    if (!(d->zero_thresh >= 0.f && d->zero_thresh < 1.f)) return fm::failf(&h->err, FM_EINVAL, "zero_thresh outside [0, 1)");
     if (d->n_weights < 0 || d->n_biases < 0 || d->n_anchors < 0 || (d->n_weights && !d->weights) ||
         (d->n_biases && !d->biases) || (d->n_anchors && !d->anchors))
-        return yfail(h, FM_EINVAL, "null weights, biases or anchors");
+        return fm::failf(&h->err, FM_EINVAL, "null weights, biases or anchors");
     h->channels = d->channels;
     h->net_w = d->net_w;
     h->net_h = d->net_h;
@@ -345,7 +317,7 @@ static int plan(fm_yolo* h, const fm_yolo_desc* d) {
     h->L.resize(d->n_layers);
     const long long lim = (1ll << 31) - 1;
     if ((long long)d->max_frames * d->channels * d->net_h * d->net_w > lim)
-        return yfail(h, FM_EINVAL, "network input of %d frames exceeds 2^31 elements", d->max_frames);
+        return fm::failf(&h->err, FM_EINVAL, "network input of %d frames exceeds 2^31 elements", d->max_frames);
     for (int i = 0; i < d->n_layers; i++) {
         Layer& l = h->L[i];
         l.d = d->layers[i];
@@ -357,12 +329,12 @@ static int plan(fm_yolo* h, const fm_yolo_desc* d) {
         case FM_YOLO_CONV: {
             if (q.filters < 1 || (q.size != 1 && q.size != 3) || (q.stride != 1 && q.stride != 2) || q.pad < 0 ||
                 q.pad > q.size / 2 || (q.leaky != 0 && q.leaky != 1))
-                return yfail(h, FM_EINVAL, "layer %d: convolution filters=%d size=%d stride=%d pad=%d leaky=%d", i,
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: convolution filters=%d size=%d stride=%d pad=%d leaky=%d", i,
                              q.filters, q.size, q.stride, q.pad, q.leaky);
             const long long K = (long long)l.Cin * q.size * q.size;
             if (q.weight_ofs < 0 || q.weight_ofs + K * q.filters > d->n_weights || q.bias_ofs < 0 ||
                 q.bias_ofs + q.filters > d->n_biases || K > (1 << 24))
-                return yfail(h, FM_EINVAL, "layer %d: %d x %lld weights do not lie inside the arrays", i, q.filters, K);
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: %d x %lld weights do not lie inside the arrays", i, q.filters, K);
             l.C = q.filters;
             l.H = (l.Hin + 2 * q.pad - q.size) / q.stride + 1;
             l.W = (l.Win + 2 * q.pad - q.size) / q.stride + 1;
@@ -374,13 +346,13 @@ static int plan(fm_yolo* h, const fm_yolo_desc* d) {
         }
         case FM_YOLO_MAXPOOL:
             if (q.size != 2 || (q.stride != 1 && q.stride != 2))
-                return yfail(h, FM_EINVAL, "layer %d: maxpool size=%d stride=%d", i, q.size, q.stride);
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: maxpool size=%d stride=%d", i, q.size, q.stride);
             l.C = l.Cin;
             l.H = q.stride == 1 ? l.Hin : (l.Hin + 1) / 2;
             l.W = q.stride == 1 ? l.Win : (l.Win + 1) / 2;
             break;
         case FM_YOLO_UPSAMPLE:
-            if (q.stride != 2) return yfail(h, FM_EINVAL, "layer %d: upsample stride=%d", i, q.stride);
+            if (q.stride != 2) return fm::failf(&h->err, FM_EINVAL, "layer %d: upsample stride=%d", i, q.stride);
             l.C = l.Cin;
             l.H = 2 * l.Hin;
             l.W = 2 * l.Win;
@@ -388,20 +360,20 @@ static int plan(fm_yolo* h, const fm_yolo_desc* d) {
         case FM_YOLO_ROUTE: {
             const int a = q.from[0], b = q.from[1];
             if (a < 0 || a >= i || b < -1 || b >= i)
-                return yfail(h, FM_EINVAL, "layer %d: route to layers %d, %d (only earlier layers)", i, a, b);
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: route to layers %d, %d (only earlier layers)", i, a, b);
             l.C = h->L[a].C + (b >= 0 ? h->L[b].C : 0);
             l.H = h->L[a].H;
             l.W = h->L[a].W;
             if (b >= 0 && (h->L[b].H != l.H || h->L[b].W != l.W))
-                return yfail(h, FM_EINVAL, "layer %d: route joins %dx%d with %dx%d", i, l.W, l.H, h->L[b].W, h->L[b].H);
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: route joins %dx%d with %dx%d", i, l.W, l.H, h->L[b].W, h->L[b].H);
             break;
         }
         case FM_YOLO_SHORTCUT: {
             const int a = q.from[0];
             if (i == 0 || a < 0 || a >= i)
-                return yfail(h, FM_EINVAL, "layer %d: shortcut from layer %d (only earlier layers)", i, a);
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: shortcut from layer %d (only earlier layers)", i, a);
             if (h->L[a].C != l.Cin || h->L[a].H != l.Hin || h->L[a].W != l.Win)
-                return yfail(h, FM_EINVAL, "layer %d: shortcut adds %dx%dx%d to %dx%dx%d", i, h->L[a].C, h->L[a].H,
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: shortcut adds %dx%dx%d to %dx%dx%d", i, h->L[a].C, h->L[a].H,
                              h->L[a].W, l.Cin, l.Hin, l.Win);
             l.C = l.Cin;
             l.H = l.Hin;
@@ -409,28 +381,28 @@ static int plan(fm_yolo* h, const fm_yolo_desc* d) {
             break;
         }
         case FM_YOLO_HEAD:
-            if (i == 0) return yfail(h, FM_EINVAL, "layer 0: a head needs a layer before it");
-            if (d->classes < 1) return yfail(h, FM_EINVAL, "layer %d: a head needs classes >= 1", i);
+            if (i == 0) return fm::failf(&h->err, FM_EINVAL, "layer 0: a head needs a layer before it");
+            if (d->classes < 1) return fm::failf(&h->err, FM_EINVAL, "layer %d: a head needs classes >= 1", i);
             if (q.n_mask < 1 || q.anchor_ofs < 0 || (long long)q.anchor_ofs + q.n_mask > d->n_anchors)
-                return yfail(h, FM_EINVAL, "layer %d: head anchors %d..%d outside the %d given", i, q.anchor_ofs,
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: head anchors %d..%d outside the %d given", i, q.anchor_ofs,
                              q.anchor_ofs + q.n_mask, d->n_anchors);
             if (l.Cin != q.n_mask * (d->classes + 5))
-                return yfail(h, FM_EINVAL, "layer %d: head with %d input channels, len(mask) * (classes + 5) = %d", i,
+                return fm::failf(&h->err, FM_EINVAL, "layer %d: head with %d input channels, len(mask) * (classes + 5) = %d", i,
                              l.Cin, q.n_mask * (d->classes + 5));
             l.C = l.Cin;
             l.H = l.Hin;
             l.W = l.Win;
             h->heads.push_back(i);
             if ((long long)h->total_rows + (long long)q.n_mask * l.H * l.W > (1 << 24))
-                return yfail(h, FM_EINVAL, "more than 2^24 candidate rows");
+                return fm::failf(&h->err, FM_EINVAL, "more than 2^24 candidate rows");
             h->total_rows += q.n_mask * l.H * l.W;
             break;
         default:
-            return yfail(h, FM_EINVAL, "layer %d: unknown kind %d", i, q.kind);
+            return fm::failf(&h->err, FM_EINVAL, "layer %d: unknown kind %d", i, q.kind);
         }
-        if (l.H < 1 || l.W < 1) return yfail(h, FM_EINVAL, "layer %d: empty output %dx%d", i, l.W, l.H);
+        if (l.H < 1 || l.W < 1) return fm::failf(&h->err, FM_EINVAL, "layer %d: empty output %dx%d", i, l.W, l.H);
         if ((long long)d->max_frames * l.C * l.H * l.W > lim)
-            return yfail(h, FM_EINVAL, "layer %d: %d frames of %dx%dx%d exceed 2^31 elements", i, d->max_frames, l.C,
+            return fm::failf(&h->err, FM_EINVAL, "layer %d: %d frames of %dx%dx%d exceed 2^31 elements", i, d->max_frames, l.C,
                          l.H, l.W);
     }
     // a route of two layers that write (not views, not yet placed elsewhere) takes them in place
@@ -519,13 +491,13 @@ static int run_layers(fm_yolo* h, int n) {
         default:
             break;  // a head decodes its input where it lies
         }
-        YH(h, hipGetLastError());
+        FM_HIP_TRY(&h->err, hipGetLastError());
     }
     return FM_OK;
 }
 
 static int run_decode(fm_yolo* h, int n, float confidence) {
-    YH(h, hipMemsetAsync(h->d_cnt, 0, (size_t)h->max_frames * sizeof(int), h->stream));
+    FM_HIP_TRY(&h->err, hipMemsetAsync(h->d_cnt, 0, (size_t)h->max_frames * sizeof(int), h->stream));
     for (size_t k = 0; k < h->heads.size(); k++) {
         const Layer& l = h->L[h->heads[k]];
         const long long total = (long long)n * l.d.n_mask * l.H * l.W;
@@ -533,7 +505,7 @@ static int run_decode(fm_yolo* h, int n, float confidence) {
                                                           h->d_anchors + 2 * l.d.anchor_ofs, (float)h->net_w,
                                                           (float)h->net_h, h->zero_thresh, confidence, (int)k,
                                                           h->d_cand, h->total_rows, h->d_cnt, total);
-        YH(h, hipGetLastError());
+        FM_HIP_TRY(&h->err, hipGetLastError());
     }
     return FM_OK;
 }
@@ -541,8 +513,8 @@ static int run_decode(fm_yolo* h, int n, float confidence) {
 // Waits for the stream, then copies each frame's candidates out sorted by (head, row).
 static int collect(fm_yolo* h, int n, float* cand, int cap, int32_t* counts) {
     std::vector<int> cnt(n);
-    YH(h, hipMemcpyAsync(cnt.data(), h->d_cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    YH(h, hipStreamSynchronize(h->stream));
+    FM_HIP_TRY(&h->err, hipMemcpyAsync(cnt.data(), h->d_cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    FM_HIP_TRY(&h->err, hipStreamSynchronize(h->stream));
     std::vector<float> rows;
     std::vector<int> order;
     for (int b = 0; b < n; b++) {
@@ -550,7 +522,7 @@ static int collect(fm_yolo* h, int n, float* cand, int cap, int32_t* counts) {
         counts[b] = c;
         if (!c) continue;
         rows.resize((size_t)c * FM_YOLO_CAND);
-        YH(h, hipMemcpy(rows.data(), h->d_cand + (size_t)b * h->total_rows * FM_YOLO_CAND,
+        FM_HIP_TRY(&h->err, hipMemcpy(rows.data(), h->d_cand + (size_t)b * h->total_rows * FM_YOLO_CAND,
                         rows.size() * sizeof(float), hipMemcpyDeviceToHost));
         order.resize(c);
         for (int i = 0; i < c; i++) order[i] = i;
@@ -582,35 +554,34 @@ int fm_yolo_create(int device, const fm_yolo_desc* d, fm_yolo** out) {
     if (!h) return FM_ENOMEM;
     *out = h;
     h->device = device;
-    if (!d) return yfail(h, FM_EINVAL, "null description");
-    if (device < 0) return yfail(h, FM_EINVAL, "device %d", device);
+    if (!d) return fm::failf(&h->err, FM_EINVAL, "null description");
+    if (device < 0) return fm::failf(&h->err, FM_EINVAL, "device %d", device);
     if (int rc = plan(h, d)) {
         h->L.clear();
         return rc;
     }
     int ndev = 0;
-    YH(h, hipGetDeviceCount(&ndev));
-    if (device >= ndev) return yfail(h, FM_EINVAL, "device %d of %d", device, ndev);
-    YH(h, hipSetDevice(device));
-    YH(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (auto& e : h->ev) YH(h, hipEventCreate(&e));
+    FM_HIP_TRY(&h->err, hipGetDeviceCount(&ndev));
+    if (device >= ndev) return fm::failf(&h->err, FM_EINVAL, "device %d of %d", device, ndev);
+    FM_HIP_TRY(&h->err, hipSetDevice(device));
+    FM_HIP_TRY(&h->err, hipStreamCreateWithFlags(h->stream.put(), hipStreamNonBlocking));
+    for (auto& e : h->ev) FM_HIP_TRY(&h->err, hipEventCreate(e.put()));
     const size_t blob = (size_t)h->channels * h->net_h * h->net_w;
-    YH(h, hipMalloc((void**)&h->d_blob, (size_t)h->max_frames * blob * sizeof(float)));
-    YH(h, hipMalloc((void**)&h->d_anchors, std::max<size_t>(2 * (size_t)d->n_anchors, 1) * sizeof(float)));
+    FM_HIP_TRY(&h->err, h->d_blob.reserve((size_t)h->max_frames * blob));
+    FM_HIP_TRY(&h->err, h->d_anchors.reserve(2 * (size_t)d->n_anchors));
     if (d->n_anchors)
-        YH(h, hipMemcpy(h->d_anchors, d->anchors, 2 * (size_t)d->n_anchors * sizeof(float), hipMemcpyHostToDevice));
+        FM_HIP_TRY(&h->err, hipMemcpy(h->d_anchors, d->anchors, 2 * (size_t)d->n_anchors * sizeof(float), hipMemcpyHostToDevice));
     float lut[256];
     for (int v = 0; v < 256; v++) lut[v] = (float)((double)v * 0.00392);
-    YH(h, hipMalloc((void**)&h->d_lut, sizeof lut));
-    YH(h, hipMemcpy(h->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
-    YH(h, hipMalloc((void**)&h->d_cnt, (size_t)h->max_frames * sizeof(int)));
-    YH(h, hipMalloc((void**)&h->d_cand,
-                    std::max<size_t>((size_t)h->max_frames * h->total_rows, 1) * FM_YOLO_CAND * sizeof(float)));
+    FM_HIP_TRY(&h->err, h->d_lut.reserve(256));
+    FM_HIP_TRY(&h->err, hipMemcpy(h->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
+    FM_HIP_TRY(&h->err, h->d_cnt.reserve((size_t)h->max_frames));
+    FM_HIP_TRY(&h->err, h->d_cand.reserve(std::max<size_t>((size_t)h->max_frames * h->total_rows, 1) * FM_YOLO_CAND));
     // activations: a layer placed in a route's buffer and a head own none
     for (auto& l : h->L) {
         if (l.alias >= 0 || l.d.kind == FM_YOLO_HEAD) continue;
         const size_t per = (size_t)l.C * l.H * l.W;
-        YH(h, hipMalloc((void**)&l.buf, (size_t)h->max_frames * per * sizeof(float)));
+        FM_HIP_TRY(&h->err, l.buf.reserve((size_t)h->max_frames * per));
         l.v = View{l.buf, per};
     }
     for (size_t i = 0; i < h->L.size(); i++) {
@@ -630,32 +601,15 @@ int fm_yolo_create(int device, const fm_yolo_desc* d, fm_yolo** out) {
         const float* w = d->weights + l.d.weight_ofs;
         for (int m = 0; m < l.C; m++)
             for (int k = 0; k < l.K; k++) wp[(size_t)k * l.Mpad + m] = w[(size_t)m * l.K + k];
-        YH(h, hipMalloc((void**)&l.wp, wp.size() * sizeof(float)));
-        YH(h, hipMemcpy(l.wp, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-        YH(h, hipMalloc((void**)&l.bias, (size_t)l.C * sizeof(float)));
-        YH(h, hipMemcpy(l.bias, d->biases + l.d.bias_ofs, (size_t)l.C * sizeof(float), hipMemcpyHostToDevice));
+        FM_HIP_TRY(&h->err, l.wp.reserve(wp.size()));
+        FM_HIP_TRY(&h->err, hipMemcpy(l.wp, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
+        FM_HIP_TRY(&h->err, l.bias.reserve((size_t)l.C));
+        FM_HIP_TRY(&h->err, hipMemcpy(l.bias, d->biases + l.d.bias_ofs, (size_t)l.C * sizeof(float), hipMemcpyHostToDevice));
     }
     return FM_OK;
 }
 
-void fm_yolo_destroy(fm_yolo* h) {
-    if (!h) return;
-    if (h->stream || h->d_blob) {
-        (void)hipSetDevice(h->device);
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        for (auto& l : h->L)
-            for (void* p : {(void*)l.buf, (void*)l.wp, (void*)l.bias})
-                if (p) (void)hipFree(p);
-        for (void* p : {(void*)h->d_blob, (void*)h->d_anchors, (void*)h->d_lut, (void*)h->d_cand, (void*)h->d_cnt,
-                        (void*)h->d_raw, (void*)h->d_roi, (void*)h->d_axo, (void*)h->d_axc, (void*)h->d_ayo,
-                        (void*)h->d_ayc, (void*)h->d_axw, (void*)h->d_ayw, (void*)h->d_xt, (void*)h->d_yt})
-            if (p) (void)hipFree(p);
-        for (auto& e : h->ev)
-            if (e) (void)hipEventDestroy(e);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
-}
+void fm_yolo_destroy(fm_yolo* h) { delete h; }
 
 const char* fm_yolo_last_error(const fm_yolo* h) { return h ? h->err.c_str() : "null detector"; }
 
@@ -675,15 +629,15 @@ int fm_yolo_route_in_place(const fm_yolo* h, int layer) {
 
 int fm_yolo_forward(fm_yolo* h, const float* blob, int n) {
     if (!h || !h->d_blob) return FM_EINVAL;
-    if (!blob || n < 1) return yfail(h, FM_EINVAL, "bad arguments (blob, n >= 1)");
-    if (n > h->max_frames) return yfail(h, FM_EINVAL, "%d frames, the detector was created for %d", n, h->max_frames);
-    YH(h, hipSetDevice(h->device));
+    if (!blob || n < 1) return fm::failf(&h->err, FM_EINVAL, "bad arguments (blob, n >= 1)");
+    if (n > h->max_frames) return fm::failf(&h->err, FM_EINVAL, "%d frames, the detector was created for %d", n, h->max_frames);
+    FM_HIP_TRY(&h->err, hipSetDevice(h->device));
     const size_t per = (size_t)h->channels * h->net_h * h->net_w;
-    YH(h, hipMemcpyAsync(h->d_blob, blob, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    YH(h, hipEventRecord(h->ev[1], h->stream));
+    FM_HIP_TRY(&h->err, hipMemcpyAsync(h->d_blob, blob, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[1], h->stream));
     if (int rc = run_layers(h, n)) return rc;
-    YH(h, hipEventRecord(h->ev[2], h->stream));
-    YH(h, hipStreamSynchronize(h->stream));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[2], h->stream));
+    FM_HIP_TRY(&h->err, hipStreamSynchronize(h->stream));
     h->last_n = n;
     read_ms(h, 1, 2);
     return FM_OK;
@@ -691,12 +645,12 @@ int fm_yolo_forward(fm_yolo* h, const float* blob, int n) {
 
 int fm_yolo_decode(fm_yolo* h, int n, float confidence, float* cand, int cap, int32_t* counts) {
     if (!h || !h->d_blob) return FM_EINVAL;
-    if (n < 1 || cap < 0 || !counts || (cap > 0 && !cand)) return yfail(h, FM_EINVAL, "bad arguments (counts[n], cand[n][cap][9])");
-    if (n != h->last_n) return yfail(h, FM_ESTATE, "%d frames asked for, the last call ran %d", n, h->last_n);
-    YH(h, hipSetDevice(h->device));
-    YH(h, hipEventRecord(h->ev[2], h->stream));
+    if (n < 1 || cap < 0 || !counts || (cap > 0 && !cand)) return fm::failf(&h->err, FM_EINVAL, "bad arguments (counts[n], cand[n][cap][9])");
+    if (n != h->last_n) return fm::failf(&h->err, FM_ESTATE, "%d frames asked for, the last call ran %d", n, h->last_n);
+    FM_HIP_TRY(&h->err, hipSetDevice(h->device));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[2], h->stream));
     if (int rc = run_decode(h, n, confidence)) return rc;
-    YH(h, hipEventRecord(h->ev[3], h->stream));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[3], h->stream));
     if (int rc = collect(h, n, cand, cap, counts)) return rc;
     read_ms(h, 2, 3);
     return FM_OK;
@@ -704,16 +658,16 @@ int fm_yolo_decode(fm_yolo* h, int n, float confidence, float* cand, int cap, in
 
 int fm_yolo_layer_output(fm_yolo* h, int layer, float* out, size_t cap) {
     if (!h || !h->d_blob) return FM_EINVAL;
-    if (layer < -1 || layer >= (int)h->L.size()) return yfail(h, FM_EINVAL, "layer %d of %zu", layer, h->L.size());
-    if (h->last_n < 1) return yfail(h, FM_ESTATE, "no call yet");
+    if (layer < -1 || layer >= (int)h->L.size()) return fm::failf(&h->err, FM_EINVAL, "layer %d of %zu", layer, h->L.size());
+    if (h->last_n < 1) return fm::failf(&h->err, FM_ESTATE, "no call yet");
     const View v = layer < 0 ? input_of(h, 0) : h->L[layer].v;
     const size_t per = layer < 0 ? (size_t)h->channels * h->net_h * h->net_w
                                  : (size_t)h->L[layer].C * h->L[layer].H * h->L[layer].W;
     const size_t total = per * h->last_n;
-    if (!out || cap < total) return yfail(h, FM_EINVAL, "layer %d holds %zu floats, room for %zu", layer, total, cap);
-    YH(h, hipSetDevice(h->device));
+    if (!out || cap < total) return fm::failf(&h->err, FM_EINVAL, "layer %d holds %zu floats, room for %zu", layer, total, cap);
+    FM_HIP_TRY(&h->err, hipSetDevice(h->device));
     for (int b = 0; b < h->last_n; b++)
-        YH(h, hipMemcpy(out + (size_t)b * per, v.p + (size_t)b * v.bs, per * sizeof(float), hipMemcpyDeviceToHost));
+        FM_HIP_TRY(&h->err, hipMemcpy(out + (size_t)b * per, v.p + (size_t)b * v.bs, per * sizeof(float), hipMemcpyDeviceToHost));
     return (int)total;
 }
 
@@ -732,90 +686,38 @@ static int detect_impl(fm_yolo* h, const uint8_t* frames, const uint8_t* const* 
                        int* roi_h_out) {
     if (!h || !h->d_blob) return FM_EINVAL;
     if ((!frames && !list) || n < 1 || H < 1 || W < 1 || roi_w < 1 || cap < 0 || !counts || (cap > 0 && !cand))
-        return yfail(h, FM_EINVAL, "bad arguments (n >= 1, frame and ROI sizes >= 1, counts[n], cand[n][cap][9])");
-    if (n > h->max_frames) return yfail(h, FM_EINVAL, "%d frames, the detector was created for %d", n, h->max_frames);
-    if (h->channels != 3) return yfail(h, FM_EINVAL, "a network of %d input channels takes no BGR frames", h->channels);
-    const int rw = roi_w, rh = (int)(H * ((double)roi_w / (double)W));  // imutils.resize(raw, width=roi_w)
+        return fm::failf(&h->err, FM_EINVAL, "bad arguments (n >= 1, frame and ROI sizes >= 1, counts[n], cand[n][cap][9])");
+    if (n > h->max_frames) return fm::failf(&h->err, FM_EINVAL, "%d frames, the detector was created for %d", n, h->max_frames);
+    if (h->channels != 3) return fm::failf(&h->err, FM_EINVAL, "a network of %d input channels takes no BGR frames", h->channels);
+    FM_HIP_TRY(&h->err, hipSetDevice(h->device));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[0], h->stream));
+    const uint8_t* roi = nullptr;
+    int rh = 0, rc = h->roi.run(&h->err, h->stream, frames, list, n, H, W, on_device != 0, roi_w, &roi, &rh);
     if (roi_h_out) *roi_h_out = rh;
-    if (rh < 1) return yfail(h, FM_EINVAL, "ROI height 0 for a %dx%d frame", W, H);
-    const double sx = 1. / ((double)rw / W), sy = 1. / ((double)rh / H);
-    const bool identity = rw == W && rh == H;
-    if (!identity && !(sx >= 1 && sy >= 1))
-        return yfail(h, FM_ENOTSUP, "frame width %d < ROI width %d: INTER_AREA upscaling is not supported", W, rw);
-    fm::AreaAxis ax, ay;
-    const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
-    const bool fast = std::fabs(sx - isx) < 2.220446049250313e-16 && std::fabs(sy - isy) < 2.220446049250313e-16;
-    const bool new_area = !identity && !fast &&
-                          (h->area_key[0] != W || h->area_key[1] != H || h->area_key[2] != rw || h->area_key[3] != rh);
-    if (new_area && (!fm::build_area_axis(W, rw, sx, ax) || !fm::build_area_axis(H, rh, sy, ay)))
-        return yfail(h, FM_ENOTSUP, "INTER_AREA table with non-consecutive taps");
-    YH(h, hipSetDevice(h->device));
-    int rc;
-    const size_t fb = (size_t)H * W * 3;
-    const uint8_t* src = frames;
-    YH(h, hipEventRecord(h->ev[0], h->stream));
-    if (list || !on_device) {
-        if ((rc = ygrow(h, &h->d_raw, h->cap_raw, n * fb))) return rc;
-        if (list)
-            for (int i = 0; i < n; i++)
-                YH(h, hipMemcpyAsync(h->d_raw + (size_t)i * fb, list[i], fb, hipMemcpyDeviceToDevice, h->stream));
-        else
-            YH(h, hipMemcpyAsync(h->d_raw, frames, n * fb, hipMemcpyHostToDevice, h->stream));
-        src = h->d_raw;
-    }
-    const uint8_t* roi = src;
-    if (!identity) {
-        if ((rc = ygrow(h, &h->d_roi, h->cap_roi, (size_t)n * rh * rw * 3))) return rc;
-        if (fast) {
-            YH(h, fm::launch_resize_area_fast(h->stream, src, h->d_roi, n, H, W, rh, rw, isx, isy));
-        } else {
-            if (new_area) {
-                YH(h, hipStreamSynchronize(h->stream));
-                h->area_key[0] = 0;
-                h->ax = ax;
-                h->ay = ay;
-                struct { void** p; const void* s; size_t b; } up[6] = {
-                    {(void**)&h->d_axo, ax.ofs.data(), ax.ofs.size() * 4}, {(void**)&h->d_axc, ax.cnt.data(), ax.cnt.size() * 4},
-                    {(void**)&h->d_axw, ax.wt.data(), ax.wt.size() * 4},   {(void**)&h->d_ayo, ay.ofs.data(), ay.ofs.size() * 4},
-                    {(void**)&h->d_ayc, ay.cnt.data(), ay.cnt.size() * 4}, {(void**)&h->d_ayw, ay.wt.data(), ay.wt.size() * 4}};
-                for (auto& u : up) {
-                    if (*u.p) YH(h, hipFree(*u.p));
-                    *u.p = nullptr;
-                    YH(h, hipMalloc(u.p, u.b));
-                    YH(h, hipMemcpy(*u.p, u.s, u.b, hipMemcpyHostToDevice));
-                }
-                h->area_key[0] = W;
-                h->area_key[1] = H;
-                h->area_key[2] = rw;
-                h->area_key[3] = rh;
-            }
-            YH(h, fm::launch_resize_area(h->stream, src, h->d_roi, n, H, W, rh, rw, h->d_axo, h->d_axc, h->d_axw,
-                                         h->ax.max_taps, h->d_ayo, h->d_ayc, h->d_ayw, h->ay.max_taps));
-        }
-        roi = h->d_roi;
-    }
+    if (rc) return rc;
+    const int rw = roi_w;
     if (h->lin_key[0] != rw || h->lin_key[1] != rh) {
         std::vector<int4> xt, yt;
         linear8u_taps(rw, h->net_w, xt);
         linear8u_taps(rh, h->net_h, yt);
-        YH(h, hipStreamSynchronize(h->stream));
+        FM_HIP_TRY(&h->err, hipStreamSynchronize(h->stream));
         h->lin_key[0] = 0;
-        if (!h->d_xt) YH(h, hipMalloc((void**)&h->d_xt, xt.size() * sizeof(int4)));
-        if (!h->d_yt) YH(h, hipMalloc((void**)&h->d_yt, yt.size() * sizeof(int4)));
-        YH(h, hipMemcpy(h->d_xt, xt.data(), xt.size() * sizeof(int4), hipMemcpyHostToDevice));
-        YH(h, hipMemcpy(h->d_yt, yt.data(), yt.size() * sizeof(int4), hipMemcpyHostToDevice));
+        FM_HIP_TRY(&h->err, h->d_xt.reserve(xt.size()));
+        FM_HIP_TRY(&h->err, h->d_yt.reserve(yt.size()));
+        FM_HIP_TRY(&h->err, hipMemcpy(h->d_xt, xt.data(), xt.size() * sizeof(int4), hipMemcpyHostToDevice));
+        FM_HIP_TRY(&h->err, hipMemcpy(h->d_yt, yt.data(), yt.size() * sizeof(int4), hipMemcpyHostToDevice));
         h->lin_key[0] = rw;
         h->lin_key[1] = rh;
     }
     const long long total = (long long)n * h->net_h * h->net_w;
     k_yolo_blob<<<nblk(total), 256, 0, h->stream>>>(roi, rh, rw, h->d_xt, h->d_yt, h->d_lut, h->d_blob, h->net_h,
                                                     h->net_w, total);
-    YH(h, hipGetLastError());
-    YH(h, hipEventRecord(h->ev[1], h->stream));
+    FM_HIP_TRY(&h->err, hipGetLastError());
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[1], h->stream));
     if ((rc = run_layers(h, n))) return rc;
-    YH(h, hipEventRecord(h->ev[2], h->stream));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[2], h->stream));
     if ((rc = run_decode(h, n, confidence))) return rc;
-    YH(h, hipEventRecord(h->ev[3], h->stream));
+    FM_HIP_TRY(&h->err, hipEventRecord(h->ev[3], h->stream));
     h->last_n = n;
     if ((rc = collect(h, n, cand, cap, counts))) return rc;
     read_ms(h, 0, 3);
@@ -826,15 +728,15 @@ extern "C" {
 
 int fm_yolo_detect_frames(fm_yolo* h, const uint8_t* frames, int n, int H, int W, int on_device, int roi_w,
                           float confidence, float* cand, int cap, int32_t* counts, int* roi_h_out) {
-    if (!frames) return h ? yfail(h, FM_EINVAL, "null frames") : FM_EINVAL;
+    if (!frames) return h ? fm::failf(&h->err, FM_EINVAL, "null frames") : FM_EINVAL;
     return detect_impl(h, frames, nullptr, n, H, W, on_device, roi_w, confidence, cand, cap, counts, roi_h_out);
 }
 
 int fm_yolo_detect_frame_list(fm_yolo* h, const uint8_t* const* frames, int n, int H, int W, int roi_w,
                               float confidence, float* cand, int cap, int32_t* counts, int* roi_h_out) {
-    if (!frames) return h ? yfail(h, FM_EINVAL, "null frame list") : FM_EINVAL;
+    if (!frames) return h ? fm::failf(&h->err, FM_EINVAL, "null frame list") : FM_EINVAL;
     for (int i = 0; i < n; i++)
-        if (!frames[i]) return yfail(h, FM_EINVAL, "frame %d: null address", i);
+        if (!frames[i]) return fm::failf(&h->err, FM_EINVAL, "frame %d: null address", i);
     return detect_impl(h, nullptr, frames, n, H, W, 1, roi_w, confidence, cand, cap, counts, roi_h_out);
 }
 

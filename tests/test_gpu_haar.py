@@ -483,3 +483,36 @@ def test_cascade_on_engine_frames_left_in_hbm():
         eng.frame_device_ptr(T, 0)  # past the batch
     eng.close()
     det.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _geometry_case(seed, W, H):
+    """(raw frame, the restatement's detections on its 300-wide ROI) with the cascade of the test below"""
+    cs = make_cascade(1, tight=0.38, depth=2, tilted=True)
+    raw = _raw_frame(seed, W, H)
+    roi = oracle.resize_area_bgr(raw, 300) if W != 300 else raw
+    return raw, haar.detect_multiscale(cs, roi, 1.1, 3)
+
+
+def test_one_detector_across_changing_geometry():
+    """One CascadeClassifier through every resize path in turn -- the general path twice with other tap tables,
+    exact 2x, identity, and the first geometry again -- then frame lists of 2 and of 4 addresses (the list
+    staging grows): the detector's ROI stage keeps its tables and buffers between calls, and each call must
+    still give the detections of the restatement."""
+    import torch
+    det = CascadeClassifier(make_cascade(1, tight=0.38, depth=2, tilted=True))
+    for W, H in [(640, 360), (450, 254), (600, 338), (300, 169), (640, 360)]:
+        cases = [_geometry_case(s, W, H) for s in range(3)]
+        got = det.detect_frames(np.stack([c[0] for c in cases]), 300, 1.1, 3)
+        for i, (_, ref) in enumerate(cases):
+            assert [tuple(r) for r in got[i].tolist()] == ref, (W, i)
+    W, H = 640, 360
+    cases = [_geometry_case(s, W, H) for s in range(4)]
+    ring = torch.from_numpy(np.stack([c[0] for c in cases])).to("cuda:0")
+    torch.cuda.synchronize()
+    for order in [(1, 0), (3, 1, 0, 2)]:
+        got = det.detect_frame_list([ring[k].data_ptr() for k in order], H, W, 300, 1.1, 3)
+        assert len(got) == len(order)
+        for i, k in enumerate(order):
+            assert [tuple(r) for r in got[i].tolist()] == cases[k][1], (order, i)
+    det.close()

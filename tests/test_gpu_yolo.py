@@ -342,3 +342,25 @@ def test_create_destroy_and_limits():
     det.close()
     print(f"a 416 x 416 detector for 8 frames held {held} bytes")
     assert held > 8 * 3 * 416 * 416 * 4 and torch.cuda.mem_get_info()[0] >= free0 - (2 << 20)
+
+
+def test_one_detector_across_changing_geometry():
+    """One YoloDetector through every resize path of its ROI stage in turn -- general, general with other tap
+    tables, exact 2x, identity, the first geometry again -- from host frames, then a frame list at the last
+    size: the network's input blob is bit-equal to the restatement after every call."""
+    import torch
+    net = 64
+    det, _, _ = _net(3, [yr.conv_cfg(4, 1, 1, "linear", bn=0)], net, net, seed=0, max_frames=2)
+    for W, H in [(640, 480), (450, 300), (600, 400), (300, 200), (640, 480)]:
+        frames = yr.make_frames(2, W, H, seed=W + net)
+        want = np.stack([yr.blob(f, net, net)[0] for f in frames])
+        det.forward(np.zeros_like(want))  # (so that a call that did nothing cannot pass on the last one's blob)
+        rows, rh = det.candidates(frames)
+        assert rh == int(H * (300 / W)) and [len(r) for r in rows] == [0, 0]
+        assert np.array_equal(det.layer_output(-1, 2), want), (W, H)
+    singles = [torch.from_numpy(frames[1]).cuda(), torch.from_numpy(frames[0]).cuda()]
+    torch.cuda.synchronize()
+    det.forward(np.zeros_like(want))
+    det.candidates_frame_list([singles[1].data_ptr(), singles[0].data_ptr()], H, W)
+    assert np.array_equal(det.layer_output(-1, 2), want)
+    det.close()
