@@ -41,7 +41,7 @@ EXPORTED = (
     "fm_yolo_create", "fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_layer_shape", "fm_yolo_detect_frames",
     "fm_yolo_detect_frame_list", "fm_yolo_forward", "fm_yolo_decode", "fm_yolo_layer_output",
     "fm_yolo_route_in_place", "fm_yolo_last_ms",
-    "fm_plan",
+    "fm_plan", "fm_read_threshold_bits",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -132,6 +132,7 @@ def load() -> C.CDLL:
     L.fm_get_counts.argtypes = [vp, vp]
     L.fm_get_contours.argtypes = [vp, i32, i32, vp, i32]
     L.fm_read_mask.argtypes = [vp, i32, i32, vp]
+    L.fm_read_threshold_bits.argtypes = [vp, i32, i32, vp]
     L.fm_read_plane.argtypes = [vp, i32, i32, i32, vp]
     L.fm_read_background.argtypes = [vp, i32, vp]
     L.fm_write_background.argtypes = [vp, i32, vp]
@@ -618,6 +619,14 @@ class MotionEngine:
     def mask(self, frame: int, stream: int) -> np.ndarray:
         out = np.empty(self.work_shape, np.uint8)
         self._check(self._L.fm_read_mask(self._h, frame, stream, _ptr(out)))
+        return out
+
+    def threshold_bits(self, frame: int, stream: int) -> np.ndarray:
+        """Diagnostics: the undilated threshold bits as the tile pixel paths store them, uint64 [ntiles][64]:
+        tile (raster order), column word c, bit r = pixel (row r, column c) of the 64 x 64 tile."""
+        h, w = self.work_shape
+        out = np.empty((((h + 63) // 64) * ((w + 63) // 64), 64), np.uint64)
+        self._check(self._L.fm_read_threshold_bits(self._h, frame, stream, _ptr(out)))
         return out
 
     def read_frame(self, frame: int, stream: int) -> np.ndarray:

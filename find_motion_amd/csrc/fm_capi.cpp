@@ -920,7 +920,7 @@ FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool a
     fa.dbits = B.d_dbits;
     fa.tiles = B.d_tiles;
     fa.tflag = B.d_tflag;
-    fa.tflag_waves = c->use_pix ? 8 : 1;
+    fa.tflag_waves = (c->use_small || c->use_wide) ? 8 : 1;
     fa.candf = B.d_candf;
     fa.clist = B.d_clist;
     fa.rlist = B.d_rlist;
@@ -961,7 +961,8 @@ FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool a
 }
 
 // The batch's pixel kernels on the pixel stream (the background recurrence is ordered here).  The counters
-// are zeroed by k_pix (k_regions on the k_fused path), the tile flags cleared by k_counts.
+// are zeroed by k_pix (k_regions on the k_fused path); the tile flags of the 64 x 64 tile kernels' batches are
+// written on the contour stream (k_tile_flags, run_contours), k_fused's are cleared by k_counts.
 int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
     hipStream_t ps = c->stream;
     const int n = fa.T;
@@ -1015,6 +1016,12 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
     const size_t F = (size_t)fa.T * fa.S;
     FM_HIP_TRY(c, hipEventRecord(B.ev_pix, ps));
     FM_HIP_TRY(c, hipStreamWaitEvent(cs, B.ev_pix, 0));
+    // The 64 x 64 tile pixel kernels (launch_pix) store threshold bits only: every frame's tile flags, the init
+    // frame's launch included, come from those bits here, at the head of the chain and ahead of the labelling gate.
+    // (The small-image and wide-Gaussian scans and k_fused write their own.)  Timed by events, like k_regions
+    // (FM_FLAG_PROFILE; never in the pixel-only mode on a contour stream).
+    if (c->use_pix && !c->use_small && !c->use_wide)
+        FM_HIP_TRY(c, c->timer.timed(cs, "tile_flags", [&](uint64_t*, uint64_t*) { return launch_tile_flags(cs, fa); }, false));
     if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
         FusedArgs fc = fa;
         // stamped by the dev build only; FM_FLAG_PROFILE: events around it (a contour stream: never in the pixel-only mode)
@@ -1447,6 +1454,19 @@ int fm_read_mask(fm_ctx* c, int frame, int stream, uint8_t* out) {
         FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_mask + f * c->work_plane, c->work_plane, hipMemcpyDeviceToHost, st));
     }
     FM_HIP_TRY(c, hipStreamSynchronize(st));
+    return FM_OK;
+}
+
+int fm_read_threshold_bits(fm_ctx* c, int frame, int stream, uint64_t* out) {
+    if (!c || !out) return failf(c, FM_EINVAL, "null argument");
+    if (!c->use_pix) return failf(c, FM_ESTATE, "this pixel path keeps no threshold bits");
+    if (int rc = check_frame(c, frame, stream, true)) return rc;
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    const BatchSlot& B = c->slots[c->ready_slot];
+    const size_t f = (size_t)frame * c->p.n_streams + stream;
+    const size_t words = (size_t)c->ntiles * 64;
+    FM_HIP_TRY(c, hipMemcpyAsync(out, B.d_bits + f * words, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->aux_stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
     return FM_OK;
 }
 

@@ -930,8 +930,9 @@ __device__ int tile_ccl(const FusedArgs& a, size_t f, int ti, int ln, uint64_t m
 // candidate: the tile's dilated mask can be non-empty.  With threshold bits
 // (dilate) that is: its own bits, or a neighbour's bits within 2 px of the
 // shared edge or corner; with already dilated bits, its own bits.
-// the tile's FLAG_* bits: one word per tile (k_fused), or one per wave of the pixel
-// kernel's workgroup (k_pix writes them with plain stores, no atomics), ORed here
+// the tile's FLAG_* bits: one word per tile (k_fused's atomicOr; k_tile_flags for the 64 x 64 pixel
+// kernels), or eight ORed here (the small-image and wide-Gaussian paths, which clear all eight and
+// atomicOr into the first)
 __device__ __forceinline__ uint32_t tile_flags(const FusedArgs& a, size_t f, int ti) {
     if (a.tflag_waves == 1) return a.tflag[f * a.ntiles + ti];
     const uint4* q = reinterpret_cast<const uint4*>(a.tflag + (f * a.ntiles + ti) * 8);
@@ -955,6 +956,41 @@ __device__ __forceinline__ bool is_candidate_lds(const int* fl, const FusedArgs&
     if (d && l) m |= (uint32_t)fl[ti + ntx - 1] & FLAG_TR;
     if (d && r) m |= (uint32_t)fl[ti + ntx + 1] & FLAG_TL;
     return m != 0;
+}
+
+// The FLAG_* word of every tile-frame of a batch whose pixel stage ran the 64 x 64 tile kernels (k_pix5,
+// k_pixw, k_pix<K>), from the column-major threshold bits they stored.  A wave takes TFN consecutive
+// tile-frames: lane = column, one 64-bit word per lane and tile-frame (512 contiguous bytes), all TFN loads
+// issued before the first ballot; lane i then writes a.tflag[first + i] (tflag_waves == 1).  Bits past the
+// image are zero (the pixel kernels' tbmask), so partial tiles need no masking.  Plain loads and stores,
+// every word rewritten every batch.  The pixel kernels formed these flags themselves until the flags moved
+// here: three ballots, the selects and a store in every wave of every frame of a barrier-locked loop whose
+// instruction stream is what limits it, against one free-running wave per TFN tile-frames here.
+// (One tile-frame per wave -- 130,560 waves of one load each per 1080p batch -- took 22 us alone but 215 us
+// beside the next batch's pixel launch, and at 8 streams its 130,560 four-wave workgroups went through the
+// dispatcher between the pixel kernel's own: configs[2] fell by 1.2 %, profiles/tile_flags_ab.txt.)
+constexpr int TFW = 4;  // waves per workgroup
+constexpr int TFN = 8;  // tile-frames per wave
+__global__ __launch_bounds__(64 * TFW) void k_tile_flags(FusedArgs a) {
+    const int ln = threadIdx.x & 63;
+    const size_t tf0 = ((size_t)blockIdx.x * TFW + (threadIdx.x >> 6)) * TFN;
+    const size_t ntf = (size_t)a.T * a.S * a.ntiles;
+    uint64_t col[TFN];
+#pragma unroll
+    for (int i = 0; i < TFN; i++) col[i] = a.bits[min(tf0 + i, ntf - 1) * 64 + ln];  // (clamped: unconditional)
+    uint32_t mine = 0;
+#pragma unroll
+    for (int i = 0; i < TFN; i++) {
+        const uint64_t orr = __builtin_amdgcn_ballot_w64(col[i] != 0);
+        const uint64_t top = __builtin_amdgcn_ballot_w64((col[i] & 3ull) != 0);
+        const uint64_t bot = __builtin_amdgcn_ballot_w64((col[i] >> 62) != 0);
+        uint32_t fl = 0;
+        if (orr) fl = FLAG_ANY | ((orr & 3ull) ? FLAG_L : 0u) | ((orr >> 62) ? FLAG_R : 0u);
+        if (top) fl |= FLAG_T | ((top & 3ull) ? FLAG_TL : 0u) | ((top >> 62) ? FLAG_TR : 0u);
+        if (bot) fl |= FLAG_B | ((bot & 3ull) ? FLAG_BL : 0u) | ((bot >> 62) ? FLAG_BR : 0u);
+        if (ln == i) mine = fl;
+    }
+    if (ln < TFN && tf0 + ln < ntf) a.tflag[tf0 + ln] = mine;
 }
 
 // one workgroup per frame: candidate list, empty-tile regions (4-connected: two
@@ -1590,6 +1626,14 @@ hipError_t launch_contour_area(hipStream_t st, const uint64_t* dbits, const uint
     if (n <= 0) return hipSuccess;
     const cc::AreaMask m{dbits, candf, mask, ntiles, ntx, h, w};
     hipLaunchKernelGGL(cc::k_contour_area, dim3((n + 255) / 256), dim3(256), 0, st, m, jobs, n, area2);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_flags(hipStream_t st, const FusedArgs& a) {
+    if (a.tflag_waves != 1) return hipErrorInvalidValue;
+    const size_t ntf = (size_t)a.T * a.S * a.ntiles, per_wg = (size_t)cc::TFW * cc::TFN;
+    if (ntf == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cc::k_tile_flags, dim3((unsigned)((ntf + per_wg - 1) / per_wg)), dim3(64 * cc::TFW), 0, st, a);
     return hipGetLastError();
 }
 

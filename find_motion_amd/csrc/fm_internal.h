@@ -109,7 +109,7 @@ struct TileRec {
                                       // component ordinal | fg << 15
 };
 
-// per-tile threshold-bit flags written by the pixel kernel (decide which tiles the
+// per-tile threshold-bit flags written by the pixel stage or by k_tile_flags (decide which tiles the
 // 5x5 dilation can make non-empty: the tile itself or a neighbour's 2-px margin)
 enum : uint32_t {
     FLAG_ANY = 1u, FLAG_L = 2u, FLAG_R = 4u, FLAG_T = 8u, FLAG_B = 16u,
@@ -130,7 +130,9 @@ struct FusedArgs {
                                  // pixel kernel dilates itself, i.e. the generic-k k_fused path)
     TileRec* tiles;              // [F][ntiles]
     uint32_t* tflag;             // [F][ntiles][tflag_waves] FLAG_* bits: where the tile has threshold bits (dilated
-                                 // bits on the k_fused path, which sets FLAG_ANY only)
+                                 // bits on the k_fused path, which sets FLAG_ANY only).  Written by k_fused,
+                                 // by the small-image / wide-Gaussian scans, or, for the 64 x 64 tile pixel
+                                 // kernels, by k_tile_flags on the contour stream from `bits`
     uint8_t* candf;              // [F][ntiles] 1: the tile's dilated mask may be non-empty (labelled)
     int32_t* clist;              // [F][ntiles] candidate tiles of each frame
     int32_t* rlist;              // [F][ntiles] representative tile of each empty-tile region
@@ -150,7 +152,8 @@ struct FusedArgs {
     int t_begin, t_end;          // k_pix: frames of the batch this launch processes
     int ntx, nty, ntiles, nnodes, cap, cvt_simd;
     int nquota;                  // nodes per frame quota
-    int tflag_waves;             // words per tile-frame in tflag: 1 (k_fused, atomicOr) or 8 (k_pix, one per wave)
+    int tflag_waves;             // words per tile-frame in tflag: 1 (k_fused's atomicOr, k_tile_flags) or 8 (the
+                                 // small-image and wide-Gaussian scans)
     int dbg_skip;                // profiling-only stage ablation (FM_DEBUG_SKIP); 0 in normal use
     uint64_t* dbg_ts;            // profiling-only s_memtime stamps [F][ntiles][16] (FM_TS); nullptr in normal use
     uint64_t* dbg_pts;           // profiling-only k_pix workgroup stamps [S][ntiles][4] (FM_PTS); nullptr in normal use
@@ -233,6 +236,9 @@ bool wide_supported(int ksize, const int32_t* coef);
 int wide_lds_bytes(int ksize, const int32_t* coef);
 size_t wide_scratch_bytes(int w, int nty, size_t frames);
 hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks_blur, uint64_t* ks_scan);
+// a.tflag (one word per tile-frame) of all a.T * a.S frames from a.bits: after the 64 x 64 tile pixel kernels
+// (launch_pix), ahead of either contour pass below
+hipError_t launch_tile_flags(hipStream_t st, const FusedArgs& a);
 // CCL over tile summaries; dilate = true: a.bits are threshold rows to dilate into a.dbits
 // gate_wait / gate_done (optional): the labelling kernel waits for gate_wait (the previous batch's
 // labelling) and gate_done is recorded after it, so that one batch's labelling runs at a time

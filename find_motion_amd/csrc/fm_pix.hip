@@ -37,7 +37,6 @@ constexpr int kPixWPE = 4;
 constexpr int NT = 512;         // threads
 constexpr int NW = NT / 64;     // waves; wave w owns tile rows [8w, 8w + 8)
 constexpr int RPWV = TS / NW;   // rows per wave in the chain stage
-static_assert(NW == 8, "tflag holds 8 words per tile (FusedArgs::tflag_waves)");
 
 __host__ __device__ constexpr int a16(int v) { return (v + 15) & ~15; }
 
@@ -285,7 +284,7 @@ template <int KC, bool PLANES, bool INIT, bool KEEP, bool TAIL>
 __device__ __forceinline__ void chain_rows(const FusedArgs& a, const uint16_t* Hs, const double* atab, const Geo& g,
                                            double (&bg)[RPWV],
                                            int wv, int ln, int x0, int y0, size_t f, const ChainCtx& cc,
-                                           bool init, uint32_t& colbits, uint32_t& flags) {
+                                           bool init, uint32_t& colbits) {
     constexpr int R = KC >> 1;
     constexpr int NV = RPWV + 2 * R;       // H rows feeding the wave's 8 outputs
     constexpr int NP = (NV + 1) / 2;       // u16 pairs
@@ -349,19 +348,10 @@ __device__ __forceinline__ void chain_rows(const FusedArgs& a, const uint16_t* H
             a.planes[2 * (size_t)a.T * a.S * plane + f * plane + li] = (uint8_t)(r - bias);
         }
     });
-    // out-of-image pixels are background for the contour pass
+    // out-of-image pixels are background for the contour pass (and for k_tile_flags, which reads
+    // the tile's FLAG_* bits off these column words)
     tb &= cc.tbmask;
     colbits = tb;
-    // where the tile has threshold bits (decides the contour pass's candidate tiles):
-    // any, within 2 px of the left / right edge, and for the tile's first / last two rows
-    const uint64_t orr = __builtin_amdgcn_ballot_w64(tb != 0);
-    const uint64_t top = wv == 0 ? __builtin_amdgcn_ballot_w64((tb & 3u) != 0) : 0ull;
-    const uint64_t bot = wv == NW - 1 ? __builtin_amdgcn_ballot_w64((tb & (3u << (RPWV - 2))) != 0) : 0ull;
-    uint32_t fl = 0;
-    if (orr) fl = FLAG_ANY | ((orr & 3ull) ? FLAG_L : 0u) | ((orr >> 62) ? FLAG_R : 0u);
-    if (wv == 0 && top) fl |= FLAG_T | ((top & 3ull) ? FLAG_TL : 0u) | ((top >> 62) ? FLAG_TR : 0u);
-    if (wv == NW - 1 && bot) fl |= FLAG_B | ((bot & 3ull) ? FLAG_BL : 0u) | ((bot >> 62) ? FLAG_BR : 0u);
-    flags = fl;
 }
 
 template <int KC, bool PLANES, bool INIT>
@@ -595,7 +585,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu((!PLANES && 
 
             // ---- vertical taps + chain for the wave's 8 rows; threshold bits by ballot
             uint32_t colbits = 0;
-            uint32_t fl = 0;
             // launder the per-tile uniforms each frame: otherwise LICM hoists dozens of
             // per-row exec masks out of the frame loop and they spill
             ChainCtx ccf = ccv;
@@ -605,13 +594,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu((!PLANES && 
             asm volatile("" : "+v"(ccf.keep_lo), "+v"(ccf.keep_hi));
             if (!(skip & 2))
                 chain_rows<KC, PLANES, INIT, KEEP, TAIL>(a, Hs + b * (g.H_bytes / 2), atab, g, bg, wvf, ln, x0f, y0f, f, ccf,
-                                                         init0 && t == t0, colbits, fl);
+                                                         init0 && t == t0, colbits);
             // column-major bit tile: word c of the tile = column c, bit r = row r; this wave
             // owns byte wv of every column word
             reinterpret_cast<uint8_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 8 + wv] = (uint8_t)colbits;
-            // this wave's flag word, a plain store every frame (an atomic would sit in vmcnt
-            // until the next frame's wait for the raw prefetch)
-            if (ln == 0) a.tflag[(f * a.ntiles + ti) * NW + wv] = fl;
 
             if (t + 1 < t1 && !(skip & 1))
                 gray_stage(raw + (b ^ 1) * g.raw_bytes, Hs + (b ^ 1) * (g.H_bytes / 2), f + S);
@@ -714,8 +700,7 @@ template <int KC> constexpr uint32_t tapv2(int j, int i) {  // chain pair i of o
 // chain_rows over H row pairs with even-aligned pair windows: output row j's window starts on an
 // even H row, absorbing a zero tap (outside the kernel, or one of OpenCV's zero end taps) on the
 // side the row parity needs, so no pair is rebuilt with v_alignbit
-// wv: the wave within its workgroup = its 8-row slice of the 64-row tile (flag rows: FLAG_T* from slice 0,
-// FLAG_B* from slice 7)
+// wv: the wave within its workgroup = its 8-row slice of the 64-row tile
 // pairs the chain of a RW-row wave reads
 template <int KC, int RW> constexpr int np_rows() {
     int m = 0;
@@ -778,31 +763,25 @@ __device__ __forceinline__ double chain_bg(const FusedArgs& a, double b, double 
     }
     return nb;
 }
-// The wave's byte (or u16) of the tile's column words and its flag word
-template <int RW, int NWT, int BAND>
-__device__ __forceinline__ void chain_flags(uint32_t tb, uint32_t tb2, int wv, const ChainCtx& cc, uint32_t& colbits,
-                                            uint32_t& flags) {
+// The wave's byte (or u16) of the tile's column words; columns and rows past the image hold zero bits, so the
+// tile's FLAG_* bits are a function of the stored words alone (k_tile_flags, fm_ccl.hip, forms them once per
+// tile-frame on the contour stream: no ballots, selects or flag store in the frame loop)
+template <int RW>
+__device__ __forceinline__ void chain_flags(uint32_t tb, uint32_t tb2, const ChainCtx& cc, uint32_t& colbits) {
     if constexpr (RW > 8) tb |= tb2 << 8;
-    tb &= cc.tbmask;
-    colbits = tb;
-    const int ws = BAND == NWT ? wv : wv % NWT;  // the wave's slice of its contour tile
-    const uint64_t orr = __builtin_amdgcn_ballot_w64(tb != 0);
-    const uint64_t top = ws == 0 ? __builtin_amdgcn_ballot_w64((tb & 3u) != 0) : 0ull;
-    const uint64_t bot = ws == NWT - 1 ? __builtin_amdgcn_ballot_w64((tb & (3u << (RW - 2))) != 0) : 0ull;
-    uint32_t fl = 0;
-    if (orr) fl = FLAG_ANY | ((orr & 3ull) ? FLAG_L : 0u) | ((orr >> 62) ? FLAG_R : 0u);
-    if (ws == 0 && top) fl |= FLAG_T | ((top & 3ull) ? FLAG_TL : 0u) | ((top >> 62) ? FLAG_TR : 0u);
-    if (ws == NWT - 1 && bot) fl |= FLAG_B | ((bot & 3ull) ? FLAG_BL : 0u) | ((bot >> 62) ? FLAG_BR : 0u);
-    flags = fl;
+    colbits = tb & cc.tbmask;
+    // pinned here: with no ballot reading them, the rows' threshold bits are otherwise sunk to the store at the
+    // end of the frame, and the rows' old backgrounds live on beside the new ones until then (k_pix5's 8-wave
+    // loop: 108 instead of 92 VGPRs and eight 64-bit moves per frame)
+    asm volatile("" : "+v"(colbits));
 }
 
-// RW: rows per wave (8, or 16 for k_pix5's 4-wave tiles and k_pixw's 128-row bands), NWT: waves per 64-row
-// contour tile, BAND: waves of the workgroup (wv counts the band's waves; wv % NWT is the tile's slice)
-template <int KC, bool KEEP, bool TAIL, bool SDWA, int RW = RPWV, int NWT = NW, int BAND = NWT>
+// RW: rows per wave (8, or 16 for k_pix5's 4-wave tiles and k_pixw's 128-row bands); wv counts the workgroup's
+// waves (a band's 8 waves of 16 rows span two contour tiles).  colbits: the wave's rows of its column word
+template <int KC, bool KEEP, bool TAIL, bool SDWA, int RW = RPWV>
 __device__ __forceinline__ void chain_rows_w(const FusedArgs& a, const uint32_t* Hp, const double* atab, double (&bg)[RW],
-                                             int wv, int ln, int x0, int y0, const ChainCtx& cc, uint32_t& colbits,
-                                             uint32_t& flags) {
-    static_assert(RW * NWT == TS && (RW == 8 || RW == 16), "rows per wave");
+                                             int wv, int ln, int x0, int y0, const ChainCtx& cc, uint32_t& colbits) {
+    static_assert(RW == 8 || RW == 16, "rows per wave");
     uint32_t P[np_rows<KC, RW>()];
     chain_pairs<RW>(P, Hp, wv, ln);
     const int w = a.w;
@@ -819,7 +798,7 @@ __device__ __forceinline__ void chain_rows_w(const FusedArgs& a, const uint32_t*
         const double bl = chain_tab<SDWA>(atab, tix);
         bg[j] = chain_bg<TAIL, RW, j>(a, b, beta, bl, wv, ln, x0, y0, w);
     });
-    chain_flags<RW, NWT, BAND>(tb, tb2, wv, cc, colbits, flags);
+    chain_flags<RW>(tb, tb2, cc, colbits);
 }
 
 // Horizontal taps with the byte window folded into the constants: output k of a quad sums its
@@ -1133,7 +1112,7 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             const int b = (t - t0) & 1;
             const size_t f = (size_t)t * S + s;
             lds_barrier();
-            uint32_t colbits = 0, fl = 0;
+            uint32_t colbits = 0;
             ChainCtx ccf = cc;
             ccf.rowvalid = __builtin_amdgcn_readfirstlane(ccf.rowvalid);
             int x0f = __builtin_amdgcn_readfirstlane(x0), y0f = __builtin_amdgcn_readfirstlane(y0), wvf = wv, var = var0;
@@ -1149,7 +1128,7 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
                 // covers its own: behind the barrier it issues every read whose address it knows (the chain's
                 // pairs, the full tap round's gray dwords); the table reads, whose addresses are the blur values,
                 // go out four rows at a time, with one gray row's taps between a group's reads and the rows that
-                // use them.  One basic block up to the flags, pinned in this order (the scheduler would otherwise
+                // use them.  One basic block up to the partial tap round, pinned in this order (the scheduler would otherwise
                 // sink the table reads below the taps): chain(t), taps(t+1) and gray(t+2) are independent, and the
                 // taps run past the batch's last frame too (into an H buffer nothing reads), like gray and the loads.
                 static_assert(G::HJ == 2 && RW == 8, "one full tap round, then wave 0's partial one");
@@ -1191,29 +1170,26 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
                 tap_store(Hn, 0, hh, hk);
                 __builtin_amdgcn_sched_barrier(0);
                 chain4(std::integral_constant<int, 4>{});
-                chain_flags<RW, NWB, NWB>(tb, tb2, wvf, ccf, colbits, fl);
+                chain_flags<RW>(tb, tb2, ccf, colbits);
                 if (wv < G::HLASTW) tap_job(edge, gn, Hn, 1);  // wave-uniform: the partial last round
             } else {
                 if (!TAIL || var == 0)
-                    chain_rows_w<KC, KEEP, false, true, RW, NWB>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
+                    chain_rows_w<KC, KEEP, false, true, RW>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits);
                 else
-                    chain_rows_w<KC, KEEP, true, true, RW, NWB>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
+                    chain_rows_w<KC, KEEP, true, true, RW>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits);
                 if (t + 1 < t1) tap_stage(edge, gray + (b ^ 1) * G::GBUF, Hs + (b ^ 1) * G::HBUF);
             }
             // unconditional like the loads (past the batch's end it fills a buffer nothing reads):
             // a skipped gray stage leaves the loads unwaited on that path, and the wait pass then
             // makes every frame wait for the stores below before the next loads
             gray_stage(gray + b * G::GBUF);
-            // the frame's bits and flag word, stored after gray(t+2) consumed the loads and before
-            // the next ones: vmcnt counts stores and loads in issue order, so stores issued after
-            // the prefetch would be waited for with it
-            if constexpr (RW == 8) {
+            // the frame's bits, stored after gray(t+2) consumed the loads and before the next ones:
+            // vmcnt counts stores and loads in issue order, so a store issued after the prefetch
+            // would be waited for with it
+            if constexpr (RW == 8)
                 reinterpret_cast<uint8_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 8 + wv] = (uint8_t)colbits;
-                if (ln == 0) a.tflag[(f * a.ntiles + ti) * NW + wv] = fl;
-            } else {  // bytes 2wv, 2wv + 1 of the column word; flag words 2wv (this wave's) and 2wv + 1 (none)
+            else  // bytes 2wv, 2wv + 1 of the column word
                 reinterpret_cast<uint16_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 4 + wv] = (uint16_t)colbits;
-                if (ln == 0) *reinterpret_cast<uint2*>(a.tflag + (f * a.ntiles + ti) * NW + 2 * wv) = make_uint2(fl, 0u);
-            }
             // unconditional (see load): past the batch's last frame it re-reads that frame
             load((size_t)min(t + 3, t1 - 1) * S + s);
         }
@@ -1432,7 +1408,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RW == 16 ? 
         const int b = (t - t0) & 1;
         const size_t f = (size_t)t * S + s;
         lds_barrier();
-        uint32_t colbits = 0, fl = 0;
+        uint32_t colbits = 0;
         ChainCtx ccf = cc;
         ccf.rowvalid = __builtin_amdgcn_readfirstlane(ccf.rowvalid);
         int x0f = __builtin_amdgcn_readfirstlane(x0), y0f = __builtin_amdgcn_readfirstlane(y0), wvf = wv, var = var0;
@@ -1441,20 +1417,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RW == 16 ? 
         asm volatile("" : "+v"(ccf.keep_lo), "+v"(ccf.keep_hi));
         if constexpr (RW > 8) asm volatile("" : "+v"(ccf.keep_2), "+v"(ccf.keep_3));
         const uint32_t* Hb = Hs + b * G::HBUF;
-        constexpr int NWT = TS / RW;  // waves per contour tile
         if (!TAIL || var == 0)
-            chain_rows_w<KC, KEEP, false, true, RW, NWT, 8>(a, Hb, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
+            chain_rows_w<KC, KEEP, false, true, RW>(a, Hb, atab, bg, wvf, ln, x0f, y0f, ccf, colbits);
         else
-            chain_rows_w<KC, KEEP, true, true, RW, NWT, 8>(a, Hb, atab, bg, wvf, ln, x0f, y0f, ccf, colbits, fl);
+            chain_rows_w<KC, KEEP, true, true, RW>(a, Hb, atab, bg, wvf, ln, x0f, y0f, ccf, colbits);
         if (t + 1 < t1) tap_stage(gray + (b ^ 1) * G::GBUF, Hs + (b ^ 1) * G::HBUF);
         gray_stage(gray + b * G::GBUF);
         if constexpr (RW == 8) {
             reinterpret_cast<uint8_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 8 + wv] = (uint8_t)colbits;
-            if (ln == 0) a.tflag[(f * a.ntiles + ti) * NW + wv] = fl;
-        } else if (tile_ok) {  // bytes 2 (wv & 3), +1 of the column word; flag words 2 (wv & 3) and the next (none)
+        } else if (tile_ok) {  // bytes 2 (wv & 3), +1 of the column word
             const int ws = wv & 3;
             reinterpret_cast<uint16_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 4 + ws] = (uint16_t)colbits;
-            if (ln == 0) *reinterpret_cast<uint2*>(a.tflag + (f * a.ntiles + ti) * NW + 2 * ws) = make_uint2(fl, 0u);
         }
         load((size_t)min(t + 3, t1 - 1) * S + s);
     }

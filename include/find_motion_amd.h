@@ -197,6 +197,12 @@ int fm_last_ccl_stats(const fm_ctx* ctx, int32_t* shared_nodes, int32_t* heavy_t
 /* Dilated threshold mask (VideoFrame.thresh after find_contours, fm.py:266), h*w bytes. */
 int fm_read_mask(fm_ctx* ctx, int frame, int stream, uint8_t* out);
 
+/* Diagnostics: the undilated threshold bits (frame_delta > threshold, fm.py:257) as the tile pixel paths
+ * store them: for each 64 x 64 tile of the work image in raster order, 64 column words (word c, bit r =
+ * pixel (row r, column c) of the tile), ntiles * 64 words in all; bits past the image are zero.
+ * FM_ESTATE on the paths that keep no threshold bits (Gaussian sizes the tile kernels do not take). */
+int fm_read_threshold_bits(fm_ctx* ctx, int frame, int stream, uint64_t* out);
+
 /* gray / blur / frame_delta planes (needs FM_FLAG_KEEP_PLANES), h*w bytes; FM_PLANE_SMALL: the
  * resized BGR frame, h*w*3 bytes (FM_ESTATE when box_size = frame width). */
 int fm_read_plane(fm_ctx* ctx, int plane, int frame, int stream, uint8_t* out);
