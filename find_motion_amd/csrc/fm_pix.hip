@@ -82,14 +82,18 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 
 // BGR2GRAY of 4 consecutive pixels packed in 3 dwords (B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3):
 // (1868 B + 9617 G + 4899 R + 8192) >> 14 computed with all constants x4, so that
 // gray is byte 2 of the sum (< 2^24) and two v_perm gather the four results.
+// I8: gray - 128 as signed bytes (the matrix cores' i8 operand) -- 128 << 16 more in the rounding literal flips
+// bit 7 of byte 2 (the carry goes to byte 3, which is not gathered): no instruction more.
+template <bool I8 = false>
 __device__ __forceinline__ uint32_t gray4(uint32_t d0, uint32_t d1, uint32_t d2) {
     const u16x2_t cbg = __builtin_bit_cast(u16x2_t, (4u * 1868u) | ((4u * 9617u) << 16));
-    constexpr uint32_t CR = 4u * 4899u, RND = 4u * 8192u;
+    constexpr uint32_t CR = 4u * 4899u, RND = 4u * 8192u + (I8 ? 128u << 16 : 0u);
     const uint32_t p0 = __builtin_amdgcn_perm(d0, d0, 0x0C010C00u);
     const uint32_t p1 = __builtin_amdgcn_perm(d1, d0, 0x0C040C03u);
     const uint32_t p2 = __builtin_amdgcn_perm(d1, d1, 0x0C030C02u);
@@ -719,14 +723,16 @@ __device__ __forceinline__ void chain_pairs(uint32_t (&P)[NPR], const uint32_t* 
 }
 // Output row j's vertical taps (+2^15: the blur value is byte 2 of acc), the keep-mask applied, and where the
 // row's blur x alpha lies in the table
-template <int KC, bool KEEP, bool SDWA, int j, int NPR>
+// H16: the pairs hold H / 16 (k_pix5's matrix-core taps, below; every k = 5 tap is a multiple of 16) and the taps
+// here are taken times 16: the same accumulator, 2^15 + sum c H = 2^15 + sum (16 c) (H / 16), in the same instructions.
+template <int KC, bool KEEP, bool SDWA, int j, bool H16 = false, int NPR>
 __device__ __forceinline__ void chain_blur(const uint32_t (&P)[NPR], const ChainCtx& cc, uint32_t& acc, uint32_t& tix) {
     using G = PW<KC>;
     acc = 32768u;
     static_for<G::np(j)>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, P[G::p0(j) + i]),
-                                     __builtin_bit_cast(u16x2_t, tapv2<KC>(j, i)), acc, false);
+                                     __builtin_bit_cast(u16x2_t, tapv2<KC>(j, i) << (H16 ? 4 : 0)), acc, false);
     });
     if (KEEP) {
         const uint32_t kw = j < 4 ? cc.keep_lo : j < 8 ? cc.keep_hi : j < 12 ? cc.keep_2 : cc.keep_3;
@@ -872,6 +878,12 @@ __device__ __forceinline__ uint32_t hs_tap(const uint32_t (&q)[N], const uint32_
 // The chain runs on even-aligned pair windows (chain_rows_w); tap jobs cover 2 H rows x 4 columns and store
 // them as row pairs (one ds_write_b128), which the chain reads back as six dwords instead of twelve u16
 // reads and their merges; the horizontal taps take shifted constants (HS).
+// The 8-wave kernel has no tap jobs: a horizontal 5-tap sum is a product with a banded constant matrix, exact
+// in i32, so H comes from the matrix cores (v_mfma_i32_16x16x32_i8, three 16-row x 16-column blocks a wave and
+// frame): gray is stored as gray - 128 (signed bytes), the taps divided by 16 (all are multiples), the product
+// starts from 128 * 16 = 2048, and the chain takes the result, H / 16, with the vertical taps times 16 -- the
+// same accumulator, bit for bit.  The REFLECT_101 columns are folded into the tap matrix once per tile (see the
+// plans in the kernel).
 template <int NWB_ = 8>
 struct P5G {
     static constexpr int NWB = NWB_;                     // waves of a tile (8 of 8 rows, or 4 of 16 rows)
@@ -886,7 +898,14 @@ struct P5G {
     // gray row stride in LDS (dwords): 24, not GQ = 18, so the four even gray rows a tap-job wave reads start 48
     // dwords apart and their windows fall in disjoint banks: LDS bank conflicts 176.3 M -> 68.2 M per 10-step run
     // (0.49 -> 0.19 per LDS-active cycle), throughput unchanged (round 6, profiles/r06/r06e_gray_stride_ab.txt)
-    static constexpr int GS = FM_P5_GS > GQ ? FM_P5_GS : GQ;
+    // Eight waves (the taps as block products, below): 20.  A wave's ds_read_b64 takes 16 rows x 32 bytes; at 20
+    // dwords the rows start at banks 20 m mod 64 = sixteen different multiples of 4, four banks each, and at 24 rows
+    // m and m + 8 share their banks.  A row's 80 bytes still hold the last column block's 32-byte window (48 .. 79).
+#ifndef FM_P5_GS8
+#define FM_P5_GS8 20
+#endif
+    static constexpr int GS = NWB == 8 ? FM_P5_GS8 : FM_P5_GS > GQ ? FM_P5_GS : GQ;
+    static_assert(GS >= 20 && GS % 2 == 0, "a 32-byte window at byte 48 of an 8-byte aligned row");
     static constexpr int NG = GH * GQ;                   // gray jobs per frame
     // Gray jobs go to waves in whole wave-slots of 64 jobs.  Waves 4..7 lose issue arbitration to waves
     // 0..3 (age order) and set every frame's barrier (FM_PTS phase stamps: waves 0..3 spent ~30 % of
@@ -904,7 +923,14 @@ struct P5G {
     static constexpr int HBUF = (GH + 2) * TS;           // u16; + the pad pair row idle tap jobs store to
     static constexpr int bytes = 2 * GBUF * 4 + 2 * HBUF * 2 + 256 * 8;
     static constexpr int dyn_bytes = bytes - 256 * 8;  // (the table is static LDS)
+    // Eight waves: H as 16-row x 16-column block products.  Wave w owns columns 16 (w & 3) .. + 15 of gray rows
+    // 34 (w >> 2) .. + 33, as three blocks starting MOFF rows into them; the third overlaps the second (its own
+    // rows, the same values stored again), so every wave runs the same three blocks at the same immediate
+    // offsets, every operand row lies inside the gray buffer and no lane is idle.
+    static constexpr int MROWS = GH / 2, MB = 3;
+    static constexpr int moff(int i) { return i == 0 ? 0 : i == 1 ? 16 : MROWS - 16; }
 };
+static_assert(P5G<8>::MROWS % 2 == 0 && P5G<8>::moff(2) % 2 == 0 && P5G<8>::moff(2) <= 32, "whole row pairs, no gap");
 static_assert(P5G<8>::GSLOW >= 0 && 4 * (P5G<8>::GFAST + P5G<8>::GSLOW) >= P5G<8>::GSLOTS, "gray slots");
 static_assert(4 * P5G<4>::GFAST >= P5G<4>::GSLOTS, "gray slots");
 
@@ -995,6 +1021,34 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
         const int hq = (int)(hsrc[i] % G::GS);
         hfix[i] = (x0 == 0 && hq == 0 ? 1u : 0u) | (hq + 1 == vq ? 2u : 0u) | (hq + 2 == vq ? 4u : 0u);
     }
+    // Eight waves: the lane's operand row (bytes into a gray buffer: row l % 16 of the wave's rows, K bytes
+    // 8 (l / 16) .. + 7 of the column block's window, which starts at gray byte 16 cb = column x0 + 16 cb - 4), its
+    // result's place (dwords into an H buffer: row pair 2 (l / 16) of the block, column l % 16) and its 8 bytes of
+    // the banded tap matrix: B[k][n] = c[k - n - 2] / 16, output n of the block over window bytes n + 2 .. n + 6.
+    // REFLECT_101 is linear, so it lives in B: a tap that falls on a column left of 0 or from w on (gray bytes
+    // that are never loaded) is added to the tap of the column it mirrors, which lies in the same window.  Column
+    // sums stay 16, every entry <= 8 (the taps undivided would reach 128 at the mirror's axis neighbour).
+    uint32_t asrc = 0, mdst = 0;
+    long btap = 0;
+    i32x4_t mc0 = {2048, 2048, 2048, 2048};  // the product's C: sum b (gray - 128) + 16 * 128 = H / 16 in [0, 4080]
+    if constexpr (NWB == 8) {
+        static_assert(Taps<5>::c[0] % 16 == 0 && Taps<5>::c[1] % 16 == 0 && Taps<5>::c[2] % 16 == 0, "taps / 16");
+        const int mn = ln & 15, mq = ln >> 4, cb = wv & 3, r0 = (wv >> 2) * G::MROWS;
+        asrc = (uint32_t)((r0 + mn) * G::GS * 4 + 16 * cb + 8 * mq);
+        mdst = (uint32_t)((r0 / 2 + 2 * mq) * TS + 16 * cb + mn);
+        const int bw = w - x0 + 4;  // gray byte of column w
+        uint64_t bt = 0;
+        static_for<5>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            int sb = 16 * cb + mn + 2 + t;                  // the tap's gray byte ...
+            if (x0 == 0 && sb < 4) sb = 8 - sb;             // ... column -1, -2 -> 1, 2
+            else if (sb >= bw) sb = 2 * bw - 2 - sb;        // ... column w, w + 1 -> w - 2, w - 3
+            const int k = sb - 16 * cb - 8 * mq;            // its byte in this lane's K slice
+            bt += (unsigned)k < 8u ? (uint64_t)(Taps<5>::c[t] / 16) << (8 * (k & 7)) : 0ull;
+        });
+        btap = (long)bt;
+        asm volatile("" : "+v"(asrc), "+v"(mdst), "+v"(btap), "+v"(mc0));  // (C held in four registers, not moved in per product)
+    }
 
     // background of the wave's 8 rows x 64 columns -> registers (as k_pix)
     double bg[RW];
@@ -1028,8 +1082,8 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
     };
     if constexpr (NWB != 8) load_bg();
 
-    uint32_t hcs[HS<KC>::NC];
-    hs_consts<KC>(hcs);
+    uint32_t hcs[HS<KC>::NC] = {};
+    if constexpr (NWB != 8) hs_consts<KC>(hcs);
     P5Raw<GJX> rw;
     // Every wave issues every job's load, idle jobs included (they read the frame's first
     // 12 B): a load under a branch makes its registers a phi of the loaded and the old
@@ -1044,8 +1098,27 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
 #pragma unroll
         for (int i = 0; i < GJX; i++) {
             if (i >= gjobs) break;  // wave-uniform
-            gb[gdst[i]] = gray4(rw.v[i].x, rw.v[i].y, rw.v[i].z);
+            gb[gdst[i]] = gray4<NWB == 8>(rw.v[i].x, rw.v[i].y, rw.v[i].z);  // (eight waves: signed bytes)
         }
+    };
+    // Eight waves: block i of the wave in pieces -- the operand read (ds_read_b64), the product, and the lane's four
+    // results (rows 4 (l / 16) .. + 3 of one column = two of the chain's row pairs) packed by one v_perm a pair and
+    // stored by one ds_write2st64_b32.  H / 16 stays as it is: chain_blur<.., H16>.
+    auto mf_read = [&](const uint32_t* gb, auto ic) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        return *reinterpret_cast<const long*>(reinterpret_cast<const uint8_t*>(gb) + asrc + G::moff(i) * G::GS * 4);
+    };
+    auto mf_mul = [&](long av) __attribute__((always_inline)) {
+        return __builtin_amdgcn_mfma_i32_16x16x32_i8(av, btap, mc0, 0, 0, 0);
+    };
+    auto mf_store = [&](uint16_t* Hb, auto ic, i32x4_t d) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        uint32_t* hp = reinterpret_cast<uint32_t*>(Hb) + mdst + G::moff(i) / 2 * TS;
+        hp[0] = __builtin_amdgcn_perm((uint32_t)d.y, (uint32_t)d.x, 0x05040100u);
+        hp[TS] = __builtin_amdgcn_perm((uint32_t)d.w, (uint32_t)d.z, 0x05040100u);
+    };
+    auto mf_stage = [&](const uint32_t* gb, uint16_t* Hb) __attribute__((always_inline)) {
+        static_for<G::MB>([&](auto ic) { mf_store(Hb, ic, mf_mul(mf_read(gb, ic))); });
     };
     // A tap job in pieces (tap_stage runs them in turn; the 8-wave frame body reads first and sums later).
     // edge: the tile holds a REFLECT_101 quad -- a bool, or a std::bool_constant where the kind of tile is compiled in
@@ -1099,7 +1172,8 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
         gray_stage(gray);
         load((size_t)min(t0 + 1, t1 - 1) * S + s);
         __syncthreads();  // atab, gray(t0)
-        tap_stage(edge, gray, Hs);
+        if constexpr (NWB == 8) mf_stage(gray, Hs);
+        else tap_stage(edge, gray, Hs);
         if (t0 + 1 < t1) gray_stage(gray + G::GBUF);
         load((size_t)min(t0 + 2, t1 - 1) * S + s);
 
@@ -1125,14 +1199,17 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
                 const uint32_t* gn = gray + (b ^ 1) * G::GBUF;
                 uint16_t* Hn = Hs + (b ^ 1) * G::HBUF;
                 // Four waves per SIMD, barrier-locked to one phase, cover little of an LDS round trip, so the wave
-                // covers its own: behind the barrier it issues every read whose address it knows (the chain's
-                // pairs, the full tap round's gray dwords); the table reads, whose addresses are the blur values,
-                // go out four rows at a time, with one gray row's taps between a group's reads and the rows that
-                // use them.  One basic block up to the partial tap round, pinned in this order (the scheduler would otherwise
-                // sink the table reads below the taps): chain(t), taps(t+1) and gray(t+2) are independent, and the
-                // taps run past the batch's last frame too (into an H buffer nothing reads), like gray and the loads.
-                static_assert(G::HJ == 2 && RW == 8, "one full tap round, then wave 0's partial one");
-                uint32_t P[np_rows<KC, RW>()], q0[3], q1[3], acc[4], hh[4], hk[4], tb = 0, tb2 = 0;
+                // covers its own: behind the barrier it issues every read whose address it knows (the three blocks'
+                // operand rows, the chain's pairs); the table reads, whose addresses are the blur values, go out four
+                // rows at a time.  The block products go to the matrix pipe first -- a blur4 and a chain4 group run
+                // before anything reads a result -- and the packs and stores stand between the second group's table
+                // reads and the rows that use them.  (The products after the first group's table reads instead: the
+                // launch alone 443 vs 437 us, beside the contour pass the same.)  One basic block, pinned in this order
+                // (the scheduler would otherwise sink the table reads): chain(t), taps(t+1) and gray(t+2) are
+                // independent, and the taps run past the batch's last frame too (into an H buffer nothing reads), like
+                // gray and the loads.
+                static_assert(G::MB == 3 && RW == 8, "three blocks a wave");
+                uint32_t P[np_rows<KC, RW>()], acc[4], tb = 0, tb2 = 0;
                 double bl[4];
                 const double beta = a.beta;
                 const uint32_t bias = (uint32_t)(255 - min(max(a.thresh, -1), 255));
@@ -1140,7 +1217,7 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
                     static_for<4>([&](auto jc) {
                         constexpr int jj = decltype(jc)::value, j = decltype(j0)::value + jj;
                         uint32_t tix;
-                        chain_blur<KC, KEEP, true, j>(P, ccf, acc[jj], tix);
+                        chain_blur<KC, KEEP, true, j, true>(P, ccf, acc[jj], tix);
                         bl[jj] = chain_tab<true>(atab, tix);
                     });
                     __builtin_amdgcn_sched_barrier(0);
@@ -1157,21 +1234,21 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
                     else rows4(j0, std::true_type{});
                     __builtin_amdgcn_sched_barrier(0);
                 };
+                const long a0 = mf_read(gn, IntC<0>{}), a1 = mf_read(gn, IntC<1>{}), a2 = mf_read(gn, IntC<2>{});
                 chain_pairs<RW>(P, Hp, wvf, ln);
-                tap_read(gn, 0, 0, q0);
-                tap_read(gn, 0, 1, q1);
+                __builtin_amdgcn_sched_barrier(0);
+                const i32x4_t d0 = mf_mul(a0), d1 = mf_mul(a1), d2 = mf_mul(a2);
                 __builtin_amdgcn_sched_barrier(0);
                 blur4(std::integral_constant<int, 0>{});
-                tap_row(edge, 0, q0, hh);
                 __builtin_amdgcn_sched_barrier(0);
                 chain4(std::integral_constant<int, 0>{});
                 blur4(std::integral_constant<int, 4>{});
-                tap_row(edge, 0, q1, hk);
-                tap_store(Hn, 0, hh, hk);
+                mf_store(Hn, IntC<0>{}, d0);
+                mf_store(Hn, IntC<1>{}, d1);
+                mf_store(Hn, IntC<2>{}, d2);
                 __builtin_amdgcn_sched_barrier(0);
                 chain4(std::integral_constant<int, 4>{});
                 chain_flags<RW>(tb, tb2, ccf, colbits);
-                if (wv < G::HLASTW) tap_job(edge, gn, Hn, 1);  // wave-uniform: the partial last round
             } else {
                 if (!TAIL || var == 0)
                     chain_rows_w<KC, KEEP, false, true, RW>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits);
@@ -1194,15 +1271,10 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             load((size_t)min(t + 3, t1 - 1) * S + s);
         }
     };
-    // Eight waves: edge and interior tiles each get their own copy, chosen before the first load (no load in
-    // flight is a phi between the copies), so the interior frame body has no REFLECT_101 branches.  Four waves
-    // (16 rows and two full tap rounds a wave: no registers to spare) keep the flag at run time.
-    if constexpr (NWB == 8) {
-        if (edge_tile) run(std::true_type{});
-        else run(std::false_type{});
-    } else {
-        run(edge_tile);
-    }
+    // Eight waves: one copy for every tile -- the image edge is in the lane's tap matrix bytes, not in the code.
+    // Four waves keep the tap jobs and their REFLECT_101 flag at run time.
+    if constexpr (NWB == 8) run(std::false_type{});
+    else run(edge_tile);
 
     double* bgo = a.bg_out + (size_t)s * plane;
     const int x = x0 + ln;
