@@ -19,11 +19,19 @@ frame, which works behind a Gaussian of any size.
                 rows, simple_tile's variants and near-misses), built inside one tile by construction and a
                 search over one parameter; the counts always come from tile_classes on oracle.dilate5.
   seams         contacts, rings, serpentines and regions laid across the tile edges at 64 and 128.
+  ccl           masks aimed at the pixel-level labelling of fm_kernels.hip (k_ccl_*): diagonal contacts across the
+                corners of its 32 x 32 blocks that are no tile corners, a frame on the image border whose hole
+                reaches the border through a 1-px channel (4-connected background, k_ccl_outer's four segments,
+                k_ccl_roots' left-neighbour test), islands inside holes.
+  overlay       a pattern on a dot lattice of pitch 6, the dots within 6 px of the pattern left out: the frames that
+                exhaust the tile pass's union-find nodes, so that relabel_frame labels adversarial pictures.
 
-test_contour_content_host.py asserts every stated class, count and contour outcome on the oracle alone;
-test_gpu_contour_content.py runs the same sets through engines and compares bit for bit.
+test_contour_content_host.py and test_pixel_ccl_host.py assert every stated class, count and contour outcome on the oracle alone;
+test_gpu_contour_content.py and test_gpu_pixel_ccl.py run the same sets through engines and compare bit for bit.
 """
 import functools
+import pathlib
+import re
 
 import numpy as np
 
@@ -519,6 +527,246 @@ def seam_set(shape):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# masks for the pixel-level labelling (fm_kernels.hip: 32 x 32 blocks): [(name, pattern, contour count)]
+
+CB = 32                   # kCclBlock
+NOTCH_SIDES = ("top", "bottom", "left", "right")
+NOTCH_CORNERS = ("top_left", "top_right", "bottom_left", "bottom_right")
+
+
+def block_corner_dots(shape, anti):
+    """corner_dots at the four-block corners of the 32-px blocks that are no tile corners (x and y odd multiples
+    of 32): the two 5 x 5 squares touch only diagonally across the corner, so one of k_ccl_merge's diagonal links
+    is the component's only connection"""
+    W, H = shape
+    p = _canvas(shape)
+    n = 0
+    for cy in range(CB, H - 4, 2 * CB):
+        for cx in range(CB, W - 4, 2 * CB):
+            _dot(p, cy - 3, cx + 2 if anti else cx - 3)
+            _dot(p, cy + 2, cx - 3 if anti else cx + 2)
+            n += 1
+    return p, n
+
+
+def _hole_dots(p, pitch=24, first=10):
+    """Dots on a grid inside a frame on the image border (a 1-px gap at least to the frame's dilation, rows and
+    columns 0 .. 4 and the last five); returns their number"""
+    H, W = p.shape
+    n = 0
+    for y in range(first, H - first, pitch):
+        for x in range(first, W - first, pitch):
+            _dot(p, y, x)
+            n += 1
+    return n
+
+
+def _notch_top(shape, at, is_open):
+    """The frame with its opening at column `at` of the top side (None: the top-left corner)"""
+    W, H = shape
+    p = _rect(_canvas(shape), 2, 2, H - 3, W - 3)
+    if is_open and at is not None:
+        p[2, at - 2:at + 3] = 0           # dilated: columns at - 1 and at + 1 stay set on rows 0 .. 4, column at is zero
+    elif is_open:
+        # the corner: the left bar moves to column 0 on rows 3 .. 9 (dilated: columns 0 .. 2 from row 1) and the top
+        # bar starts at column 6 (columns 4 ..): row 0 up to column 3 and column 3 down to row 4 stay zero
+        p[2:8, 2] = 0
+        p[2, 2:6] = 0
+        p[3:10, 0] = 1
+    return p, _hole_dots(p)
+
+
+def border_notch(shape, where, is_open, pos=1):
+    """(pattern, dots, zero border pixels [(y, x)]).  A frame (pattern rows / columns 2 and the last but two) whose
+    dilation covers the image border all round, around a grid of dots.  Closed, the dots are not external: one
+    contour.  Open, the hole's background reaches the border through one channel 1 px wide, and every dot is
+    external.  where = a side: the channel is straight, 5 px long, and exactly one border pixel is zero; pos 0, 1, 2
+    puts it near the side's start, on a 32-px block edge near its middle, near its end.  where = a corner: the
+    corner pixel is zero.  (A dilated mask cannot open a corner with two zero border pixels: the square that sets
+    the third one, (1, 0) at the top-left corner, has its centre on row 3 and sets (1, 1) too, which shuts the
+    corner pixel and its neighbour off.)  The channel runs from the corner pixel along row 0 to column 3 and down
+    column 3: four zero border pixels, 1 px wide all the way."""
+    W, H = shape
+    side = where.split("_")[0] if where in NOTCH_CORNERS else where
+    flip_x = where.endswith("right") and where in NOTCH_CORNERS
+    if where in NOTCH_CORNERS:
+        p, n = _notch_top(shape, None, is_open)
+        zero = [(0, x) for x in range(4)] if is_open else []
+        if side == "bottom":
+            p, zero = p[::-1], [(H - 1 - y, x) for y, x in zero]
+        if flip_x:
+            p, zero = p[:, ::-1], [(y, W - 1 - x) for y, x in zero]
+        return np.ascontiguousarray(p), n, zero
+    length = W if side in ("top", "bottom") else H
+    at = (7, (length // 2) // CB * CB, length - 8)[pos]
+    if side in ("top", "bottom"):
+        p, n = _notch_top(shape, at, is_open)
+        zero = [(0, at)] if is_open else []
+        if side == "bottom":
+            p, zero = p[::-1], [(H - 1, at)] if is_open else []
+    else:
+        p, n = _notch_top((H, W), at, is_open)
+        p = p.T
+        zero = [(at, 0)] if is_open else []
+        if side == "right":
+            p, zero = p[:, ::-1], [(at, W - 1)] if is_open else []
+    return np.ascontiguousarray(p), n, zero
+
+
+def islands(shape):
+    """nested_rings with dots in every hole: between the outer and the middle ring (inside a ring's hole), between
+    the middle and the inner ring (inside a ring that is itself inside a ring's hole) and inside the innermost.
+    Only the outer ring is external.  Returns (pattern, dots)."""
+    W, H = shape
+    p = nested_rings(shape)
+    n = 1
+    for i in (0, 1):                      # 9 zero pixels between two rings' dilations: a dot's square and 2 px each side
+        y0, x0, y1, x1 = 17 + 14 * i, 17 + 14 * i, H - 18 - 14 * i, W - 18 - 14 * i
+        for x in range(x0, x1 + 1, 12):
+            _dot(p, y0, x)
+            _dot(p, y1, x)
+            n += 2
+        for y in range(y0 + 12, y1 - 6, 12):
+            _dot(p, y, x0)
+            _dot(p, y, x1)
+            n += 2
+    for y in range(46, H - 46, 12):
+        for x in range(46, W - 46, 12):
+            if abs(y - H // 2) > 6 or abs(x - W // 2) > 6:
+                _dot(p, y, x)
+                n += 1
+    return p, n
+
+
+@functools.lru_cache(None)
+def notch_table(shape):
+    """name -> (pattern, dots, zero border pixels, open) of every border_notch case of a shape"""
+    out = {"notch_closed": border_notch(shape, "top", False) + (False,)}
+    for side in NOTCH_SIDES:
+        for pos, at in enumerate(("start", "middle", "end")):
+            out[f"notch_{side}_{at}"] = border_notch(shape, side, True, pos) + (True,)
+    for corner in NOTCH_CORNERS:
+        out[f"notch_{corner}"] = border_notch(shape, corner, True) + (True,)
+    return out
+
+
+def ccl_set(shape):
+    """[(name, pattern, external contours)] at a shape of at least 128 x 128"""
+    out = []
+    for anti in (False, True):
+        p, n = block_corner_dots(shape, anti)
+        out.append(("block_corner_anti" if anti else "block_corner_main", p, n))
+    for name, (p, dots, zero, is_open) in notch_table(shape).items():
+        out.append((name, p, 1 + dots if is_open else 1))
+    out.append(("islands", islands(shape)[0], 1))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# overlays: the frames of the pool-exhaustion cases (painted through the frame itself at ksize 1)
+
+LATTICE_PITCH, CLEARANCE = 6, 6
+
+
+def lattice(shape, offset):
+    """Single-pixel dots at pitch 6 from (offset, offset): dilated, 5 x 5 squares with 1-px gaps"""
+    p = _canvas(shape)
+    p[offset % LATTICE_PITCH::LATTICE_PITCH, offset % LATTICE_PITCH::LATTICE_PITCH] = 1
+    return p
+
+
+def overlay(pattern, offset=0):
+    """pattern | lattice, without the lattice dots within a Chebyshev distance of 6 of a pattern pixel (three 5 x 5
+    dilations): a 2-px gap at least between a dot's square and the pattern's dilation, so the pattern's contours
+    stay contours of the frame"""
+    H, W = pattern.shape
+    near = (np.asarray(pattern) != 0).astype(np.uint8) * 255
+    for _ in range(CLEARANCE // 2):
+        near = oracle.dilate5(near)
+    return ((pattern != 0) | ((lattice((W, H), offset) != 0) & (near == 0))).astype(np.uint8)
+
+
+def overlay_sources(shape):
+    """[(name, pattern)]: seam_set and a pick of ccl_set, the pictures the overlays cycle"""
+    pick = ("block_corner_main", "block_corner_anti", "islands", "notch_top_middle", "notch_bottom_right",
+            "notch_closed")
+    return [(c[0], c[1]) for c in seam_set(shape)] + [(c[0], c[1]) for c in ccl_set(shape) if c[0] in pick]
+
+
+def fallback_frames(shape, n, every, first=0):
+    """[(name, pattern)] of an n-frame batch that exhausts the tile pass's nodes: a black frame, then pure lattices
+    (offset = the frame's index) but for every `every`-th frame, an overlay; the overlays cycle overlay_sources
+    from its entry `first`"""
+    src = overlay_sources(shape)
+    out, k = [("black", _canvas(shape))], first
+    for t in range(1, n):
+        if t % every == 0:
+            name, p = src[k % len(src)]
+            out.append((f"overlay_{name}_{t % LATTICE_PITCH}", overlay(p, t)))
+            k += 1
+        else:
+            out.append((f"lattice_{t % LATTICE_PITCH}", lattice(shape, t)))
+    return out
+
+
+def node_allotment(ntiles, frames):
+    """Union-find nodes per tile-frame that a slot of `frames` frames gives the tile pass on average: each frame's
+    quota and the shared overflow pool, with the constants read from fm_internal.h and combined as fm_create does
+    (nn = tf + tf * kNodesPerTileFrame + max(tf * kNodesShared, ntiles * kTileMaxRuns); the first tf are the
+    empty-tile region slots)"""
+    text = (pathlib.Path(__file__).resolve().parent.parent / "find_motion_amd" / "csrc" / "fm_internal.h").read_text()
+    k = {n: int(re.search(rf"constexpr int {n} = (\d+);", text).group(1))
+         for n in ("kNodesPerTileFrame", "kNodesShared", "kTileMaxRuns")}
+    tf = ntiles * frames
+    return (tf * k["kNodesPerTileFrame"] + max(tf * k["kNodesShared"], ntiles * k["kTileMaxRuns"])) / tf
+
+
+def tile_components(masks):
+    """The 8-connected foreground components of every 64 x 64 tile of every mask of a list, each tile on its own
+    (a component that crosses a tile edge counts once in each tile): their total.  Row runs, the pairs of touching
+    runs of consecutive rows, and a minimum-label sweep with pointer jumping over those pairs."""
+    planes = []
+    for m in masks:
+        h, w = m.shape
+        nty, ntx = -(-h // TS), -(-w // TS)
+        pad = np.zeros((nty * TS, ntx * TS), bool)
+        pad[:h, :w] = m != 0
+        sep = np.zeros((nty, TS + 1, ntx, TS + 1), bool)      # a zero row and column after every tile
+        sep[:, :TS, :, :TS] = pad.reshape(nty, TS, ntx, TS)
+        planes.append(sep.reshape(nty * (TS + 1), ntx * (TS + 1)))
+    width = max(p.shape[1] for p in planes)
+    img = np.concatenate([np.pad(p, ((0, 0), (0, width - p.shape[1]))) for p in planes])
+    d = np.diff(np.pad(img, ((0, 0), (1, 1))).astype(np.int8), axis=1)
+    ys, xs = np.nonzero(d == 1)                               # run starts, in raster order
+    ye, xe = np.nonzero(d == -1)                              # one past each run's end
+    n = len(ys)
+    if n == 0:
+        return 0
+    K = width + 4
+    skey, ekey = ys * K + xs, ye * K + xe - 1
+    lo = np.searchsorted(ekey, (ys - 1) * K + xs - 1, "left")        # first run of the row above ending at xs - 1 or later
+    hi = np.searchsorted(skey, (ys - 1) * K + xe, "right") - 1       # last one starting at the end + 1 or before
+    cnt = np.maximum(hi - lo + 1, 0)
+    a = np.repeat(np.arange(n), cnt)
+    b = np.repeat(lo, cnt) + (np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    lab = np.arange(n)
+    while True:
+        m = np.minimum(lab[a], lab[b])
+        new = lab.copy()
+        np.minimum.at(new, a, m)
+        np.minimum.at(new, b, m)
+        while True:
+            nn = new[new]
+            if np.array_equal(nn, new):
+                break
+            new = nn
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    return int((lab == np.arange(n)).sum())
+
+
+# ------------------------------------------------------------------------------------------------------------
 # references and the comparison with an engine
 
 _REFERENCES = {}
@@ -537,13 +785,15 @@ def reference(shape, name, pattern):
             a.setflags(write=False)
         ref = _REFERENCES[(shape, name)] = dict(
             pattern=pattern.copy(), mask=dil, boxes=[c["bbox"] for c in cs], origins=[c["origin"] for c in cs],
-            classes=classes, heavy=sum(1 for v in classes.values() if v[0] == "heavy"), bits=bits)
+            areas=[c["area"] for c in cs], classes=classes, heavy=sum(1 for v in classes.values() if v[0] == "heavy"), bits=bits)
     assert np.array_equal(ref["pattern"], pattern), f"two patterns named {name} at {shape}"
     return ref
 
 
 def patterns_of(shape, kind):
-    """[(name, pattern)] of a case set: "boundary", "seams", "cut" or "four_wave\""""
+    """[(name, pattern)] of a case set: "boundary", "seams", "cut", "ccl" or "four_wave\""""
+    if kind == "ccl":
+        return [(c[0], c[1]) for c in ccl_set(shape)]
     if kind == "boundary":
         return [(c[0], c[1]) for c in boundary_set(shape)]
     if kind == "cut":
@@ -553,16 +803,21 @@ def patterns_of(shape, kind):
     return [(c[0], c[1]) for c in seam_set(shape)]
 
 
-def run_batches(eng, shape, named, trace=False):
+def run_batches(eng, shape, named, trace=False, areas=False):
     """The patterns `named` [(name, pattern)] through an engine, S per batch (a short last batch is filled from the
     list's start), T = 2, one batch after the other: every batch's masks, counts, boxes, origins, threshold bits
-    and backgrounds against the oracle, no fallback, and heavy_tiles equal to the model's count.  Returns the
-    number of batches."""
-    from find_motion_amd._native import FMError
+    and backgrounds against the oracle, no fallback, and heavy_tiles equal to the model's count.  On the per-frame
+    path ("pixel": k_pixel and the pixel-level labelling, no tile pass) the bits are refused as on "fused", and
+    both statistics hold the 0 a context starts with: fm_wait copies them from the tile pass's words on the
+    tile paths only.  Where the engine keeps planes, the blur and delta planes are 255 on the pattern and 0
+    elsewhere, and 0 on the black frame.  trace: every point of every contour (an engine with contour_points);
+    areas: every contour's area against the oracle's (an engine with contour_area).  Returns the number of batches."""
+    from find_motion_amd._native import PLANE_BLUR, PLANE_DELTA, FMError
 
     S = eng.n_streams
     W, H = shape
     assert eng.work_shape == (H, W) and (eng.params.threshold, eng.params.avg) == (0, 0.0)
+    keeps_bits = eng.pixel_path not in ("fused", "pixel")
     nb = -(-len(named) // S)
     for b in range(nb):
         group = [named[(b * S + s) % len(named)] for s in range(S)]
@@ -583,19 +838,87 @@ def run_batches(eng, shape, named, trace=False):
             assert counts[1, s] == len(ref["boxes"]) == len(got), f"{name} ({at}): {counts[1, s]} contours"
             assert [g.bbox for g in got] == ref["boxes"], f"boxes {name} ({at})"
             assert [g.origin for g in got] == ref["origins"], f"origins {name} ({at})"
-            if eng.pixel_path == "fused":  # (k_fused keeps dilated bits only)
+            if not keeps_bits:  # (k_fused keeps dilated bits only, the per-frame path a byte mask)
                 try:
                     eng.threshold_bits(1, s)
-                    raise AssertionError("the fused path returned threshold bits")
+                    raise AssertionError(f"the {eng.pixel_path} path returned threshold bits")
                 except FMError:
                     pass
             else:
                 assert not eng.threshold_bits(0, s).any(), f"{at}: black frame's bits"
                 np.testing.assert_array_equal(eng.threshold_bits(1, s), ref["bits"], err_msg=f"bits {name} ({at})")
+            if eng.keep_planes:
+                want = (ref["pattern"] != 0).astype(np.uint8) * 255
+                for which in (PLANE_BLUR, PLANE_DELTA):
+                    assert not eng.plane(which, 0, s).any(), f"plane {which} of the black frame ({at})"
+                    np.testing.assert_array_equal(eng.plane(which, 1, s), want, err_msg=f"plane {which} {name} ({at})")
             assert not eng.background(s).any(), f"background {name} ({at})"
             if trace:
                 from test_gpu_contour_points import check_frame
                 check_frame(eng, 1, s, mask=ref["mask"], tag=f"{name} ({at})")
-        heavy = sum(r["heavy"] for r in refs)
+            if areas:
+                assert [g.area for g in got] == ref["areas"], f"areas {name} ({at})"
+        heavy = 0 if eng.pixel_path == "pixel" else sum(r["heavy"] for r in refs)
+        shared = eng.ccl_stats()["shared_nodes"]
         assert eng.ccl_stats()["heavy_tiles"] == heavy, f"{at}: heavy_tiles {eng.ccl_stats()} != {heavy}"
+        assert eng.pixel_path != "pixel" or shared == 0, f"{at}: {eng.ccl_stats()} on the per-frame path"
     return nb
+
+
+_PLAIN = {}
+
+
+def plain_reference(shape, name, pattern):
+    """The oracle's mask, boxes and origins of a frame painted directly (ksize 1, threshold 0, a black background):
+    reference() without the class model, for the large frames of the pool-exhaustion cases"""
+    ref = _PLAIN.get((shape, name))
+    if ref is None:
+        dil = dilated(pattern)
+        dil.setflags(write=False)
+        cs = oracle.find_contours_ext(dil, cap=1 << 16)
+        ref = _PLAIN[(shape, name)] = dict(pattern=pattern.copy(), mask=dil, boxes=[c["bbox"] for c in cs],
+                                           origins=[c["origin"] for c in cs])
+    assert np.array_equal(ref["pattern"], pattern), f"two frames named {name} at {shape}"
+    return ref
+
+
+def run_direct(eng, shape, named, fallback):
+    """One batch on a one-stream engine with ksize 1, threshold 0, avg 0.0 whose background is black (or not yet
+    initialised, with a black first frame): frame t is pattern t painted white; every frame's mask, count, boxes
+    and origins against the oracle.  fallback: whether the batch has to exhaust the tile pass's nodes (at least one
+    frame relabelled by the pixel-level labelling; a batch without one fails) or must not."""
+    W, H = shape
+    assert eng.work_shape == (H, W) and eng.n_streams == 1 and eng.params.ksize == 1
+    assert (eng.params.threshold, eng.params.avg) == (0, 0.0)
+    fr = np.zeros((len(named), 1, H, W, 3), np.uint8)
+    for t, (_, p) in enumerate(named):
+        fr[t, 0][p != 0] = 255
+    eng.submit(fr)
+    eng.wait()
+    print(f"\n{W} x {H}, {len(named)} frames: {eng.fallbacks()} relabelled, {eng.ccl_stats()}")
+    assert (eng.fallbacks() > 0) == fallback, f"{eng.fallbacks()} frames fell back"
+    counts = eng.counts()
+    for t, (name, p) in enumerate(named):
+        ref = plain_reference(shape, name, p)
+        np.testing.assert_array_equal(eng.mask(t, 0), ref["mask"], err_msg=f"mask of frame {t} {name}")
+        got = eng.contours(t, 0)
+        assert counts[t, 0] == len(ref["boxes"]) == len(got), f"frame {t} {name}: {counts[t, 0]} contours"
+        assert [g.bbox for g in got] == ref["boxes"], f"boxes of frame {t} {name}"
+        assert [g.origin for g in got] == ref["origins"], f"origins of frame {t} {name}"
+    assert not eng.background(0).any()
+
+
+TRACE_PATHS = ("reg", "lds", "lds_big", "unstaged")
+
+
+def trace_paths(boxes):
+    """The path of fm_trace.hip each contour box (x, y, w, h) takes, as trace_box_path decides it (restated, with
+    the limits read from fm_trace.hip): the padded box in 32-bit words per row, plus one, times its rows"""
+    text = (pathlib.Path(__file__).resolve().parent.parent / "find_motion_amd" / "csrc" / "fm_trace.hip").read_text()
+    k = {n: int(re.search(rf"constexpr int {n} = (\d+);", text).group(1)) for n in ("kTinyBox", "kWinWords", "kBigWords")}
+    out = []
+    for _, _, bw, bh in boxes:
+        words = (((bw + 2 + 31) >> 5) + 1) * (bh + 2)
+        out.append("reg" if bw <= k["kTinyBox"] and bh <= k["kTinyBox"] else
+                   "lds" if words <= k["kWinWords"] else "lds_big" if words <= k["kBigWords"] else "unstaged")
+    return out

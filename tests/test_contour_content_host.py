@@ -4,7 +4,9 @@ For every shape the GPU module runs: the painter gives the oracle exactly dilate
 11 and 21 (and 1 at the small shape), batch after batch on one stream without a reset; every boundary tile has
 exactly the stated class and run counts by contour_content.tile_classes; each case set holds all six classes; the
 seam cases give the contour counts and the external / not-external outcomes their names say; no tile exceeds
-kTileMaxRuns.
+kTileMaxRuns.  The same for the per-frame path's cases (a Gaussian of 51) and for the masks aimed at the pixel-level
+labelling: the block-corner contacts, the border notches (which border pixels are zero, that they are 4-connected
+to the hole, the contour counts) and the islands.
 """
 import numpy as np
 import pytest
@@ -21,8 +23,12 @@ def _sid(shape):
     return f"{shape[0]}x{shape[1]}"
 
 
+CCL_SHAPES = (cc.CHAIN, cc.FRAME) + cc.CUTS      # the shapes that also run the masks for the pixel-level labelling
+
+
 def _all(shape):
-    return [(f"{kind}:{n}", p) for kind in KINDS[shape] for n, p in cc.patterns_of(shape, kind)]
+    kinds = KINDS[shape] + (("ccl",) if shape in CCL_SHAPES else ())
+    return [(f"{kind}:{n}", p) for kind in kinds for n, p in cc.patterns_of(shape, kind)]
 
 
 def test_shapes_take_the_layouts_they_stand_for():
@@ -44,6 +50,14 @@ def test_shapes_take_the_layouts_they_stand_for():
         assert shape[0] % 64 in (1, 2, 63) and shape[1] % 64 in (1, 2, 63)
     assert {s[0] % 64 for s in cc.CUTS} == {s[1] % 64 for s in cc.CUTS} == {1, 2, 63}
     assert plan(cc.FOUR_WAVE, 5, n_streams=8)["tiles"] * 8 == 1024
+    # a Gaussian above 49 taps: the per-frame path at 16 tiles or fewer, or where planes are kept; else fm_wide.hip
+    assert (plan(cc.FRAME, 51, n_streams=3)["pixel_path"], plan(cc.FRAME, 51, n_streams=3)["tiles"]) == ("pixel", 12)
+    assert plan(cc.CHAIN, 51, n_streams=3, keep_planes=True)["pixel_path"] == "pixel"
+    assert (plan(cc.CHAIN, 51, n_streams=3)["pixel_path"], plan(cc.CHAIN, 51, n_streams=3)["tiles"]) == ("wide", 30)
+    for shape in cc.CUTS:   # 32 x 32 labelling blocks and 64 x 16 k_pixel tiles cut at 1, 2 and 31
+        assert plan(shape, 51, n_streams=3, keep_planes=True)["pixel_path"] == "pixel"
+    assert {s[0] % 32 for s in cc.CUTS} == {s[1] % 32 for s in cc.CUTS} == {1, 2, 31}
+    assert {s[1] % 16 for s in cc.CUTS} <= {1, 2, 15}
 
 
 @pytest.mark.parametrize("shape", SHAPES[:-1], ids=_sid)
@@ -52,7 +66,7 @@ def test_painter_identity(shape):
     frame, a white frame, no reset between -- and gives dilate5(pattern), the shared reference's contours and a
     background of zeros every time."""
     W, H = shape
-    for k in (1, 5) if shape == cc.SMALL else (5, 11, 21):
+    for k in (1, 5) if shape == cc.SMALL else (5, 11, 21, 51):
         orc = oracle.OracleStream(oracle.OracleConfig(H=H, W=W, box=W, ksize=k, thresh=0, alpha=0.0))
         for name, p in _all(shape):
             fr, keeps = cc.paint_frames([p])
@@ -64,6 +78,9 @@ def test_painter_identity(shape):
             np.testing.assert_array_equal(res["mask"], cc.dilated(p), err_msg=f"k {k} {name}")
             np.testing.assert_array_equal(res["mask"], ref["mask"])
             np.testing.assert_array_equal(res["delta"] > 0, p != 0, err_msg=f"threshold bits k {k} {name}")
+            for plane in ("blur", "delta"):   # what an engine that keeps planes returns
+                np.testing.assert_array_equal(res[plane], (p != 0) * np.uint8(255), err_msg=f"{plane} k {k} {name}")
+                assert not first[plane].any(), (k, name)
             assert (res["boxes"], res["origins"]) == (ref["boxes"], ref["origins"]), (k, name)
             assert not orc.bg.any(), (k, name)
 
@@ -268,6 +285,89 @@ def test_seam_cases(shape):
         assert all(0 < y < nty - 1 and 0 < x < ntx - 1 for y, x in hole)
         assert ((98, 98) in refs[n]["origins"]) == is_open
         assert (158, H - 5) in refs[n]["origins"]
+
+
+def _flood4(zero, seeds):
+    """The pixels of `zero` (bool) 4-connected to the seed pixels"""
+    reach = np.zeros_like(zero)
+    for y, x in seeds:
+        reach[y, x] = zero[y, x]
+    while True:
+        grow = reach.copy()
+        grow[1:] |= reach[:-1]
+        grow[:-1] |= reach[1:]
+        grow[:, 1:] |= reach[:, :-1]
+        grow[:, :-1] |= reach[:, 1:]
+        grow &= zero
+        if np.array_equal(grow, reach):
+            return reach
+        reach = grow
+
+
+@pytest.mark.parametrize("shape", CCL_SHAPES, ids=_sid)
+def test_masks_for_the_pixel_level_labelling(shape):
+    W, H = shape
+    cases = {n: (p, cnt) for n, p, cnt in cc.ccl_set(shape)}
+    refs = {n: cc.reference(shape, n, p) for n, (p, _) in cases.items()}
+    for n, (p, cnt) in cases.items():
+        assert len(refs[n]["boxes"]) == cnt, (n, len(refs[n]["boxes"]), cnt)
+        assert all(c[0] != "over" for c in refs[n]["classes"].values()), n
+    # every pair of dots is one 10 x 10 contour around a corner of four 32-px blocks that is no tile corner, and
+    # the two squares touch there diagonally only
+    for n, main in (("block_corner_main", True), ("block_corner_anti", False)):
+        boxes = refs[n]["boxes"]
+        assert len(boxes) == ((H - 5 - 32) // 64 + 1) * ((W - 5 - 32) // 64 + 1) >= 4
+        d = refs[n]["mask"]
+        for x, y, bw, bh in boxes:
+            cx, cy = x + 5, y + 5
+            assert (bw, bh) == (10, 10) and cx % 64 == 32 and cy % 64 == 32, (n, x, y, bw, bh)
+            assert bool(d[cy - 1, cx - 1]) == bool(d[cy, cx]) == main, (n, cx, cy)
+            assert bool(d[cy - 1, cx]) == bool(d[cy, cx - 1]) == (not main), (n, cx, cy)
+    # the notches: the zero border pixels, their 4-connection to the hole, the counts
+    tab = cc.notch_table(shape)
+    assert len(tab) == 1 + 4 * 3 + 4
+    border = np.zeros((H, W), bool)
+    border[0] = border[-1] = border[:, 0] = border[:, -1] = True
+    hole = (10, 7)                                 # left of the first dot's square
+    for n, (p, dots, zero, is_open) in tab.items():
+        d = refs[n]["mask"]
+        assert dots >= 12 and not d[hole], n
+        got = sorted(zip(*np.nonzero(border & (d == 0))))
+        assert got == sorted(zero), (n, got, zero)
+        assert len(zero) == (0 if not is_open else 4 if n[6:] in cc.NOTCH_CORNERS else 1), (n, zero)
+        assert len(refs[n]["boxes"]) == (1 + dots if is_open else 1), n
+        assert refs[n]["boxes"][0] == (0, 0, W, H), n
+        if is_open:
+            reach = _flood4(d == 0, zero)
+            assert reach[hole] and all(reach[z] for z in zero), n
+            # 1 px wide: with any channel pixel next to the border filled, the hole is closed again
+            y, x = zero[-1] if n[6:] in cc.NOTCH_CORNERS else zero[0]
+            shut = d.copy()
+            shut[y, x] = 255
+            assert len(oracle.find_contours_ext(shut)) == 1, n
+        else:
+            assert not _flood4(d == 0, [hole])[border].any()
+    sides = {n: z[0] for n, (p, dots, z, o) in tab.items() if o and len(z) == 1}
+    assert {sides[f"notch_top_{a}"][1] for a in ("start", "middle", "end")} == {7, (W // 2) // 32 * 32, W - 8}
+    assert {sides[f"notch_right_{a}"] for a in ("start", "middle", "end")} == {(7, W - 1), ((H // 2) // 32 * 32, W - 1),
+                                                                               (H - 8, W - 1)}
+    assert {z[0] for z in sides.values()} >= {0, H - 1} and {z[1] for z in sides.values()} >= {0, W - 1}
+    corners = {tab[f"notch_{c}"][2][0] for c in cc.NOTCH_CORNERS}
+    assert corners == {(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1)}
+    # the islands: one contour; without the outer ring the middle ring and the dots of the outer hole are external,
+    # without the two outer rings the inner ring and the dots of the middle hole
+    p, dots = cc.islands(shape)
+    assert refs["islands"]["boxes"] == [(8, 8, W - 16, H - 16)]
+    rings = [cc._rect(cc._canvas(shape), 10 + 14 * i, 10 + 14 * i, H - 11 - 14 * i, W - 11 - 14 * i) for i in range(3)]
+    left = [dots]
+    for i in range(3):
+        p = p & ~rings[i]
+        cs = oracle.find_contours_ext(cc.dilated(p))
+        left.append(len(cs) - (1 if i < 2 else 0))    # the dots now external (and the next ring)
+        assert (i == 2) or (8 + 14 * (i + 1), 8 + 14 * (i + 1), W - 16 - 28 * (i + 1), H - 16 - 28 * (i + 1)) in \
+            [c["bbox"] for c in cs], i
+    assert left[3] == dots and 0 < left[1] < left[2] < left[3] and left[1] >= 8 and left[2] - left[1] >= 8
+    assert left[3] - left[2] >= 2                 # dots inside the innermost ring
 
 
 def test_four_wave_frames():

@@ -8,14 +8,17 @@ paints exact masks through the keep-mask behind any Gaussian, and test_contour_c
 class, count and outcome of them on the oracle.
 
   case              shape      k   sets                 what runs
-  chain, dilating   324 x 260  5   boundary + seams     k_pix5, k_tile_flags, the dilating chain on 30 tiles
+  chain, dilating   324 x 260  5   boundary, seams, ccl  k_pix5, k_tile_flags, the dilating chain on 30 tiles
   frame layout      200 x 136  5   boundary + seams     k_pix5, k_frame_contours<true> on 12 tiles
   k_pixw            324 x 260  21  boundary + seams     k_pixw, the dilating chain
-  fused             324 x 260  11  boundary + seams     k_fused, the non-dilating chain
+  fused             324 x 260  11  boundary, seams, ccl  k_fused, the non-dilating chain
   small path        128 x 96   1   boundary (13 tiles)  the small-image path, k_frame_contours on 4 tiles
   trace             324 x 260  5   seams                contour_points: every point and area (fm_trace.hip)
   cut               3 shapes   5   cut                  w % 64 and h % 64 in {1, 2, 63}: tiles cut by the image
   four-wave         8 x 1024 x 512  5  mixed frames     k_pix5's 4-wave tiles, 128 tiles per frame
+
+("ccl": the masks aimed at the pixel-level labelling -- block-corner contacts, border notches, islands -- which the
+tile pass has to get right too; test_gpu_pixel_ccl.py runs every set on the per-frame and the wide path.)
 
 Every case: S streams carry different patterns in one batch (T = 2: a black frame, a white one), batch after
 batch on one engine, so that slots are reused with other masks; masks, counts, boxes, origins, threshold bits
@@ -52,7 +55,7 @@ def _run(shape, k, kinds, path, chain, S=3, reuse=False, **kw):
 
 
 def test_dilating_chain():
-    _run(cc.CHAIN, 5, ("boundary", "seams"), "pix", True, reuse=True)
+    _run(cc.CHAIN, 5, ("boundary", "seams", "ccl"), "pix", True, reuse=True)
 
 
 def test_frame_layout():
@@ -64,7 +67,7 @@ def test_wide_gaussian_kernel():
 
 
 def test_fused_non_dilating_chain():
-    _run(cc.CHAIN, 11, ("boundary", "seams"), "fused", True)
+    _run(cc.CHAIN, 11, ("boundary", "seams", "ccl"), "fused", True)
 
 
 def test_small_image_path():

@@ -133,6 +133,31 @@ def ring_and_blob(h, w):
     return m
 
 
+def dot_and_corner_dots():
+    """An isolated dot and a dot in each corner of a 100 x 100 image (dilated: 5 x 5, and 3 x 3 against the
+    corners, where the register path's window starts left of and above the image)."""
+    m = np.zeros((100, 100), np.uint8)
+    m[50, 40] = m[0, 0] = m[99, 99] = m[0, 99] = m[99, 0] = 255
+    return m
+
+
+def edge_blob():
+    """A 200 x 130 blob (not a multiple of 64; outside the image is zero) that touches all four edges, with a
+    notch cut into each."""
+    m = np.full((130, 200), 255, np.uint8)
+    m[0:30, 50:59] = 0
+    m[60:69, 170:200] = 0
+    m[100:130, 20:29] = 0
+    m[40:49, 0:25] = 0
+    return m
+
+
+def box_words(bbox):
+    """32-bit words of a contour box's staged window, as trace_box_path counts them: the padded box's words per
+    row, plus one, times its rows."""
+    return (((bbox[2] + 2 + 31) >> 5) + 1) * (bbox[3] + 2)
+
+
 # ---- fixtures and random masks -----------------------------------------------------------------
 def test_fixture_masks_and_random_speckle():
     from golden_cases import contour_cases
@@ -158,21 +183,14 @@ def test_fixture_masks_and_random_speckle():
 
 # ---- shapes the walk can get wrong -------------------------------------------------------------
 def test_isolated_dot_and_corner_dots():
-    m = np.zeros((100, 100), np.uint8)
-    m[50, 40] = m[0, 0] = m[99, 99] = m[0, 99] = m[99, 0] = 255
-    ref, stats = painted_case(m)
+    ref, stats = painted_case(dot_and_corner_dots())
     assert len(ref) == 5
     assert sorted(c["bbox"][2:] for c in ref) == [(3, 3)] * 4 + [(5, 5)] and all(c["npts"] == 4 for c in ref)
     assert stats["staged"] == 5 and stats["unstaged"] == 0 and stats["steps"] > 0
 
 
 def test_blob_touching_all_four_edges():
-    m = np.full((130, 200), 255, np.uint8)   # not a multiple of 64; outside the image is zero
-    m[0:30, 50:59] = 0
-    m[60:69, 170:200] = 0
-    m[100:130, 20:29] = 0
-    m[40:49, 0:25] = 0
-    ref, _ = painted_case(m)
+    ref, _ = painted_case(edge_blob())
     assert len(ref) == 1 and ref[0]["bbox"] == (0, 0, 200, 130) and ref[0]["npts"] >= 20
 
 
@@ -196,18 +214,27 @@ def test_spiral_long_walk_across_tiles():
 
 # ---- both paths ---------------------------------------------------------------------------------
 def test_staged_and_unstaged_contours_in_one_frame():
+    """The ring grows with the image until its window no longer fits the big LDS window; every size visited is
+    compared with the oracle.  At 640 x 360 the ring's box needs more than kWinWords (2,048) words and at most
+    kBigWords (16,256): staged by k_trace_lds<EMIT, 1, kBigWords>, the 63.5 KiB window."""
     for w, h in ((640, 360), (1280, 720), (1920, 1080)):
-        eng = paint([ring_and_blob(h, w)])
+        eng = paint([ring_and_blob(h, w)], profile=True)
         stats = eng.trace_stats()
+        ran = {n for n, (ms, cnt) in eng.kernel_times().items() if cnt > 0 and n.startswith("trace_")}
+        ref = check_frame(eng, 1, 0, mask=oracle.dilate5(ring_and_blob(h, w)), tag=f"{w} x {h}")
+        eng.close()
+        assert len(ref) == 2 and ref[0]["bbox"][2] >= w - 50 and ref[1]["bbox"][2] <= 40, (w, h)
+        if (w, h) == (640, 360):
+            assert stats["staged"] == 2 and stats["unstaged"] == 0, stats
+            assert 2048 < box_words(ref[0]["bbox"]) <= 16256 and box_words(ref[1]["bbox"]) <= 2048, ref
+            assert ran == {"trace_count_lds", "trace_emit_lds", "trace_count_lds_big", "trace_emit_lds_big"}, ran
         if stats["unstaged"] >= 1:
             break
-        eng.close()
     else:
         pytest.fail("the ring's contour is still staged at 1920 x 1080")
-    ref = check_frame(eng, 1, 0)
-    eng.close()
     assert len(ref) == 2 and stats["staged"] >= 1 and stats["unstaged"] >= 1
     assert ref[0]["bbox"][2] >= w - 50 and ref[1]["bbox"][2] <= 40
+    assert box_words(ref[0]["bbox"]) > 16256 and "trace_emit_unstaged" in ran, (ref[0]["bbox"], ran)
 
 
 # ---- both mask representations ------------------------------------------------------------------
