@@ -1,7 +1,8 @@
 """The host side of the YOLOv3 object stage on a machine without a GPU: the Darknet cfg parser and weights
 loader (find_motion_amd/darknet.py), the restated 8-bit INTER_LINEAR and blob table, cvlib's box loop and
 NMSBoxes (the product's host tail and tests/yolo_ref.py's restatement alike), fm_yolo_create's refusals (host
-code of the built library) and the drop-in's wiring with a fake detector."""
+code of the built library), the drop-in's wiring with a fake detector, known answers for the yolov3 and
+yolov3-tiny generators, and the exact integer convolution reference."""
 import ctypes as C
 import logging
 import struct
@@ -503,3 +504,117 @@ def test_cli_flag_and_ini_setting(tmp_path):
     ini.write_text("[settings]\nyolo-dir = /from/ini\nyolo_tiny = True\n")
     args = cli.process_config(str(ini), parser.parse_args(["x.avi"]))
     assert args.yolo_dir == "/from/ini" and args.yolo_tiny is True
+
+
+# ---- the two real topologies from the shared generators, and the exact convolution reference ---------------------
+def _param_count(layers):
+    """Floats of a .weights file after its header: weights + (beta, gamma, mean, var) or the bias."""
+    return sum(ly["filters"] * ly["in_c"] * ly["size"] ** 2 + (4 if ly["batch_normalize"] else 1) * ly["filters"]
+               for ly in layers if ly["kind"] == dk.CONV)
+
+
+TOPOLOGIES = [
+    pytest.param(yr.full_cfg, 107, 75, 23, 62001757, 248007048, {83: [79], 86: [85, 61], 95: [91], 98: [97, 36]},
+                 {82: 13, 94: 26, 106: 52}, 10647, id="yolov3"),
+    pytest.param(yr.tiny_cfg, 24, 13, 0, 8858734, 35434956, {17: [13], 20: [19, 8]}, {16: 13, 23: 26}, 2535,
+                 id="yolov3-tiny"),
+]
+
+
+@pytest.mark.parametrize("gen, n_layers, n_convs, n_shortcuts, n_params, n_bytes, routes, heads, rows", TOPOLOGIES)
+def test_real_topology_known_answers(gen, n_layers, n_convs, n_shortcuts, n_params, n_bytes, routes, heads, rows):
+    net, layers = dk.parse_cfg(gen())
+    assert (net["width"], net["height"], net["channels"]) == ("416", "416", "3")
+    convs = [ly for ly in layers if ly["kind"] == dk.CONV]
+    assert len(layers) == n_layers and len(convs) == n_convs
+    assert sum(ly["kind"] == dk.SHORTCUT for ly in layers) == n_shortcuts
+    assert _param_count(layers) == n_params
+    assert max(ly["in_c"] * ly["size"] ** 2 for ly in convs) == 4608 and max(ly["filters"] for ly in convs) == 1024
+    assert {ly["index"]: ly["layers"] for ly in layers if ly["kind"] == dk.ROUTE} == routes
+    shapes = yr.layer_shapes(layers, 416, 416)
+    ys = [ly for ly in layers if ly["kind"] == dk.YOLO]
+    assert {ly["index"]: shapes[ly["index"]] for ly in ys} == {i: (255, g, g) for i, g in heads.items()}
+    assert all(ly["classes"] == 80 and len(ly["mask"]) == 3 for ly in ys)
+    assert sum(len(ly["mask"]) * shapes[ly["index"]][1] * shapes[ly["index"]][2] for ly in ys) == rows
+    # every head's convolution is linear, without batch norm, 255 wide; every other one leaky with batch norm
+    for ly in convs:
+        head = layers[ly["index"] + 1]["kind"] == dk.YOLO
+        assert (ly["activation"], ly["batch_normalize"]) == (("linear", 0) if head else ("leaky", 1)), ly["index"]
+        assert not head or (ly["filters"], ly["size"]) == (255, 1)
+    # the file write_weights makes of it: the 20-byte header and every parameter, and load_weights takes it back
+    raw = {ly["index"]: tuple(np.zeros(k, np.float32) for k in
+                              ([ly["filters"]] * (4 if ly["batch_normalize"] else 1)
+                               + [ly["filters"] * ly["in_c"] * ly["size"] ** 2])) for ly in convs}
+    data = dk.write_weights(layers, raw)
+    del raw
+    assert len(data) == n_bytes == 20 + 4 * n_params
+    del data
+
+
+def test_real_topology_generators_take_classes_and_size():
+    for gen, n_heads in ((yr.full_cfg, 3), (yr.tiny_cfg, 2)):
+        net, layers = dk.parse_cfg(gen(classes=3, width=96, height=64))
+        assert (net["width"], net["height"]) == ("96", "64")
+        ys = [ly for ly in layers if ly["kind"] == dk.YOLO]
+        assert len(ys) == n_heads and all(ly["classes"] == 3 and ly["in_c"] == 24 for ly in ys)
+        shapes = yr.layer_shapes(layers, 96, 64)
+        assert [shapes[ly["index"]][1:] for ly in ys] == [(2, 3), (4, 6), (8, 12)][:n_heads]
+    # the shapes the walk gives are fm_yolo_create's own: a route joining what it says are equal sizes is accepted,
+    # and an odd size through tiny's stride-2 pools rounds up
+    _, layers = dk.parse_cfg(yr.tiny_cfg(classes=1, width=72, height=40))
+    assert yr.layer_shapes(layers, 72, 40)[11] == (512, 2, 3) and yr.layer_shapes(layers, 72, 40)[9] == (256, 2, 3)
+
+
+@pytest.mark.parametrize("cin, cout, size, stride, h, w", [(5, 7, 3, 1, 4, 6), (6, 9, 3, 2, 5, 7), (6, 9, 3, 2, 6, 4),
+                                                          (8, 3, 1, 1, 3, 5), (4, 4, 3, 1, 1, 1)])
+def test_conv_exact_equals_the_float64_convolution_on_integers(cin, cout, size, stride, h, w):
+    rng = np.random.default_rng(cin * 10 + cout)
+    x = rng.integers(-3, 4, (2, cin, h, w))
+    wt = rng.integers(-2, 3, (cout, cin, size, size))
+    b = rng.integers(-8, 9, cout)
+    want, wmag = yr.conv(x, wt, b, stride, size // 2, False)
+    for args in ((x, wt, b), (x.astype(np.float32), wt.astype(np.float32), b.astype(np.float32))):
+        got, mag = yr.conv_exact(*args, stride, size // 2, False)
+        assert got.dtype == np.float32 and mag.dtype == np.int64
+        assert got.shape == want.shape and np.array_equal(got, want) and np.array_equal(mag, wmag)
+    assert (want < 0).any() and (want >= 0).any()
+    # leaky: the values that are not negative as they were, a negative one times f32 0.1 with one rounding
+    leaky, lmag = yr.conv_exact(x, wt, b, stride, size // 2, True)
+    assert leaky.dtype == np.float32 and np.array_equal(lmag, mag)
+    neg = want < 0
+    assert np.array_equal(leaky[~neg], want[~neg])
+    assert np.array_equal(leaky[neg], np.float32(0.1) * want[neg].astype(np.float32))
+    assert float(np.float32(0.1)) != 0.1  # (so that the line above is not the float64 product)
+    w64, _ = yr.conv(x, wt, b, stride, size // 2, True)
+    assert np.all(np.abs(leaky - w64) <= 2 * yr.U * np.abs(w64))
+
+
+def test_conv_exact_refuses_what_breaks_its_condition():
+    x = np.full((1, 2, 3, 3), 3)
+    w = np.full((1, 2, 3, 3), 2)
+    b = np.array([8])
+    out, mag = yr.conv_exact(x, w, b, 1, 1, False)
+    assert int(mag.max()) == 2 * 9 * 6 + 8 == int(out.max())
+    # a magnitude sum of exactly 2^24 is refused, one below it is taken, whatever the sign of the terms
+    big = (1 << 24) - 8
+    for sign in (1, -1):
+        x1 = np.array([[[[sign * big]]]])
+        with pytest.raises(AssertionError, match="2\\^24"):
+            yr.conv_exact(x1, np.array([[[[1]]]]), np.array([8]), 1, 0, False)
+        out, mag = yr.conv_exact(x1, np.array([[[[1]]]]), np.array([7 * sign]), 1, 0, False)
+        assert int(mag[0, 0, 0, 0]) == (1 << 24) - 1 and float(out[0, 0, 0, 0]) == sign * ((1 << 24) - 1)
+    # terms that cancel in the result still count
+    with pytest.raises(AssertionError, match="2\\^24"):
+        yr.conv_exact(np.array([[[[1 << 23]], [[1 << 23]]]]), np.array([[[[1]], [[-1]]]]), np.array([0]), 1, 0, False)
+    # values that are no integers
+    for bad in ((x + 0.5, w, b), (x, w * 0.25, b), (x, w, b + 0.1)):
+        with pytest.raises(AssertionError, match="integer"):
+            yr.conv_exact(*bad, 1, 1, False)
+    # and forward_exact holds a shortcut's sum to the same
+    body = [yr.conv_cfg(1, 1, 1, "linear", 0), "[shortcut]\nfrom=-1\nactivation=linear\n"]
+    _, layers = dk.parse_cfg(yr.net_cfg(1, body, 1, 1))
+    params = [(np.ones((1, 1, 1, 1)), np.zeros(1)), None]
+    outs = yr.forward_exact(layers, params, np.full((1, 1, 1, 1), (1 << 23) - 1))
+    assert outs[1].dtype == np.float32 and float(outs[1][0, 0, 0, 0]) == (1 << 24) - 2
+    with pytest.raises(AssertionError, match="shortcut"):
+        yr.forward_exact(layers, params, np.full((1, 1, 1, 1), 1 << 23))

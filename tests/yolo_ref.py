@@ -1,7 +1,9 @@
 """TEST ONLY: a plain float64 numpy restatement of the YOLOv3 object stage, independent of
 find_motion_amd's kernels and host tail: the blob with its integer arithmetic (imutils.resize's INTER_AREA from
 the oracle, cv2.resize's 8-bit INTER_LINEAR, the R/B swap and cvlib's 0.00392), the Darknet layers, the region
-layer's decode, cvlib's box loop and cv2.dnn.NMSBoxes.  Also the seeded miniature networks the tests run.
+layer's decode, cvlib's box loop and cv2.dnn.NMSBoxes.  Also the exact convolution of small integers (int64),
+the seeded miniature networks the tests run, and the one copy of the yolov3 and yolov3-tiny cfg generators, which
+tools/bench_yolo.py imports.
 """
 import math
 
@@ -80,6 +82,77 @@ def conv(x, w, b, stride, pad, leaky):
     if leaky:
         out = np.where(out > 0, out, 0.1 * out)
     return out.reshape(n, m, ho, wo), mag.reshape(n, m, ho, wo)
+
+
+def conv_exact(x, w, b, stride, pad, leaky):
+    """The convolution of integer-valued arrays in int64: (the exact result as float32 [n, m, ho, wo], the
+    magnitude sums sum |w x| + |b| as int64).  With `leaky` a negative result v becomes
+    np.float32(0.1) * np.float32(v): one f32 rounding, what the epilogue computes.  Refuses (AssertionError)
+    values that are no integers and any magnitude sum >= 2^24: below it every partial sum of an f32 fma chain,
+    in whatever order, is an integer below 2^24 and so exact, and the f32 result must equal this one bit for bit."""
+    xi, wi, bi = (np.asarray(a).astype(np.int64) for a in (x, w, b))
+    if not all(np.array_equal(i, np.asarray(a)) for i, a in ((xi, x), (wi, w), (bi, b))):
+        raise AssertionError("conv_exact takes integer-valued arrays")
+    n, c, H, W = xi.shape
+    m, _, s, _ = wi.shape
+    ho, wo = (H + 2 * pad - s) // stride + 1, (W + 2 * pad - s) // stride + 1
+    xp = np.zeros((n, c, H + 2 * pad, W + 2 * pad), np.int64)
+    xp[:, :, pad:pad + H, pad:pad + W] = xi
+    cols = np.empty((c, s, s, n, ho, wo), np.int64)
+    for ky in range(s):
+        for kx in range(s):
+            cols[:, ky, kx] = xp[:, :, ky:ky + stride * (ho - 1) + 1:stride,
+                                 kx:kx + stride * (wo - 1) + 1:stride].transpose(1, 0, 2, 3)
+    cols = cols.reshape(c * s * s, n * ho * wo)
+    wm = wi.reshape(m, c * s * s)
+    out = wm @ cols + bi[:, None]
+    mag = np.abs(wm) @ np.abs(cols) + np.abs(bi)[:, None]
+    if int(mag.max()) >= 1 << 24:
+        raise AssertionError(f"conv_exact: a magnitude sum of {int(mag.max())} is not below 2^24")
+    f = out.astype(np.float32)
+    if leaky:
+        f = np.where(out < 0, np.float32(0.1) * f, f).astype(np.float32)
+    shape = (m, n, ho, wo)
+    return f.reshape(shape).transpose(1, 0, 2, 3).copy(), mag.reshape(shape).transpose(1, 0, 2, 3).copy()
+
+
+def forward_exact(layers, params, x):
+    """Every layer's output as float32 from an integer-valued x [n, c, h, w] through integer parameters, each
+    one exact: the convolutions by conv_exact (which asserts its 2^24 condition), a shortcut's sum asserted
+    below 2^24 as well, the other layers moving values only."""
+    outs = []
+    prev = np.asarray(x, np.float32)
+    for ly in layers:
+        if ly["kind"] == dk.CONV:
+            w, b = params[ly["index"]]
+            prev, _ = conv_exact(prev, w, b, ly["stride"], ly["pad"], ly["activation"] == "leaky")
+        else:
+            prev, _ = layer(ly, params, prev, outs)
+            if ly["kind"] == dk.SHORTCUT:
+                big = np.abs(outs[ly["index"] - 1].astype(np.int64)) + np.abs(outs[ly["from"]].astype(np.int64))
+                if int(big.max()) >= 1 << 24:
+                    raise AssertionError(f"layer {ly['index']}: a shortcut's sum is not below 2^24")
+        assert prev.dtype == np.float32
+        outs.append(prev)
+    return outs
+
+
+def layer_shapes(layers, net_w, net_h):
+    """(channels, height, width) of every layer's output for a network input of net_w x net_h."""
+    out = []
+    for ly in layers:
+        h, w = out[-1][1:] if out else (net_h, net_w)
+        k = ly["kind"]
+        if k == dk.CONV:
+            h, w = ((v + 2 * ly["pad"] - ly["size"]) // ly["stride"] + 1 for v in (h, w))
+        elif k == dk.MAXPOOL and ly["stride"] == 2:
+            h, w = (h + 1) // 2, (w + 1) // 2
+        elif k == dk.UPSAMPLE:
+            h, w = 2 * h, 2 * w
+        elif k == dk.ROUTE:
+            h, w = out[ly["layers"][0]][1:]
+        out.append((ly["out_c"], h, w))
+    return out
 
 
 def maxpool(x, stride):
@@ -250,6 +323,49 @@ def mini_cfg() -> str:
         conv_cfg(24, 1, 1, "linear", 0),        # 15
         yolo_cfg("0,1,2"),                      # 16
     ])
+
+
+ANCHORS_TINY = "10,14, 23,27, 37,58, 81,82, 135,169, 344,319"
+ANCHORS = "10,13, 16,30, 33,23, 30,61, 62,45, 59,119, 116,90, 156,198, 373,326"
+
+
+def _head(mask, anchors, num, classes):
+    return [conv_cfg(3 * (classes + 5), 1, 1, "linear", 0),
+            f"[yolo]\nmask = {mask}\nanchors = {anchors}\nclasses={classes}\nnum={num}\njitter=.3\nignore_thresh = .7\n"
+            "truth_thresh = 1\nrandom=1\n"]
+
+
+def tiny_cfg(classes=80, width=416, height=416) -> str:
+    """yolov3-tiny.cfg's layer list, restated: 24 layers, 13 convolutions, heads at 1/32 and 1/16."""
+    pool = "[maxpool]\nsize=2\nstride=2\n"
+    body = []
+    for f in (16, 32, 64, 128, 256):
+        body += [conv_cfg(f, 3), pool]
+    body += [conv_cfg(512, 3), "[maxpool]\nsize=2\nstride=1\n", conv_cfg(1024, 3), conv_cfg(256, 1), conv_cfg(512, 3)]
+    body += _head("3,4,5", ANCHORS_TINY, 6, classes)
+    body += ["[route]\nlayers = -4\n", conv_cfg(128, 1), "[upsample]\nstride=2\n", "[route]\nlayers = -1, 8\n",
+             conv_cfg(256, 3)]
+    body += _head("0,1,2", ANCHORS_TINY, 6, classes)
+    return net_cfg(3, body, width, height)
+
+
+def full_cfg(classes=80, width=416, height=416) -> str:
+    """yolov3.cfg's layer list, restated: Darknet-53 (52 convolutions, 23 shortcuts) and three heads at 1/32,
+    1/16 and 1/8; 107 layers, 75 convolutions."""
+    res = "[shortcut]\nfrom=-3\nactivation=linear\n"
+    body = [conv_cfg(32, 3)]
+    for f, blocks in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
+        body.append(conv_cfg(f, 3, 2))
+        for _ in range(blocks):
+            body += [conv_cfg(f // 2, 1), conv_cfg(f, 3), res]
+    for f, mask, back in ((512, "6,7,8", None), (256, "3,4,5", 61), (128, "0,1,2", 36)):
+        if back is not None:
+            body += ["[route]\nlayers = -4\n", conv_cfg(f, 1), "[upsample]\nstride=2\n",
+                     f"[route]\nlayers = -1, {back}\n"]
+        for _ in range(3):
+            body += [conv_cfg(f, 1), conv_cfg(2 * f, 3)]
+        body += _head(mask, ANCHORS, 9, classes)
+    return net_cfg(3, body, width, height)
 
 
 def random_raw(layers, seed, gain=1.0, obj_bias=-4.0):

@@ -2,9 +2,10 @@
 """Time of the YOLOv3 object stage (fm_yolo_detect_frames) per call: 17 frames of 1080p -> INTER_AREA to
 width 300 -> 416 x 416 blob -> the network -> the decode.
 
-The layer list is yolov3-tiny's (or, with --model yolov3, the full Darknet-53 stack), restated here; the
-weights are random (no trained file is needed to time a network; the objectness biases are pushed down, yet how
-many rows the decode keeps -- `rows_kept` -- is an accident of the weights, not a trained network's few dozen).
+The layer list is yolov3-tiny's (or, with --model yolov3, the full Darknet-53 stack), from the generators the tests
+use (tests/yolo_ref.py); the weights are random (no trained file is needed to time a network; the objectness biases
+are pushed down, yet how many rows the decode keeps -- `rows_kept` -- is an accident of the weights, not a trained
+network's few dozen).
 Reported per call: ms per stage (HIP
 events), the convolutions' FLOPs over the network stage's time against the 157 TFLOP/s f32-matrix peak, and the
 same convolution stack through torch.nn.functional.conv2d in the same run -- a yardstick only: torch picks
@@ -22,49 +23,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))  # yolo_ref: the one copy of the two cfg generators
 
 PEAK_TFLOPS = 157.0  # f32-input MFMA, MI355X
-
-ANCHORS_TINY = "10,14, 23,27, 37,58, 81,82, 135,169, 344,319"
-ANCHORS = "10,13, 16,30, 33,23, 30,61, 62,45, 59,119, 116,90, 156,198, 373,326"
-
-
-def conv(filters, size, stride=1, act="leaky", bn=1):
-    return (f"[convolutional]\n{'batch_normalize=1' if bn else ''}\nfilters={filters}\nsize={size}\nstride={stride}\n"
-            f"pad=1\nactivation={act}\n")
-
-
-def yolo(mask, anchors, num):
-    return (f"[yolo]\nmask = {mask}\nanchors = {anchors}\nclasses=80\nnum={num}\njitter=.3\nignore_thresh = .7\n"
-            "truth_thresh = 1\nrandom=1\n")
-
-
-def tiny_cfg() -> str:
-    pool = "[maxpool]\nsize=2\nstride=2\n"
-    body = []
-    for f in (16, 32, 64, 128, 256):
-        body += [conv(f, 3), pool]
-    body += [conv(512, 3), "[maxpool]\nsize=2\nstride=1\n", conv(1024, 3), conv(256, 1), conv(512, 3),
-             conv(255, 1, 1, "linear", 0), yolo("3,4,5", ANCHORS_TINY, 6), "[route]\nlayers = -4\n", conv(128, 1),
-             "[upsample]\nstride=2\n", "[route]\nlayers = -1, 8\n", conv(256, 3), conv(255, 1, 1, "linear", 0),
-             yolo("0,1,2", ANCHORS_TINY, 6)]
-    return "[net]\nwidth=416\nheight=416\nchannels=3\n\n" + "\n".join(body)
-
-
-def full_cfg() -> str:
-    res = "[shortcut]\nfrom=-3\nactivation=linear\n"
-    body = [conv(32, 3)]
-    for f, blocks in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
-        body.append(conv(f, 3, 2))
-        for _ in range(blocks):
-            body += [conv(f // 2, 1), conv(f, 3), res]
-    for f, mask, back in ((512, "6,7,8", None), (256, "3,4,5", 61), (128, "0,1,2", 36)):
-        if back is not None:
-            body += ["[route]\nlayers = -4\n", conv(f, 1), "[upsample]\nstride=2\n", f"[route]\nlayers = -1, {back}\n"]
-        for _ in range(3):
-            body += [conv(f, 1), conv(2 * f, 3)]
-        body += [conv(255, 1, 1, "linear", 0), yolo(mask, ANCHORS, 9)]
-    return "[net]\nwidth=416\nheight=416\nchannels=3\n\n" + "\n".join(body)
 
 
 def random_params(layers, seed=0):
@@ -113,6 +74,8 @@ def main():
     a = ap.parse_args()
     import torch
     import torch.nn.functional as F
+
+    from yolo_ref import full_cfg, tiny_cfg
 
     from find_motion_amd import YoloDetector
     from find_motion_amd import darknet as dk
