@@ -20,6 +20,9 @@ LIB_PATH = os.environ.get("FM_HIP_LIB") or LIB_PATH  # unset or empty: the in-tr
 FM_OK, FM_EINVAL, FM_EHIP, FM_ENOMEM, FM_ESTATE, FM_ENOTSUP = 0, -1, -2, -3, -4, -5
 FM_FLAG_KEEP_PLANES, FM_FLAG_PROFILE, FM_FLAG_PROFILE_PIX, FM_FLAG_CONTOUR_AREA = 0x1, 0x2, 0x4, 0x8
 FM_FLAG_CONTOUR_POINTS = 0x10
+FM_FLAG_AREA_UPSCALE = 0x20
+RESIZE_IDENTITY, RESIZE_FAST, RESIZE_GENERAL, RESIZE_UP = 0, 1, 2, 3
+RESIZE_NAMES = ("identity", "area_fast", "area", "area_up")
 PLANE_GRAY, PLANE_BLUR, PLANE_DELTA, PLANE_SMALL = 0, 1, 2, 3
 
 EXPORTED = (
@@ -42,6 +45,7 @@ EXPORTED = (
     "fm_yolo_detect_frame_list", "fm_yolo_forward", "fm_yolo_decode", "fm_yolo_layer_output",
     "fm_yolo_route_in_place", "fm_yolo_last_ms",
     "fm_plan", "fm_read_threshold_bits",
+    "fm_resize_kind", "fm_area_up_taps", "fm_haar_set_roi_upscale", "fm_yolo_set_roi_upscale",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -147,6 +151,10 @@ def load() -> C.CDLL:
     L.fm_rasterize_masks.argtypes = [i32, i32, C.c_double, vp, vp, i32, vp]
     L.fm_max_inflight.argtypes = [vp]
     L.fm_plan.argtypes = [C.POINTER(FMParams), C.POINTER(FMPlan)]
+    L.fm_resize_kind.argtypes = [C.POINTER(FMParams), C.POINTER(i32)]
+    L.fm_area_up_taps.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.fm_haar_set_roi_upscale.argtypes = [vp, i32]
+    L.fm_yolo_set_roi_upscale.argtypes = [vp, i32]
     L.fm_last_fallbacks.argtypes = [vp]
     L.fm_last_ccl_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.fm_get_contour_points.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -264,30 +272,59 @@ def yuv_frame_bytes(width: int, height: int, fmt, pitch: int = 0, chroma_offset:
     return int(n.value)
 
 
-def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_points=False) -> int:
+def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_points=False,
+                 area_upscale=False) -> int:
     """fm_params.flags of MotionEngine's keyword arguments."""
     return ((FM_FLAG_KEEP_PLANES if keep_planes else 0) | (FM_FLAG_CONTOUR_AREA if contour_area else 0) |
-            (FM_FLAG_CONTOUR_POINTS if contour_points else 0) |
+            (FM_FLAG_CONTOUR_POINTS if contour_points else 0) | (FM_FLAG_AREA_UPSCALE if area_upscale else 0) |
             (FM_FLAG_PROFILE_PIX if profile == "pix" else FM_FLAG_PROFILE if profile else 0))
 
 
 def plan(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: int, threshold: int = 12,
          avg: float = 0.1, max_batch: int = 1, max_contours: int = 4096, keep_planes: bool = False,
          profile: bool | str = False, device: int = 0, contour_area: bool = False,
-         contour_points: bool = False) -> dict:
+         contour_points: bool = False, area_upscale: bool = False) -> dict:
     """What MotionEngine(**params) would set up, asked of the library without touching a device (fm_plan: the
     same validation and selection as fm_create): work_shape (h, w), tiles, max_inflight and pixel_path, one of
     "small", "pix", "fused", "wide" and "pixel" (the per-frame path: one batch in flight).  FMError as
     MotionEngine raises it for parameters the engine refuses."""
     L = load()
     p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg), max_batch,
-                 max_contours, engine_flags(keep_planes, profile, contour_area, contour_points))
+                 max_contours, engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale))
     out = FMPlan()
     rc = L.fm_plan(C.byref(p), C.byref(out))
     if rc != FM_OK:
         raise FMError(rc, L.fm_last_error(None).decode())
     return {"work_shape": (out.work_h, out.work_w), "tiles": out.tiles, "max_inflight": out.max_inflight,
             "pixel_path": out.pixel_path.decode()}
+
+
+def resize_kind(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: int, threshold: int = 12,
+                avg: float = 0.1, max_batch: int = 1, max_contours: int = 4096, keep_planes: bool = False,
+                profile: bool | str = False, device: int = 0, contour_area: bool = False,
+                contour_points: bool = False, area_upscale: bool = False) -> int:
+    """The resize MotionEngine(**params) would put in front of the pixel chain (fm_resize_kind: no device is
+    touched): RESIZE_IDENTITY, RESIZE_FAST, RESIZE_GENERAL, or RESIZE_UP for a box wider than the frame, which
+    needs area_upscale=True.  FMError as plan() raises it."""
+    L = load()
+    p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg), max_batch,
+                 max_contours, engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale))
+    kind = C.c_int32(-1)
+    rc = L.fm_resize_kind(C.byref(p), C.byref(kind))
+    if rc != FM_OK:
+        raise FMError(rc, L.fm_last_error(None).decode())
+    return int(kind.value)
+
+
+def area_up_taps(ssize: int, dsize: int):
+    """The enlarging resize's taps of one axis as the library builds them (fm_area_up_taps: host only):
+    int32 arrays s0, s1, a0, a1 of dsize values."""
+    L = load()
+    out = [np.zeros(max(int(dsize), 1), np.int32) for _ in range(4)]
+    rc = L.fm_area_up_taps(int(ssize), int(dsize), *[_ptr(a) for a in out])
+    if rc != FM_OK:
+        raise FMError(rc, L.fm_last_error(None).decode())
+    return tuple(out)
 
 
 @dataclass
@@ -326,11 +363,13 @@ class MotionEngine:
     def __init__(self, *, n_streams: int, src_w: int, src_h: int, box_size: int, ksize: int,
                  threshold: int, avg: float, max_batch: int = 1, max_contours: int = 4096,
                  keep_planes: bool = False, profile: bool | str = False, device: int = 0,
-                 contour_area: bool = False, contour_points: bool = False):
+                 contour_area: bool = False, contour_points: bool = False, area_upscale: bool = False):
+        # area_upscale: a box wider than the frame enlarges it, as imutils.resize does (else FM_ENOTSUP)
         # profile: True = every kernel timed with HIP events, "pix" = pixel-stream kernels only
         self._L = load()
         p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg),
-                     max_batch, max_contours, engine_flags(keep_planes, profile, contour_area, contour_points))
+                     max_batch, max_contours,
+                     engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale))
         h = C.c_void_p()
         rc = self._L.fm_create(C.byref(h), C.byref(p))
         if rc != FM_OK:
@@ -345,6 +384,9 @@ class MotionEngine:
         self._check(self._L.fm_plan(C.byref(p), C.byref(pl)))
         self.pixel_path = pl.pixel_path.decode()
         self.tiles = pl.tiles
+        kind = C.c_int32(-1)
+        self._check(self._L.fm_resize_kind(C.byref(p), C.byref(kind)))
+        self.resize_kind = int(kind.value)  # RESIZE_*
         self.n_streams = n_streams
         self.src_shape = (src_h, src_w, 3)
         self.device = int(device)
@@ -694,7 +736,8 @@ class CascadeClassifier:
     empty tuple when nothing is found, as cv2 does.  `detect_batch` runs many images of
     one size in one call (the ROI frames of many streams)."""
 
-    def __init__(self, path_or_cascade, device: int = 0):
+    def __init__(self, path_or_cascade, device: int = 0, roi_upscale: bool = False):
+        # roi_upscale: detect_frames enlarges frames narrower than roi_w, as imutils.resize does (else FM_ENOTSUP)
         from .cascade import Cascade, parse
         cs = path_or_cascade if isinstance(path_or_cascade, Cascade) else parse(path_or_cascade)
         self.cascade = cs
@@ -713,6 +756,11 @@ class CascadeClassifier:
             L.fm_haar_destroy(h)
             self._h = None
             raise FMError(rc, f"fm_haar_create: {msg}")
+        if roi_upscale:
+            self.set_roi_upscale(True)
+
+    def set_roi_upscale(self, on: bool) -> None:
+        load().fm_haar_set_roi_upscale(self._h, int(bool(on)))
 
     def empty(self) -> bool:
         return self._h is None
@@ -909,7 +957,8 @@ class YoloDetector:
     per frame.  The network input is 416 x 416 whatever the cfg's [net] says, as cvlib passes it."""
 
     def __init__(self, layers, params, classes, net_w: int = 416, net_h: int = 416, max_frames: int = 1,
-                 zero_thresh: float = 0.2, device: int = 0, channels=None):
+                 zero_thresh: float = 0.2, device: int = 0, channels=None, roi_upscale: bool = False):
+        # roi_upscale: frames narrower than roi_w are enlarged, as imutils.resize does (else FM_ENOTSUP)
         L = load()
         self.layers, self.classes = layers, list(classes)
         self.net_w, self.net_h, self.max_frames = int(net_w), int(net_h), int(max_frames)
@@ -922,9 +971,14 @@ class YoloDetector:
             L.fm_yolo_destroy(h)
             self._h = None
             raise FMError(rc, f"fm_yolo_create: {msg}")
+        if roi_upscale:
+            self.set_roi_upscale(True)
         rows = C.c_int()
         L.fm_yolo_layer_shape(self._h, -1, None, None, None, C.byref(rows))
         self.rows = rows.value  # candidate rows of all heads, per frame
+
+    def set_roi_upscale(self, on: bool) -> None:
+        load().fm_yolo_set_roi_upscale(self._h, int(bool(on)))
 
     @classmethod
     def from_dir(cls, directory, tiny: bool = False, device: int = 0, **kw):

@@ -97,6 +97,8 @@ struct fm_ctx {
     ResizeMode rmode = ResizeMode::Identity;
     int fast_sx = 1, fast_sy = 1;
     AreaAxis ax, ay;
+    AreaUpAxis upx, upy;  // FM_FLAG_AREA_UPSCALE: the enlarging resize's taps and its kernel's tiling
+    AreaUpPlan up_plan{};
     std::vector<int32_t> coef;
 
     // streams: pixel work (caller-replaceable), contour pass, synchronous reads
@@ -148,6 +150,7 @@ struct fm_ctx {
     int nquota = 0;                                             // nodes of each frame's quota
     int32_t *d_xofs = nullptr, *d_xcnt = nullptr, *d_yofs = nullptr, *d_ycnt = nullptr;
     float *d_xwt = nullptr, *d_ywt = nullptr;
+    uint32_t *d_upx = nullptr, *d_upy = nullptr;
 
     // batches
     BatchSlot slots[kSlots];
@@ -459,10 +462,15 @@ static int plan_context(fm_ctx* c, const fm_params& p) {
 
     // resize mode (cv::resize: copy if same size; INTER_AREA needs scale >= 1)
     const AreaMode m = area_resize_mode(p.src_w, p.src_h, c->w, c->h);
-    if (m.kind == AreaMode::Upscale)
+    if (m.kind == AreaMode::Upscale && !(p.flags & FM_FLAG_AREA_UPSCALE))
         return failf(kNoCtx, FM_ENOTSUP, "box_size %d > frame width %d: INTER_AREA upscaling is bilinear in OpenCV, not supported",
                      p.box_size, p.src_w);
     c->rmode = m.kind;
+    if (m.kind == AreaMode::Upscale) {
+        if (!build_area_up_axis(p.src_w, c->w, c->upx) || !build_area_up_axis(p.src_h, c->h, c->upy))
+            return failf(kNoCtx, FM_ENOTSUP, "frame %dx%d too large for the INTER_AREA upscaling tables", p.src_w, p.src_h);
+        c->up_plan = plan_area_up(c->upy, c->w);
+    }
     if (m.kind == AreaMode::Fast) c->fast_sx = m.isx, c->fast_sy = m.isy;
     if (m.kind == AreaMode::General &&
         (!build_area_axis(p.src_w, c->w, m.sx, c->ax) || !build_area_axis(p.src_h, c->h, m.sy, c->ay)))
@@ -509,6 +517,27 @@ int fm_plan(const fm_params* prm, struct fm_plan* out) {
     out->tiles = ((c.w + 63) / 64) * ((c.h + 63) / 64);
     out->max_inflight = c.nslots;
     std::snprintf(out->pixel_path, sizeof out->pixel_path, "%s", pixel_path_name(&c));
+    return FM_OK;
+}
+
+int fm_resize_kind(const fm_params* prm, int* kind) {
+    if (!prm || !kind) return failf(kNoCtx, FM_EINVAL, "null argument");
+    fm_ctx c;  // host fields only: nothing to release
+    if (int rc = plan_context(&c, *prm)) return rc;
+    *kind = c.rmode == ResizeMode::Identity ? FM_RESIZE_IDENTITY : c.rmode == ResizeMode::Fast ? FM_RESIZE_FAST
+            : c.rmode == ResizeMode::General ? FM_RESIZE_GENERAL : FM_RESIZE_UP;
+    return FM_OK;
+}
+
+int fm_area_up_taps(int ssize, int dsize, int32_t* s0, int32_t* s1, int32_t* a0, int32_t* a1) {
+    AreaUpAxis A;
+    if (!s0 || !s1 || !a0 || !a1) return failf(kNoCtx, FM_EINVAL, "null argument");
+    if (ssize < 1 || dsize < ssize) return failf(kNoCtx, FM_EINVAL, "not an enlarging axis (%d -> %d)", ssize, dsize);
+    if (!build_area_up_axis(ssize, dsize, A)) return failf(kNoCtx, FM_ENOTSUP, "axis of %d too large for the tables", ssize);
+    std::copy(A.s0.begin(), A.s0.end(), s0);
+    std::copy(A.s1.begin(), A.s1.end(), s1);
+    std::copy(A.a0.begin(), A.a0.end(), a0);
+    std::copy(A.a1.begin(), A.a1.end(), a1);
     return FM_OK;
 }
 
@@ -655,13 +684,14 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     FM_HIP_TRY(cp, hipMemset(c->d_has_keep, 0, S));
     FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * sizeof(double)));
     FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * sizeof(double)));
+    auto up = [&](auto** d, const auto& v) -> int {
+        int r = dalloc(cp, d, v.size());
+        if (r) return r;
+        hipError_t e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+        return e == hipSuccess ? 0 : failf(cp, FM_EHIP, "hipMemcpy tables: %s", hipGetErrorString(e));
+    };
+    if (c->rmode == ResizeMode::Upscale && ((rc = up(&c->d_upx, c->upx.tab)) || (rc = up(&c->d_upy, c->upy.tab)))) return rc;
     if (c->rmode == ResizeMode::General) {
-        auto up = [&](auto** d, const auto& v) -> int {
-            int r = dalloc(cp, d, v.size());
-            if (r) return r;
-            hipError_t e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-            return e == hipSuccess ? 0 : failf(cp, FM_EHIP, "hipMemcpy tables: %s", hipGetErrorString(e));
-        };
         if ((rc = up(&c->d_xofs, c->ax.ofs)) || (rc = up(&c->d_xcnt, c->ax.cnt)) || (rc = up(&c->d_xwt, c->ax.wt)) ||
             (rc = up(&c->d_yofs, c->ay.ofs)) || (rc = up(&c->d_ycnt, c->ay.cnt)) || (rc = up(&c->d_ywt, c->ay.wt)))
             return rc;
@@ -899,6 +929,11 @@ int resize_input(fm_ctx* c, BatchSlot& B, hipStream_t rs, const uint8_t* src, si
         FM_HIP_TRY(c, c->timer.timed(rs, "resize_area_fast", [&](uint64_t* ks, uint64_t*) {
             return launch_resize_area_fast(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->fast_sx,
                                            c->fast_sy, ks);
+        }));
+    else if (c->rmode == ResizeMode::Upscale)
+        FM_HIP_TRY(c, c->timer.timed(rs, "resize_area_up", [&](uint64_t* ks, uint64_t*) {
+            return launch_resize_area_up(rs, src, B.d_work, (int)F, c->p.src_h, c->p.src_w, c->h, c->w, c->d_upx, c->d_upy,
+                                         c->up_plan, nullptr, ks);
         }));
     return FM_OK;
 }

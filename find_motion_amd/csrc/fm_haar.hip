@@ -1190,6 +1190,12 @@ double fm_haar_last_ms(const fm_haar* h) { return h ? h->last_ms : 0.; }
 
 int fm_haar_last_sweep(const fm_haar* h) { return h ? h->last_sweep : 0; }
 
+int fm_haar_set_roi_upscale(fm_haar* h, int on) {
+    if (!h) return FM_EINVAL;
+    h->roi.allow_upscale(on != 0);
+    return FM_OK;
+}
+
 }  // extern "C"
 
 // find_objects' resize + detect over n frames: consecutive [n][H][W][3] frames at `frames` (host memory,

@@ -198,6 +198,21 @@ hipError_t launch_resize_area(hipStream_t st, const uint8_t* src, uint8_t* dst, 
                               int ytaps, const uint8_t* const* srcs = nullptr, uint64_t* kstamp = nullptr);
 hipError_t launch_resize_area_fast(hipStream_t st, const uint8_t* src, uint8_t* dst, int F, int H, int W,
                                    int h, int w, int sx, int sy, uint64_t* kstamp = nullptr);
+// INTER_AREA towards a larger image (cv::resize's bilinear resizer with area-mode taps; fm_roi.h builds xtab / ytab
+// and the plan).  A workgroup takes `rows` destination rows of a span of `cols` destination columns (nspans spans
+// per row) and holds the source bytes and the horizontal results of at most `nsrc` source rows in `lds` bytes of LDS.
+struct AreaUpPlan {
+    int rows, cols, nspans, nsrc, lds;
+};
+// 16-bit elements between two rows of horizontal results in LDS: the span's 3 * cols, two more that a lane's
+// third dword may reach into, rows dword-aligned
+__host__ __device__ constexpr int area_up_hstride(int cols) { return (3 * cols + 3) & ~1; }
+// bytes between two rows of staged source bytes: up to cols + 1 source pixels from up to 3 bytes into the first
+// dword, and the 12 bytes a lane reads from the dword of its first tap on
+__host__ __device__ constexpr int area_up_rawstride(int cols) { return (3 * (cols + 1) + 15) & ~3; }
+hipError_t launch_resize_area_up(hipStream_t st, const uint8_t* src, uint8_t* dst, int F, int H, int W, int h, int w,
+                                 const uint32_t* xtab, const uint32_t* ytab, const AreaUpPlan& plan,
+                                 const uint8_t* const* srcs = nullptr, uint64_t* kstamp = nullptr);
 hipError_t launch_pixel(hipStream_t st, const PixelArgs& a);
 // YUV frames -> packed BGR [F][H][W][3] (fm_yuv.hip).  Frame f is at srcs[f] (a device table of F
 // addresses) when srcs is set, at src + f * frame_stride otherwise; pitch / chroma_offset as resolved

@@ -2,6 +2,7 @@
 //
 // Stage map (reference = find_motion/find_motion.py, "fm.py"):
 //   k_resize_area / k_resize_area_fast   imutils.resize(INTER_AREA)        fm.py:492
+//   k_resize_area_up                     the same towards a larger image   fm.py:492
 //   k_pixel                              cvtColor, GaussianBlur, mask,     fm.py:493-494, 619-662
 //                                        convertScaleAbs+absdiff,
 //                                        threshold, accumulateWeighted,
@@ -333,6 +334,194 @@ hipError_t launch_resize_area_fast(hipStream_t st, const uint8_t* src, uint8_t* 
     dim3 grid((n + 255) / 256, F);
     const float inv_area = 1.f / (float)(sx * sy);
     hipLaunchKernelGGL(k_resize_area_fast, grid, dim3(256), 0, st, src, dst, H, W, h, w, sx, sy, inv_area, kstamp);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// INTER_AREA towards a larger image: cv::resize's 8-bit bilinear resizer with area-mode taps (fm_roi.cpp builds
+// them).  All integer: D = S[s0] * a0 + S[s1] * a1 per source row, dst = (((b0 * (D0 >> 4)) >> 16) + ((b1 *
+// (D1 >> 4)) >> 16) + 2) >> 2.  The output is the larger side, so the kernel is shaped by its stores.
+//
+// A workgroup takes p.rows destination rows of one span of p.cols destination columns of one frame:
+//   1. the span's column table (s0 << 12 | a1 per destination column) and the band's row table go to LDS;
+//   2. the source bytes the span reads, of every source row the band reads, go to LDS: aligned dword loads, all
+//      of a thread's loads in flight before the first is stored (one byte load per lane and tap left a wave
+//      waiting for memory once per element: 1.28 ms per 64 frames of 1280 x 720 -> 1920 x 1080); a dword that is
+//      not wholly inside the frame is put together from the bytes that are, so no read passes a frame's last byte
+//      or precedes its first;
+//   3. the horizontal results D >> 4 (16 bits) go to LDS, once per source row however many destination rows use
+//      it, a lane per destination pixel: its two source pixels are six consecutive bytes (where the first tap is
+//      the row's last pixel the second coefficient is 0, so what follows it in LDS is multiplied by 0);
+//   4. each lane takes one aligned dword of the destination (aligned in memory: a row starts at any byte when
+//      3 * w is no multiple of 4) and stores it whole, a wave 256 contiguous bytes per store.  Where the span is
+//      the full width the band's rows are one contiguous range and a dword may run from one row into the next;
+//      a dword that the range only partly covers (its two ends, shared with the neighbouring workgroup) is
+//      stored by bytes.  A lane's four horizontal results are 8 bytes of LDS at a 2-byte alignment, read as
+//      three dwords (lanes 8 bytes apart: two lanes per bank) and shifted into place.
+// (Workgroups of 1,024 threads, two a CU, took 0.77 ms where these take 0.61 ms per 64 frames of 1280 x 720 ->
+// 1920 x 1080: more waves per CU did not help.  DESIGN.md 3.3.)
+constexpr int RU_T = 256;
+
+struct RuRow {
+    const uint16_t *h0, *h1;  // the row's two source rows of horizontal results
+    uint32_t b0, b1;
+};
+__device__ __forceinline__ RuRow ru_row(const uint32_t* yt, const uint16_t* Hs, int r, int sr0, int H, int hstride) {
+    const uint32_t ty = yt[r];
+    const int s0 = (int)(ty >> 12), s1 = min(s0 + 1, H - 1);
+    const uint32_t b1 = ty & 0xfffu;
+    return {Hs + (s0 - sr0) * hstride, Hs + (s1 - sr0) * hstride, 2048u - b1, b1};
+}
+__device__ __forceinline__ uint32_t ru_value(uint32_t d0, uint32_t d1, uint32_t b0, uint32_t b1) {
+    return (((b0 * d0) >> 16) + ((b1 * d1) >> 16) + 2u) >> 2;
+}
+
+__global__ __launch_bounds__(RU_T) void k_resize_area_up(const uint8_t* __restrict__ src,
+                                                         const uint8_t* const* __restrict__ srcs,
+                                                         uint8_t* __restrict__ dst, int H, int W, int h, int w,
+                                                         const uint32_t* __restrict__ xtab,
+                                                         const uint32_t* __restrict__ ytab, AreaUpPlan p,
+                                                         uint64_t* kstamp) {
+    kstamp_begin_grid(kstamp);
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint32_t* xt = reinterpret_cast<uint32_t*>(lds);          // [p.cols]
+    uint32_t* yt = xt + p.cols;                               // [p.rows]
+    uint16_t* Hs = reinterpret_cast<uint16_t*>(yt + p.rows);  // [p.nsrc][hstride], rows dword-aligned
+    const int tid = threadIdx.x;
+    const int band = blockIdx.x / p.nspans, span = blockIdx.x - band * p.nspans;
+    const int y0 = band * p.rows, ny = min(p.rows, h - y0);
+    const int x0 = span * p.cols, nx = min(p.cols, w - x0);
+    const int segb = 3 * nx, hstride = area_up_hstride(p.cols);
+    const size_t f = blockIdx.y, rowb = (size_t)3 * w;
+    const uint8_t* S = srcs ? srcs[f] : src + f * (size_t)H * W * 3;
+
+    for (int i = tid; i < nx; i += RU_T) xt[i] = xtab[x0 + i];
+    for (int i = tid; i < ny; i += RU_T) yt[i] = ytab[y0 + i];
+    __syncthreads();
+    const int sr0 = (int)(yt[0] >> 12);
+    const int ns = min((int)(yt[ny - 1] >> 12) + 1, H - 1) - sr0 + 1;
+    if (ns > p.nsrc) return;  // (the plan covers every band: never taken)
+    const int rstride = area_up_rawstride(p.cols);  // bytes between two rows of source bytes, a multiple of 4
+    uint32_t* raw = reinterpret_cast<uint32_t*>(Hs + p.nsrc * hstride);  // [p.nsrc][rstride / 4]
+
+    // the span's source columns c0 .. c1 of the band's source rows -> raw: row j holds the dwords from the aligned
+    // address at or below the row segment's first byte, which lies lead(j) bytes into the first
+    const int c0 = (int)(xt[0] >> 12), c1 = min((int)(xt[nx - 1] >> 12) + 1, W - 1);
+    const int rawb = 3 * (c1 - c0 + 1);
+    if (rawb + 12 > rstride) return;  // (at most cols + 1 source columns: never taken)
+    const int ndw = (rawb + 6) >> 2, total = ns * ndw;
+    const uint8_t* Send = S + (size_t)H * W * 3;
+    const uint8_t* G0 = S + (size_t)sr0 * W * 3 + (size_t)3 * c0;
+    const float dinv = 1.f / (float)ndw;
+    constexpr int RU_U = 4;
+    for (int base = 0; base < total; base += RU_T * RU_U) {
+        uint32_t v[RU_U];
+        int at[RU_U];
+#pragma unroll
+        for (int u = 0; u < RU_U; u++) {
+            const int idx = base + u * RU_T + tid;
+            at[u] = -1;
+            v[u] = 0;
+            if (idx < total) {
+                int j = (int)((float)idx * dinv);  // idx / ndw (idx < 2^24: off by one at most)
+                j -= j * ndw > idx;
+                j += (j + 1) * ndw <= idx;
+                const int i = idx - j * ndw;
+                const uint8_t* G = G0 + (size_t)j * W * 3;
+                const uint8_t* q = G - ((uintptr_t)G & 3) + 4 * i;
+                if (q >= S && q + 4 <= Send) {
+                    v[u] = *reinterpret_cast<const uint32_t*>(q);
+                } else {
+                    for (int b = 0; b < 4; b++)
+                        if (q + b >= S && q + b < Send) v[u] |= (uint32_t)q[b] << (8 * b);
+                }
+                at[u] = j * (rstride >> 2) + i;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RU_U; u++)
+            if (at[u] >= 0) raw[at[u]] = v[u];
+    }
+    __syncthreads();
+
+    // horizontal pass: every source row of the band, once; a lane per destination pixel
+    for (int j = 0; j < ns; j++) {
+        const int lead = (int)((uintptr_t)(G0 + (size_t)j * W * 3) & 3);
+        const uint32_t* Rj = raw + j * (rstride >> 2);
+        uint16_t* Hj = Hs + j * hstride;
+        for (int dx = tid; dx < nx; dx += RU_T) {
+            const uint32_t t = xt[dx];
+            const uint32_t a1 = t & 0xfffu, a0 = 2048u - a1;
+            const int off = lead + 3 * ((int)(t >> 12) - c0);
+            const uint32_t* q = Rj + (off >> 2);
+            const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
+            const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)off & 3u);  // bytes off .. off + 3
+            const uint32_t hi = __builtin_amdgcn_alignbyte(d2, d1, (uint32_t)off & 3u);  // bytes off + 4 .. off + 7
+            uint16_t* o = Hj + 3 * dx;
+            o[0] = (uint16_t)(((lo & 0xffu) * a0 + (lo >> 24) * a1) >> 4);
+            o[1] = (uint16_t)((((lo >> 8) & 0xffu) * a0 + (hi & 0xffu) * a1) >> 4);
+            o[2] = (uint16_t)((((lo >> 16) & 0xffu) * a0 + ((hi >> 8) & 0xffu) * a1) >> 4);
+        }
+    }
+    __syncthreads();
+
+    // vertical pass and stores.  Segments: the whole band when the span is the full width, else one per row
+    const bool merged = p.nspans == 1;
+    const int nseg = merged ? 1 : ny;
+    const int seglen = merged ? ny * segb : segb;
+    const float rinv = 1.f / (float)segb;
+    uint8_t* band0 = dst + (f * h + y0) * rowb + (size_t)3 * x0;
+    for (int sg = 0; sg < nseg; sg++) {
+        uint8_t* A = band0 + (size_t)sg * rowb;
+        const int lead = (int)((uintptr_t)A & 3);  // the segment starts `lead` bytes into its first dword
+        const int nch = (lead + seglen + 3) >> 2;
+        for (int ch = tid; ch < nch; ch += RU_T) {
+            const int p0 = ch * 4 - lead;  // the dword's first byte, relative to the segment
+            const int pb = max(p0, 0), pe = min(p0 + 4, seglen);
+            int r = sg;
+            if (merged) {  // pb / segb (pb < 2^24: exact in float, the quotient off by one at most)
+                r = (int)((float)pb * rinv);
+                r -= r * segb > pb;
+                r += (r + 1) * segb <= pb;
+            }
+            int e = merged ? pb - r * segb : pb;
+            RuRow rw = ru_row(yt, Hs, r, sr0, H, hstride);
+            if (pe - pb == 4 && e + 4 <= segb) {
+                const int eb = e & ~1;
+                const uint32_t sh = (uint32_t)(e & 1) * 16u;
+                const uint32_t* q0 = reinterpret_cast<const uint32_t*>(rw.h0 + eb);
+                const uint32_t* q1 = reinterpret_cast<const uint32_t*>(rw.h1 + eb);
+                const uint32_t u0 = q0[0], u1 = q0[1], u2 = q0[2], v0 = q1[0], v1 = q1[1], v2 = q1[2];
+                const uint32_t ul = __builtin_amdgcn_alignbit(u1, u0, sh), uh = __builtin_amdgcn_alignbit(u2, u1, sh);
+                const uint32_t vl = __builtin_amdgcn_alignbit(v1, v0, sh), vh = __builtin_amdgcn_alignbit(v2, v1, sh);
+                const uint32_t out = ru_value(ul & 0xffffu, vl & 0xffffu, rw.b0, rw.b1) |
+                                     ru_value(ul >> 16, vl >> 16, rw.b0, rw.b1) << 8 |
+                                     ru_value(uh & 0xffffu, vh & 0xffffu, rw.b0, rw.b1) << 16 |
+                                     ru_value(uh >> 16, vh >> 16, rw.b0, rw.b1) << 24;
+                *reinterpret_cast<uint32_t*>(A + p0) = out;
+            } else {
+                for (int q = pb; q < pe; q++) {
+                    A[q] = (uint8_t)ru_value(rw.h0[e], rw.h1[e], rw.b0, rw.b1);
+                    if (++e == segb && q + 1 < pe) {  // (full-width spans only) into the next row
+                        e = 0;
+                        rw = ru_row(yt, Hs, ++r, sr0, H, hstride);
+                    }
+                }
+            }
+        }
+    }
+    kstamp_end_wg(kstamp);
+}
+
+hipError_t launch_resize_area_up(hipStream_t st, const uint8_t* src, uint8_t* dst, int F, int H, int W, int h, int w,
+                                 const uint32_t* xtab, const uint32_t* ytab, const AreaUpPlan& p,
+                                 const uint8_t* const* srcs, uint64_t* kstamp) {
+    if (p.rows < 1 || p.cols < 1 || (long long)p.nspans * p.cols < w || p.lds > 64 * 1024 ||
+        p.lds < 4 * p.cols + 4 * p.rows + p.nsrc * (2 * area_up_hstride(p.cols) + area_up_rawstride(p.cols)))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((h + p.rows - 1) / p.rows) * p.nspans), F);
+    (void)hipFuncSetAttribute((const void*)k_resize_area_up, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+    hipLaunchKernelGGL(k_resize_area_up, grid, dim3(RU_T), p.lds, st, src, srcs, dst, H, W, h, w, xtab, ytab, p, kstamp);
     return hipGetLastError();
 }
 

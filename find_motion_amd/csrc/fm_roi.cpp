@@ -20,6 +20,53 @@ AreaMode area_resize_mode(int src_w, int src_h, int dst_w, int dst_h) {
     return m;
 }
 
+bool build_area_up_axis(int ssize, int dsize, AreaUpAxis& A) {
+    if (ssize < 1 || dsize < 1 || ssize >= (1 << 20)) return false;
+    A.s0.resize(dsize), A.s1.resize(dsize), A.a0.resize(dsize), A.a1.resize(dsize), A.tab.resize(dsize);
+    const double inv = (double)dsize / ssize, scale = 1. / inv;
+    for (int dx = 0; dx < dsize; dx++) {
+        int sx = (int)std::floor(dx * scale);
+        float fx = (float)((dx + 1) - (sx + 1) * inv);
+        fx = fx <= 0 ? 0.f : fx - std::floor(fx);
+        if (sx < 0) sx = 0, fx = 0.f;
+        if (sx >= ssize - 1) sx = ssize - 1, fx = 0.f;
+        A.s0[dx] = sx;
+        A.s1[dx] = std::min(sx + 1, ssize - 1);
+        A.a0[dx] = (int16_t)std::lrintf((1.f - fx) * 2048.f);  // cvRound: to nearest, ties to even
+        A.a1[dx] = (int16_t)std::lrintf(fx * 2048.f);
+        A.tab[dx] = (uint32_t)sx << 12 | (uint32_t)A.a1[dx];
+    }
+    return true;
+}
+
+// The source rows a band of r destination rows reads: from its first row's first tap to its last row's second.
+static int band_source_rows(const AreaUpAxis& ay, int r) {
+    const int h = (int)ay.s0.size();
+    int ns = 1;
+    for (int y0 = 0; y0 < h; y0 += r) ns = std::max(ns, ay.s1[std::min(y0 + r, h) - 1] - ay.s0[y0] + 1);
+    return ns;
+}
+
+AreaUpPlan plan_area_up(const AreaUpAxis& ay, int w) {
+    // spans of at most 1,024 columns, equal to within one; then as many rows (up to 32) as keep the column table
+    // and the rows' source bytes and 16-bit horizontal results within 48 KiB, so that three workgroups fit a CU's LDS
+    constexpr int kMaxCols = 1024, kMaxRows = 32, kLds = 48 * 1024;
+    AreaUpPlan p{};
+    p.nspans = (w + kMaxCols - 1) / kMaxCols;
+    p.cols = (w + p.nspans - 1) / p.nspans;
+    p.nspans = (w + p.cols - 1) / p.cols;
+    auto lds = [&](int r, int ns) { return 4 * p.cols + 4 * r + ns * (2 * area_up_hstride(p.cols) + area_up_rawstride(p.cols)); };
+    p.rows = 1;
+    for (int r = std::min<int>(kMaxRows, (int)ay.s0.size()); r > 1; r--)
+        if (lds(r, band_source_rows(ay, r)) <= kLds) {
+            p.rows = r;
+            break;
+        }
+    p.nsrc = band_source_rows(ay, p.rows);
+    p.lds = lds(p.rows, p.nsrc);
+    return p;
+}
+
 // one tap table at its exact size
 template <class T>
 static hipError_t upload(DevBuf<T>& b, const std::vector<T>& v) {
@@ -34,7 +81,7 @@ int RoiStage::run(std::string* err, hipStream_t st, const uint8_t* frames, const
     if (roi_h) *roi_h = rh;
     if (rh < 1) return failf(err, FM_EINVAL, "ROI height 0 for a %dx%d frame", W, H);
     const AreaMode m = area_resize_mode(W, H, rw, rh);
-    if (m.kind == AreaMode::Upscale)
+    if (m.kind == AreaMode::Upscale && !allow_upscale_)
         return failf(err, FM_ENOTSUP, "frame width %d < ROI width %d: INTER_AREA upscaling is not supported", W, rw);
     const size_t fb = (size_t)H * W * 3;
     const uint8_t* src = frames;
@@ -72,6 +119,21 @@ int RoiStage::run(std::string* err, hipStream_t st, const uint8_t* frames, const
         if (dlist)
             if (int rc = gather()) return rc;
         FM_HIP_TRY(err, launch_resize_area_fast(st, src, roi_.get(), n, H, W, rh, rw, m.isx, m.isy));
+    } else if (m.kind == AreaMode::Upscale) {
+        const int key[4] = {W, H, rw, rh};
+        if (!std::equal(key, key + 4, area_key_)) {
+            area_key_[0] = 0;
+            AreaUpAxis ux, uy;
+            if (!build_area_up_axis(W, rw, ux) || !build_area_up_axis(H, rh, uy))
+                return failf(err, FM_ENOTSUP, "frame %dx%d too large for the INTER_AREA upscaling tables", W, H);
+            FM_HIP_TRY(err, hipStreamSynchronize(st));
+            FM_HIP_TRY(err, upload(upx_, ux.tab));
+            FM_HIP_TRY(err, upload(upy_, uy.tab));
+            up_ = plan_area_up(uy, rw);
+            std::copy(key, key + 4, area_key_);
+        }
+        // (a frame list is read where its frames lie)
+        FM_HIP_TRY(err, launch_resize_area_up(st, src, roi_.get(), n, H, W, rh, rw, upx_.get(), upy_.get(), up_, dlist));
     } else {
         const int key[4] = {W, H, rw, rh};
         if (!std::equal(key, key + 4, area_key_)) {

@@ -613,6 +613,12 @@ void fm_yolo_destroy(fm_yolo* h) { delete h; }
 
 const char* fm_yolo_last_error(const fm_yolo* h) { return h ? h->err.c_str() : "null detector"; }
 
+int fm_yolo_set_roi_upscale(fm_yolo* h, int on) {
+    if (!h) return FM_EINVAL;
+    h->roi.allow_upscale(on != 0);
+    return FM_OK;
+}
+
 int fm_yolo_layer_shape(const fm_yolo* h, int layer, int* c, int* hh, int* w, int* rows) {
     if (!h || h->L.empty() || layer < -1 || layer >= (int)h->L.size()) return FM_EINVAL;
     if (c) *c = layer < 0 ? h->channels : h->L[layer].C;

@@ -74,7 +74,7 @@ from collections import deque
 import numpy as np
 
 from . import videoio
-from ._native import (PLANE_BLUR, PLANE_DELTA, PLANE_GRAY, CascadeClassifier, FMError, MJpegDecoder, MotionEngine,
+from ._native import (PLANE_BLUR, PLANE_DELTA, PLANE_GRAY, RESIZE_NAMES, CascadeClassifier, FMError, MJpegDecoder, MotionEngine,
                       YoloDetector, rasterize_masks)
 from .feeder import BatchFeeder
 
@@ -103,6 +103,13 @@ CASCADE_LOOKUP = {
 
 class VideoError(Exception):
     """fm.py:173-178"""
+
+
+def _roi_upscale(det):
+    """find_objects enlarges frames narrower than its ROI width, as imutils.resize does: the detector's switch on."""
+    if hasattr(det, "set_roi_upscale"):
+        det.set_roi_upscale(True)
+    return det
 
 
 def make_gaussian_size(box_size: int, blur_scale: int) -> int:
@@ -332,7 +339,7 @@ class VideoMotion:
                 continue
             key = (os.path.realpath(path), self.device)
             if key not in _CASCADES:  # one device copy per file and device, shared by every stream
-                _CASCADES[key] = CascadeClassifier(path, device=self.device)
+                _CASCADES[key] = _roi_upscale(CascadeClassifier(path, device=self.device))
             self.cascades[title] = _CASCADES[key]
 
     def _calc_min_area(self) -> None:
@@ -364,7 +371,9 @@ class VideoMotion:
                                         box_size=self.box_size, ksize=self.gaussian[0], threshold=self.delta_thresh,
                                         avg=self.avg, max_batch=self.batch, keep_planes=self.keep_planes,
                                         device=self.device, contour_area=self.area_filter,
-                                        **({"contour_points": True} if self.contour_points else {}))
+                                        **({"contour_points": True} if self.contour_points else {}),
+                                        # a box wider than the frame enlarges it, as imutils.resize does
+                                        **({"area_upscale": True} if self.box_size > self.frame_width else {}))
         self._log_pixel_path()
         if self.mask_areas:
             h, w = self._engine.work_shape
@@ -382,8 +391,10 @@ class VideoMotion:
             return
         h, w = self._engine.work_shape
         k = self.gaussian[0]
-        self.log.info("%s: %d x %d work image, Gaussian %d: pixel path '%s', %d batch(es) in flight", self.filename,
-                      w, h, k, path, getattr(self._engine, "max_inflight", 1))
+        kind = getattr(self._engine, "resize_kind", None)
+        resize = RESIZE_NAMES[kind] if kind is not None else "unknown"
+        self.log.info("%s: %d x %d work image (resize '%s'), Gaussian %d: pixel path '%s', %d batch(es) in flight",
+                      self.filename, w, h, resize, k, path, getattr(self._engine, "max_inflight", 1))
         if path != "pixel":
             return
         tiles = getattr(self._engine, "tiles", ((w + 63) // 64) * ((h + 63) // 64))
@@ -409,7 +420,7 @@ class VideoMotion:
         key = tuple(os.path.realpath(f) for f in files) + (self.device,)
         if key not in _YOLOS:  # one device copy per file set and device, shared by every stream
             try:
-                _YOLOS[key] = YoloDetector.from_dir(self.yolo_dir, tiny=self.tiny, device=self.device)
+                _YOLOS[key] = _roi_upscale(YoloDetector.from_dir(self.yolo_dir, tiny=self.tiny, device=self.device))
             except (ValueError, OSError, FMError) as e:
                 self.log.warning("YOLO files in %s refused (%s): object detection skipped", self.yolo_dir, e)
                 return
@@ -819,7 +830,8 @@ class StreamGroup:
         self.engine = make(n_streams=S, src_w=W, src_h=H, box_size=box, ksize=make_gaussian_size(box, blur_scale),
                            threshold=kwargs.get("threshold", 7), avg=kwargs.get("avg", 0.1), max_batch=self.batch,
                            keep_planes=show or dbg, device=device, contour_area=area_filter,
-                           **({"contour_points": True} if kwargs.get("contour_points") else {}))
+                           **({"contour_points": True} if kwargs.get("contour_points") else {}),
+                           **({"area_upscale": True} if box > W else {}))
         self.videos = [VideoMotion(filename=f, capture=c, engine=self.engine, stream=s, batch=self.batch, **kwargs)
                        for s, (f, c) in enumerate(zip(self.filenames, caps))]
 

@@ -51,13 +51,17 @@ extern "C" {
                                         (fm.py:269-272): fm_contour.npts, fm_get_contour_points.  area2 is filled
                                         too (the count pass has it; FM_FLAG_CONTOUR_AREA need not be set and
                                         starts no second trace).  Off: no kernel, buffer or result differs */
+#define FM_FLAG_AREA_UPSCALE 0x20u /* accept box_size > src_w: imutils.resize(raw, width=box) enlarges the frame
+                                      (fm.py:490), and cv2.resize(INTER_AREA) then runs its 8-bit bilinear resizer
+                                      with area-mode taps (the kernel `resize_area_up`).  Off: FM_ENOTSUP for such
+                                      a box, as before; no kernel, buffer, result or status differs */
 
 /* planes for fm_read_plane */
 #define FM_PLANE_GRAY 0  /* VideoFrame.gray        (fm.py:493) */
 #define FM_PLANE_BLUR 1  /* VideoFrame.blur, masked (fm.py:494, 619-636) */
 #define FM_PLANE_DELTA 2 /* VideoFrame.frame_delta (fm.py:250) */
-#define FM_PLANE_SMALL 3 /* the INTER_AREA-resized BGR frame `small` (fm.py:490), h*w*3 bytes; resize modes only,
-                            no FM_FLAG_KEEP_PLANES needed */
+#define FM_PLANE_SMALL 3 /* the INTER_AREA-resized BGR frame `small` (fm.py:490), h*w*3 bytes; resize modes only
+                            (the enlarged frame under FM_FLAG_AREA_UPSCALE), no FM_FLAG_KEEP_PLANES needed */
 
 typedef struct fm_ctx fm_ctx;
 
@@ -111,6 +115,18 @@ struct fm_plan {
     char pixel_path[16];
 };
 int fm_plan(const fm_params* params, struct fm_plan* out);
+
+/* Which resize fm_create would set up in front of the pixel chain, without touching a device; fm_plan's
+ * validation and status codes (FM_RESIZE_UP only with FM_FLAG_AREA_UPSCALE, FM_ENOTSUP for such a box without). */
+#define FM_RESIZE_IDENTITY 0 /* box_size = src_w: the frame is the work image */
+#define FM_RESIZE_FAST 1     /* INTER_AREA by whole factors */
+#define FM_RESIZE_GENERAL 2  /* INTER_AREA, any shrinking factors */
+#define FM_RESIZE_UP 3       /* box_size > src_w: the enlarging resize */
+int fm_resize_kind(const fm_params* params, int* kind);
+/* The enlarging resize's taps for one axis of ssize source and dsize >= ssize destination elements, as the engine
+ * and the detectors build them (host only): per destination index the two source indices and their 11-bit
+ * coefficients (a0 + a1 = 2048), dsize values each. */
+int fm_area_up_taps(int ssize, int dsize, int32_t* s0, int32_t* s1, int32_t* a0, int32_t* a1);
 
 /* Last error message for ctx (or the calling thread's last error if ctx is NULL). */
 const char* fm_last_error(const fm_ctx* ctx);
@@ -302,7 +318,10 @@ int fm_haar_detect(fm_haar* det, const uint8_t* images, int n, int H, int W, int
 /* find_objects (find_motion.py:703-731) on raw frames: each [H][W][3] BGR
  * frame is resized to width roi_w with INTER_AREA on the device
  * (imutils.resize: height int(H * roi_w / W), *roi_h_out), then detected as
- * fm_haar_detect with default min/max sizes.  FM_ENOTSUP when W < roi_w. */
+ * fm_haar_detect with default min/max sizes.  FM_ENOTSUP when W < roi_w, unless
+ * fm_haar_set_roi_upscale allowed it. */
+int fm_haar_set_roi_upscale(fm_haar* det, int on); /* on: frames narrower than roi_w are enlarged as
+                                                      FM_FLAG_AREA_UPSCALE enlarges them; off (default): refused */
 int fm_haar_detect_frames(fm_haar* det, const uint8_t* frames, int n, int H, int W, int on_device, int roi_w,
                           double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts,
                           int* roi_h_out);
@@ -545,12 +564,14 @@ typedef struct fm_yolo_desc {
 int fm_yolo_create(int device, const fm_yolo_desc* desc, fm_yolo** out);
 void fm_yolo_destroy(fm_yolo* det);
 const char* fm_yolo_last_error(const fm_yolo* det);
+/* on: frames narrower than roi_w are enlarged as FM_FLAG_AREA_UPSCALE enlarges them; off (default): FM_ENOTSUP */
+int fm_yolo_set_roi_upscale(fm_yolo* det, int on);
 /* Layer `layer`'s output shape (-1: the network input); total candidate rows of all heads in *rows.
  * Any pointer may be NULL. */
 int fm_yolo_layer_shape(const fm_yolo* det, int layer, int* c, int* h, int* w, int* rows);
 /* find_objects' YOLO pass on n raw frames ([n][H][W][3] BGR; host memory, or device memory when
  * on_device): INTER_AREA to width roi_w (imutils.resize: height int(H * roi_w / W), *roi_h_out; FM_ENOTSUP
- * when W < roi_w), 8-bit INTER_LINEAR to the network size, the network, the decode.  cand[n][cap][9] gets
+ * when W < roi_w and fm_yolo_set_roi_upscale is off), 8-bit INTER_LINEAR to the network size, the network, the decode.  cand[n][cap][9] gets
  * each frame's rows whose best class score exceeds `confidence`, sorted by (head, row); counts[n] their
  * number (may exceed cap; only cap are written).  More than max_frames: FM_EINVAL, nothing enqueued.
  * Synchronous. */
