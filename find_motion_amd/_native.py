@@ -43,12 +43,13 @@ EXPORTED = (
     "fm_yuv_frame_bytes", "fm_submit_yuv", "fm_submit_yuv_list",
     "fm_yolo_create", "fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_layer_shape", "fm_yolo_detect_frames",
     "fm_yolo_detect_frame_list", "fm_yolo_forward", "fm_yolo_decode", "fm_yolo_layer_output",
-    "fm_yolo_route_in_place", "fm_yolo_last_ms",
+    "fm_yolo_route_in_place", "fm_yolo_last_ms", "fm_yolo_create_precision", "fm_yolo_precision",
     "fm_plan", "fm_read_threshold_bits",
     "fm_resize_kind", "fm_area_up_taps", "fm_haar_set_roi_upscale", "fm_yolo_set_roi_upscale",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
+YOLO_PRECISIONS = {"f32": 0, "f16": 1}  # FM_YOLO_F32, FM_YOLO_F16
 # fm_yuv_layout.format (FM_YUV_*), by fourcc
 YUV_NV12, YUV_I420, YUV_YUY2, YUV_UYVY = 0, 1, 2, 3
 YUV_FORMATS = {"NV12": YUV_NV12, "I420": YUV_I420, "IYUV": YUV_I420, "YUY2": YUV_YUY2, "YUYV": YUV_YUY2,
@@ -205,6 +206,8 @@ def load() -> C.CDLL:
     L.fm_mjpeg_enc_last_ms.argtypes = [vp]
     L.fm_mjpeg_enc_last_ms.restype = C.c_double
     L.fm_yolo_create.argtypes = [i32, C.POINTER(FMYoloDesc), C.POINTER(vp)]
+    L.fm_yolo_create_precision.argtypes = [i32, C.POINTER(FMYoloDesc), i32, C.POINTER(vp)]
+    L.fm_yolo_precision.argtypes = [vp]
     L.fm_yolo_destroy.argtypes = [vp]
     L.fm_yolo_destroy.restype = None
     L.fm_yolo_last_error.argtypes = [vp]
@@ -954,17 +957,23 @@ class YoloDetector:
 
     `YoloDetector.from_dir(dir, tiny)` reads yolov3[-tiny].cfg, yolov3[-tiny].weights and
     yolov3_classes.txt (find_motion_amd.darknet); `detect_frames` returns cvlib's (bboxes, labels, confs)
-    per frame.  The network input is 416 x 416 whatever the cfg's [net] says, as cvlib passes it."""
+    per frame.  The network input is 416 x 416 whatever the cfg's [net] says, as cvlib passes it.
+    precision "f16" keeps weights and activations in half precision (fm_yolo_create_precision); the default
+    "f32" is the arithmetic the parity tests pin."""
 
     def __init__(self, layers, params, classes, net_w: int = 416, net_h: int = 416, max_frames: int = 1,
-                 zero_thresh: float = 0.2, device: int = 0, channels=None, roi_upscale: bool = False):
+                 zero_thresh: float = 0.2, device: int = 0, channels=None, roi_upscale: bool = False,
+                 precision: str = "f32"):
         # roi_upscale: frames narrower than roi_w are enlarged, as imutils.resize does (else FM_ENOTSUP)
+        if precision not in YOLO_PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {sorted(YOLO_PRECISIONS)}")
+        self._precision = precision
         L = load()
         self.layers, self.classes = layers, list(classes)
         self.net_w, self.net_h, self.max_frames = int(net_w), int(net_h), int(max_frames)
         d, self._keep = yolo_desc(layers, params, net_w, net_h, max_frames, zero_thresh, channels)
         h = C.c_void_p()
-        rc = L.fm_yolo_create(int(device), C.byref(d), C.byref(h))
+        rc = L.fm_yolo_create_precision(int(device), C.byref(d), YOLO_PRECISIONS[precision], C.byref(h))
         self._h = h
         if rc != FM_OK:
             msg = L.fm_yolo_last_error(h).decode() if h else ""
@@ -976,6 +985,11 @@ class YoloDetector:
         rows = C.c_int()
         L.fm_yolo_layer_shape(self._h, -1, None, None, None, C.byref(rows))
         self.rows = rows.value  # candidate rows of all heads, per frame
+
+    @property
+    def precision(self) -> str:
+        """"f32" or "f16": what the detector was created with."""
+        return self._precision
 
     def set_roi_upscale(self, on: bool) -> None:
         load().fm_yolo_set_roi_upscale(self._h, int(bool(on)))

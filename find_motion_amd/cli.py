@@ -57,6 +57,9 @@ def get_args(parser: ArgumentParser) -> None:
                         help="Directory with cvlib's yolov3[-tiny].cfg, yolov3[-tiny].weights and yolov3_classes.txt "
                              "(~/.cvlib/object_detection/yolo/yolov3): tag written frames with YOLOv3 on the GPU "
                              "(default: $FM_YOLO_DIR, else off)")
+    parser.add_argument("--yolo-precision", choices=("f32", "f16"), default=None,
+                        help="Arithmetic of the YOLOv3 stage: f32, or f16 weights and activations on the f16 matrix "
+                             "instructions (default: $FM_YOLO_PRECISION, else f32)")
     parser.add_argument("--blur-scale", "-b", type=int, default=20,
                         help="Scale of gaussian blur size compared to video width (used as 1/blur_scale)")
     parser.add_argument("--box-size", "-B", type=int, default=100, help="Pixel size to scale the video to for processing")
@@ -107,6 +110,8 @@ def process_config(config_file: str, args: Namespace) -> Namespace:
             if value not in ("True", "False"):
                 raise ValueError("{} must be True or False".format(setting))
             use_value = value == "True"
+        if setting == "yolo_precision" and value not in ("f32", "f16"):
+            raise ValueError("yolo_precision must be f32 or f16")
         if setting in ("masks", "cameras", "time_order"):
             use_value = literal_eval(value)
         setattr(args, setting, use_value)
@@ -215,7 +220,8 @@ def _job_kwargs(args) -> dict:
                 blur_scale=args.blur_scale, box_size=args.box_size, min_box_scale=args.min_box_scale,
                 threshold=args.threshold, avg=args.avg, fps=args.fps, min_time=args.mintime,
                 cache_time=args.cachetime, multiprocess=args.processes > 1, cascades=args.cascade_object,
-                yolo_tiny=args.yolo_tiny, yolo_dir=getattr(args, "yolo_dir", None), gpu_decode=getattr(args, "gpu_decode", None),
+                yolo_tiny=args.yolo_tiny, yolo_dir=getattr(args, "yolo_dir", None),
+                yolo_precision=getattr(args, "yolo_precision", None), gpu_decode=getattr(args, "gpu_decode", None),
                 gpu_encode=getattr(args, "gpu_encode", None),
                 contour_points=bool(getattr(args, "contour_points", False)))
 

@@ -56,7 +56,8 @@ then carries its CHAIN_APPROX_SIMPLE points, traced on the GPU: np.asarray(c)
 is the (n, 1, 2) int32 array cv2.findContours returns at fm.py:269-272),
 yolo_dir (the directory of cvlib's yolov3 files, default $FM_YOLO_DIR: find_objects
 then tags frames with YOLOv3 on the GPU as fm.py:733-741 does with cvlib; without
-it that stage is off).
+it that stage is off), yolo_precision ("f32", the default, or "f16": the network in
+half precision on the f16 matrix instructions; default $FM_YOLO_PRECISION).
 
 There is no CPU fallback: without the HIP library this module raises
 NativeLibraryMissing at VideoMotion construction.
@@ -86,7 +87,7 @@ GREEN = (0, 255, 0)
 
 # fm.py:104-122
 _CASCADES: dict = {}  # (path, device) -> CascadeClassifier
-_YOLOS: dict = {}  # (cfg path, weights path, names path, device) -> YoloDetector
+_YOLOS: dict = {}  # (cfg path, weights path, names path, device, precision) -> YoloDetector
 
 CASCADE_LOOKUP = {
     "frontalcatface": "Cat 1",
@@ -241,7 +242,7 @@ class VideoMotion:
                  device: int = 0, batch: int = 1, capture=None, engine: MotionEngine = None,
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
                  pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None,
-                 contour_points: bool = False, yolo_dir: str = None) -> None:
+                 contour_points: bool = False, yolo_dir: str = None, yolo_precision: str = None) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -276,6 +277,9 @@ class VideoMotion:
         self._load_cascades()
         self.tiny = yolo_tiny
         self.yolo_dir = yolo_dir if yolo_dir is not None else (os.environ.get("FM_YOLO_DIR") or None)
+        self.yolo_precision = yolo_precision if yolo_precision is not None else (os.environ.get("FM_YOLO_PRECISION") or "f32")
+        if self.yolo_precision not in ("f32", "f16"):
+            raise ValueError(f"yolo_precision {self.yolo_precision!r}: f32 or f16")
         self.yolo = None  # the YOLOv3 detector (_load_yolo), only with a yolo_dir
         self.amount_of_frames = -1
         self.frame_width = -1
@@ -417,14 +421,16 @@ class VideoMotion:
         if missing:
             self.log.warning("YOLO files not found: %s: object detection skipped", missing)
             return
-        key = tuple(os.path.realpath(f) for f in files) + (self.device,)
-        if key not in _YOLOS:  # one device copy per file set and device, shared by every stream
+        key = tuple(os.path.realpath(f) for f in files) + (self.device, self.yolo_precision)
+        if key not in _YOLOS:  # one device copy per file set, device and precision, shared by every stream
             try:
-                _YOLOS[key] = _roi_upscale(YoloDetector.from_dir(self.yolo_dir, tiny=self.tiny, device=self.device))
+                kw = {} if self.yolo_precision == "f32" else {"precision": self.yolo_precision}  # (f32: the call as it was)
+                _YOLOS[key] = _roi_upscale(YoloDetector.from_dir(self.yolo_dir, tiny=self.tiny, device=self.device, **kw))
             except (ValueError, OSError, FMError) as e:
                 self.log.warning("YOLO files in %s refused (%s): object detection skipped", self.yolo_dir, e)
                 return
         self.yolo = _YOLOS[key]
+        self.log.info("YOLO stage: %s on the GPU in %s", os.path.basename(stem), self.yolo_precision)
 
     def _get_video_info(self) -> None:
         """fm.py:427-444"""

@@ -562,6 +562,19 @@ typedef struct fm_yolo_desc {
  * the arrays ...), then upload the re-packed weights and allocate every layer's activations.  *out is set
  * even on failure so that fm_yolo_last_error can say why; release it with fm_yolo_destroy. */
 int fm_yolo_create(int device, const fm_yolo_desc* desc, fm_yolo** out);
+/* fm_yolo_create (which means FM_YOLO_F32) with the arithmetic chosen.  FM_YOLO_F16: the blob's table values,
+ * the folded weights and every activation are f16 (each rounded to nearest even, results clamped to +-65504);
+ * a convolution accumulates the f16 x f16 products in f32 on v_mfma_f32_32x32x16_f16 and adds bias and leaky
+ * in f32; a shortcut is one f32 add; a convolution read by a head stores f32, so the decode is the same.
+ * Before any HIP call: another precision is FM_EINVAL; in FM_YOLO_F16 a weight that is not finite in f16
+ * (|w| >= 65520), a head that does not follow a convolution and a layer other than the head reading a head's
+ * convolution are FM_ENOTSUP, the message naming the layer.  Every other fm_yolo_* call works alike in both:
+ * fm_yolo_forward takes f32, fm_yolo_layer_output gives NCHW f32 (the stored halves widened). */
+#define FM_YOLO_F32 0
+#define FM_YOLO_F16 1
+int fm_yolo_create_precision(int device, const fm_yolo_desc* desc, int precision, fm_yolo** out);
+/* FM_YOLO_F32 or FM_YOLO_F16 (FM_EINVAL for NULL) */
+int fm_yolo_precision(const fm_yolo* det);
 void fm_yolo_destroy(fm_yolo* det);
 const char* fm_yolo_last_error(const fm_yolo* det);
 /* on: frames narrower than roi_w are enlarged as FM_FLAG_AREA_UPSCALE enlarges them; off (default): FM_ENOTSUP */
@@ -588,7 +601,8 @@ int fm_yolo_decode(fm_yolo* det, int n, float confidence, float* cand, int cap, 
  * input), copied to out: parity tests.  Returns their number (cap counts floats; FM_EINVAL when smaller). */
 int fm_yolo_layer_output(fm_yolo* det, int layer, float* out, size_t cap);
 /* Whether layer `layer` (a route) takes its inputs in place -- its sources wrote at channel offsets of its
- * buffer -- 1, or by the copy kernel, 0 (read-only, for tests). */
+ * buffer -- 1, or by the copy kernel, 0 (read-only, for tests).  In FM_YOLO_F16 (NHWC) a route is placed only
+ * when its second source's channel offset is a multiple of 8. */
 int fm_yolo_route_in_place(const fm_yolo* det, int layer);
 /* Device time of the last call per stage (HIP events), ms: resize + blob, network, decode; returns their sum.
  * stages may be NULL. */
