@@ -712,8 +712,8 @@ template <int KC, int RW> constexpr int np_rows() {
     return m;
 }
 
-// The chain in pieces: chain_rows_w runs them row by row; k_pix5's 8-wave frame body issues every row's LDS
-// read first and puts the tap jobs' arithmetic between the table reads and the rows that use them.
+// The chain in pieces: chain_rows_w runs them row by row; k_pix5's 8-wave frame body takes its accumulators from
+// the matrix cores instead of chain_pairs / chain_blur and runs chain_tab / chain_bit four rows at a time.
 // The wave's H pairs: NPR dwords of its column
 template <int RW, int NPR>
 __device__ __forceinline__ void chain_pairs(uint32_t (&P)[NPR], const uint32_t* Hp, int wv, int ln) {
@@ -723,16 +723,14 @@ __device__ __forceinline__ void chain_pairs(uint32_t (&P)[NPR], const uint32_t* 
 }
 // Output row j's vertical taps (+2^15: the blur value is byte 2 of acc), the keep-mask applied, and where the
 // row's blur x alpha lies in the table
-// H16: the pairs hold H / 16 (k_pix5's matrix-core taps, below; every k = 5 tap is a multiple of 16) and the taps
-// here are taken times 16: the same accumulator, 2^15 + sum c H = 2^15 + sum (16 c) (H / 16), in the same instructions.
-template <int KC, bool KEEP, bool SDWA, int j, bool H16 = false, int NPR>
+template <int KC, bool KEEP, bool SDWA, int j, int NPR>
 __device__ __forceinline__ void chain_blur(const uint32_t (&P)[NPR], const ChainCtx& cc, uint32_t& acc, uint32_t& tix) {
     using G = PW<KC>;
     acc = 32768u;
     static_for<G::np(j)>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, P[G::p0(j) + i]),
-                                     __builtin_bit_cast(u16x2_t, tapv2<KC>(j, i) << (H16 ? 4 : 0)), acc, false);
+                                     __builtin_bit_cast(u16x2_t, tapv2<KC>(j, i)), acc, false);
     });
     if (KEEP) {
         const uint32_t kw = j < 4 ? cc.keep_lo : j < 8 ? cc.keep_hi : j < 12 ? cc.keep_2 : cc.keep_3;
@@ -751,9 +749,10 @@ __device__ __forceinline__ double chain_tab(const double* atab, uint32_t tix) {
     return SDWA ? *reinterpret_cast<const double*>(reinterpret_cast<const char*>(atab) + tix) : atab[tix];
 }
 // Row j's threshold bit into tb (rows 0..7) / tb2 (rows 8..15): one dot4 moves the bit into byte 1 of the word
-template <int j>
+// BYTE: the accumulator's byte that holds the blur value (1 where it is k_pix5's 5 x 5 block product)
+template <int j, int BYTE = 2>
 __device__ __forceinline__ void chain_bit(uint32_t acc, double b, uint32_t bias, uint32_t& tb, uint32_t& tb2) {
-    const uint32_t q = __builtin_amdgcn_cvt_pk_u8_f32(fabsf(__double2float_rn(b)), 2, acc);
+    const uint32_t q = __builtin_amdgcn_cvt_pk_u8_f32(fabsf(__double2float_rn(b)), BYTE, acc);
     const uint32_t r = __builtin_amdgcn_sad_u8(acc, q, bias);
     if constexpr (j < 8) tb = __builtin_amdgcn_udot4(r, (1u << j) << 8, tb, false);
     else tb2 = __builtin_amdgcn_udot4(r, (1u << (j - 8)) << 8, tb2, false);
@@ -878,12 +877,14 @@ __device__ __forceinline__ uint32_t hs_tap(const uint32_t (&q)[N], const uint32_
 // The chain runs on even-aligned pair windows (chain_rows_w); tap jobs cover 2 H rows x 4 columns and store
 // them as row pairs (one ds_write_b128), which the chain reads back as six dwords instead of twelve u16
 // reads and their merges; the horizontal taps take shifted constants (HS).
-// The 8-wave kernel has no tap jobs: a horizontal 5-tap sum is a product with a banded constant matrix, exact
-// in i32, so H comes from the matrix cores (v_mfma_i32_16x16x32_i8, three 16-row x 16-column blocks a wave and
-// frame): gray is stored as gray - 128 (signed bytes), the taps divided by 16 (all are multiples), the product
-// starts from 128 * 16 = 2048, and the chain takes the result, H / 16, with the vertical taps times 16 -- the
-// same accumulator, bit for bit.  The REFLECT_101 columns are folded into the tap matrix once per tile (see the
-// plans in the kernel).
+// The 8-wave kernel has no tap jobs, no H and no vertical pass: every k = 5 tap is a multiple of 16, so every
+// product c[i] c[j] is a multiple of 256 and the two-pass accumulator 2^15 + sum_v c_v (sum_h c_h g) is
+// 256 (S + 128) with S = sum (c[dr] c[dc] / 256) g[r + dr][c + dc]: blur = (S + 128) >> 8, one exact integer form
+// with weights {1, 4, 6, 16, 24, 36} that sum to 256.  S + 128 of a 16-row x 16-column block is two products on
+// the matrix cores (v_mfma_i32_16x16x64_i8, K = 120 of 128: 5 gray rows x a 24-byte window per output row), two
+// blocks a wave and frame: gray is stored as gray - 128 (signed bytes), the products start from 128 * 256 + 128,
+// and the result's byte 1 is the blur, already in the registers of the lanes that run the chain on it.  The
+// REFLECT_101 columns are folded into the tap matrix once per tile (entries <= 48; see the plans in the kernel).
 template <int NWB_ = 8>
 struct P5G {
     static constexpr int NWB = NWB_;                     // waves of a tile (8 of 8 rows, or 4 of 16 rows)
@@ -898,9 +899,10 @@ struct P5G {
     // gray row stride in LDS (dwords): 24, not GQ = 18, so the four even gray rows a tap-job wave reads start 48
     // dwords apart and their windows fall in disjoint banks: LDS bank conflicts 176.3 M -> 68.2 M per 10-step run
     // (0.49 -> 0.19 per LDS-active cycle), throughput unchanged (round 6, profiles/r06/r06e_gray_stride_ab.txt)
-    // Eight waves (the taps as block products, below): 20.  A wave's ds_read_b64 takes 16 rows x 32 bytes; at 20
-    // dwords the rows start at banks 20 m mod 64 = sixteen different multiples of 4, four banks each, and at 24 rows
-    // m and m + 8 share their banks.  A row's 80 bytes still hold the last column block's 32-byte window (48 .. 79).
+    // Eight waves (the blur as block products, below): 20.  A wave's ds_read_b128 takes 16 bytes of each of 16 rows
+    // per lane group; at 20 dwords the rows start at banks 20 m mod 64 = sixteen different multiples of 4, four banks
+    // each, and at 24 rows m and m + 8 share their banks.  A row's 80 bytes (16-byte aligned) hold the last column
+    // block's 24-byte window (48 .. 71).
 #ifndef FM_P5_GS8
 #define FM_P5_GS8 20
 #endif
@@ -910,9 +912,14 @@ struct P5G {
     // Gray jobs go to waves in whole wave-slots of 64 jobs.  Waves 4..7 lose issue arbitration to waves
     // 0..3 (age order) and set every frame's barrier (FM_PTS phase stamps: waves 0..3 spent ~30 % of
     // their cycles in the barrier), so waves 0..3 take GFAST slots each and waves 4..7 the rest; the
-    // partial last slot goes to wave 3.  (GFAST A/B: 4 >= 3 > 5.)  Four waves: an even deal.
+    // partial last slot goes to wave 3.  (GFAST A/B with tap jobs or the H block products in every wave: 4 >= 3 > 5;
+    // with the whole blur as block products, 87 VALU a wave-frame before its gray slots: 3 > 4)
+    // Four waves: an even deal.
     static constexpr int GSLOTS = (NG + 63) / 64;
-    static constexpr int GFAST = NWB == 8 ? 4 : (GSLOTS + NWB - 1) / NWB;
+#ifndef FM_P5_GFAST
+#define FM_P5_GFAST 3
+#endif
+    static constexpr int GFAST = NWB == 8 ? FM_P5_GFAST : (GSLOTS + NWB - 1) / NWB;
     static constexpr int GSLOW = NWB == 8 ? (GSLOTS - 4 * GFAST + 3) / 4 : 0;
     static constexpr int GJ = GFAST > GSLOW ? GFAST : GSLOW;  // load rounds per wave
     static constexpr int NH = (GH / 2) * (TS / 4);       // tap jobs per frame
@@ -921,16 +928,16 @@ struct P5G {
     static constexpr int HLASTW = (NH - (HJ - 1) * NTB + 63) / 64;
     static constexpr int GBUF = GH * GS + 64;            // + a pad slot per lane for the idle jobs' stores (branch-free)
     static constexpr int HBUF = (GH + 2) * TS;           // u16; + the pad pair row idle tap jobs store to
-    static constexpr int bytes = 2 * GBUF * 4 + 2 * HBUF * 2 + 256 * 8;
+    // (eight waves: no H buffers, the blur comes out of the block products in registers)
+    static constexpr int bytes = 2 * GBUF * 4 + (NWB == 8 ? 0 : 2 * HBUF * 2) + 256 * 8;
     static constexpr int dyn_bytes = bytes - 256 * 8;  // (the table is static LDS)
-    // Eight waves: H as 16-row x 16-column block products.  Wave w owns columns 16 (w & 3) .. + 15 of gray rows
-    // 34 (w >> 2) .. + 33, as three blocks starting MOFF rows into them; the third overlaps the second (its own
-    // rows, the same values stored again), so every wave runs the same three blocks at the same immediate
-    // offsets, every operand row lies inside the gray buffer and no lane is idle.
-    static constexpr int MROWS = GH / 2, MB = 3;
-    static constexpr int moff(int i) { return i == 0 ? 0 : i == 1 ? 16 : MROWS - 16; }
+    // Eight waves: the blur as 16-row x 16-column block products.  Wave w owns columns 16 (w & 3) .. + 15 of tile
+    // rows 32 (w >> 2) .. + 31 as MB blocks of 16 rows; block i's 5 x 24 byte windows start MOFF gray rows down.
+    static constexpr int MROWS = 32, MB = 2;
+    static constexpr int moff(int i) { return 16 * i; }
 };
-static_assert(P5G<8>::MROWS % 2 == 0 && P5G<8>::moff(2) % 2 == 0 && P5G<8>::moff(2) <= 32, "whole row pairs, no gap");
+static_assert(2 * P5G<8>::MROWS == P5G<8>::TH && P5G<8>::MROWS + P5G<8>::moff(1) + 15 + 4 < P5G<8>::GH, "operand rows in the gray buffer");
+static_assert(P5G<8>::GS % 4 == 0 && P5G<8>::GS * 4 >= 48 + 24, "16-byte aligned rows that hold the last block's 24-byte window");
 static_assert(P5G<8>::GSLOW >= 0 && 4 * (P5G<8>::GFAST + P5G<8>::GSLOW) >= P5G<8>::GSLOTS, "gray slots");
 static_assert(4 * P5G<4>::GFAST >= P5G<4>::GSLOTS, "gray slots");
 
@@ -1021,38 +1028,92 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
         const int hq = (int)(hsrc[i] % G::GS);
         hfix[i] = (x0 == 0 && hq == 0 ? 1u : 0u) | (hq + 1 == vq ? 2u : 0u) | (hq + 2 == vq ? 4u : 0u);
     }
-    // Eight waves: the lane's operand row (bytes into a gray buffer: row l % 16 of the wave's rows, K bytes
-    // 8 (l / 16) .. + 7 of the column block's window, which starts at gray byte 16 cb = column x0 + 16 cb - 4), its
-    // result's place (dwords into an H buffer: row pair 2 (l / 16) of the block, column l % 16) and its 8 bytes of
-    // the banded tap matrix: B[k][n] = c[k - n - 2] / 16, output n of the block over window bytes n + 2 .. n + 6.
-    // REFLECT_101 is linear, so it lives in B: a tap that falls on a column left of 0 or from w on (gray bytes
-    // that are never loaded) is added to the tap of the column it mirrors, which lies in the same window.  Column
-    // sums stay 16, every entry <= 8 (the taps undivided would reach 128 at the mirror's axis neighbour).
-    uint32_t asrc = 0, mdst = 0;
-    long btap = 0;
-    i32x4_t mc0 = {2048, 2048, 2048, 2048};  // the product's C: sum b (gray - 128) + 16 * 128 = H / 16 in [0, 4080]
+    // Eight waves: output row m = l % 16 of a block, over the 5 x 24 byte window of gray rows m .. m + 4 that starts
+    // at gray byte 16 cb (column x0 + 16 cb - 4); two products take its K = 120 bytes, and l / 16 = q picks the
+    // lane's sixteen of each:
+    //   product 1   bytes 0 .. 15 of gray row m + q                            (asrc, one ds_read_b128)
+    //   product 2   two 8-byte slots 2 q, 2 q + 1 of: row m + 4 bytes 0 .. 7, row m + 4 bytes 8 .. 15, bytes
+    //               16 .. 23 of rows m, m + 1, .., m + 4, and a slot with zero taps (it reads slot 6's bytes)
+    //                                                                          (asrc2, asrc3, one ds_read_b64 each)
+    // The lane's 2 x 16 bytes of the tap matrix follow the same map: B[k][n] = c[dr] c[dc] / 256 where K byte k is
+    // window row dr, window byte n + 2 + dc, output n = l % 16 of the block.  REFLECT_101 is linear, so it lives
+    // in B: a tap that falls on a column left of 0 or from w on (gray bytes that are never loaded) is added to the
+    // tap of the column it mirrors, which lies in the same window.  Column sums stay 256, every entry <= 48.
+    uint32_t asrc = 0, asrc2 = 0, asrc3 = 0, asrc2b = 0, asrc3b = 0, bdst = 0;
+    long long li0 = 0;                       // (TAIL) the linear image index of the lane's first pixel
+    i32x4_t btap1 = {0, 0, 0, 0}, btap2 = {0, 0, 0, 0};
+    // the products' C: sum b (gray - 128) + 128 * 256 + the rounding 128 = 256 * blur + (a byte's worth of fraction)
+    i32x4_t mc0 = {32896, 32896, 32896, 32896};
     if constexpr (NWB == 8) {
         static_assert(Taps<5>::c[0] % 16 == 0 && Taps<5>::c[1] % 16 == 0 && Taps<5>::c[2] % 16 == 0, "taps / 16");
         const int mn = ln & 15, mq = ln >> 4, cb = wv & 3, r0 = (wv >> 2) * G::MROWS;
-        asrc = (uint32_t)((r0 + mn) * G::GS * 4 + 16 * cb + 8 * mq);
-        mdst = (uint32_t)((r0 / 2 + 2 * mq) * TS + 16 * cb + mn);
+        const int s2 = 2 * mq, s3 = 2 * mq + 1;  // the lane's slots of product 2
+        asrc = (uint32_t)((r0 + mn + mq) * G::GS * 4 + 16 * cb);
+        asrc2 = (uint32_t)((r0 + mn + (s2 < 2 ? 4 : s2 - 2)) * G::GS * 4 + 16 * cb + (s2 < 2 ? 8 * s2 : 16));
+        asrc3 = (uint32_t)((r0 + mn + (s3 < 2 ? 4 : min(s3 - 2, 4))) * G::GS * 4 + 16 * cb + (s3 < 2 ? 8 * s3 : 16));
         const int bw = w - x0 + 4;  // gray byte of column w
-        uint64_t bt = 0;
+        // the window row's horizontal taps / 16 of output mn, folded: bytes 0 .. 7, 8 .. 15, 16 .. 23
+        uint64_t hw0 = 0, hw1 = 0, hw2 = 0;
         static_for<5>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
             int sb = 16 * cb + mn + 2 + t;                  // the tap's gray byte ...
             if (x0 == 0 && sb < 4) sb = 8 - sb;             // ... column -1, -2 -> 1, 2
             else if (sb >= bw) sb = 2 * bw - 2 - sb;        // ... column w, w + 1 -> w - 2, w - 3
-            const int k = sb - 16 * cb - 8 * mq;            // its byte in this lane's K slice
-            bt += (unsigned)k < 8u ? (uint64_t)(Taps<5>::c[t] / 16) << (8 * (k & 7)) : 0ull;
+            const int k = sb - 16 * cb;                     // its byte in the window (outputs past the image: any)
+            const uint64_t v = (uint64_t)(Taps<5>::c[t] / 16) << (8 * (k & 7));
+            hw0 += (unsigned)k < 8u ? v : 0ull;
+            hw1 += (unsigned)(k - 8) < 8u ? v : 0ull;
+            hw2 += (unsigned)(k - 16) < 8u ? v : 0ull;
         });
-        btap = (long)bt;
-        asm volatile("" : "+v"(asrc), "+v"(mdst), "+v"(btap), "+v"(mc0));  // (C held in four registers, not moved in per product)
+        // times the window row's vertical tap / 16, byte by byte: a byte is at most 8 x 6, so nothing carries
+        auto cv = [](int dr) { return (uint64_t)(dr == 0 || dr == 4 ? Taps<5>::c[0] / 16 : dr == 2 ? Taps<5>::c[2] / 16 : Taps<5>::c[1] / 16); };
+        static_assert(Taps<5>::c[0] == Taps<5>::c[4] && Taps<5>::c[1] == Taps<5>::c[3], "symmetric taps");
+        const uint64_t b1l = hw0 * cv(mq), b1h = hw1 * cv(mq);                         // window row q, bytes 0 .. 15
+        const uint64_t b2l = mq == 0 ? hw0 * cv(4) : hw2 * cv(s2 - 2);                 // slot 2 q
+        const uint64_t b2h = mq == 0 ? hw1 * cv(4) : mq == 3 ? 0ull : hw2 * cv(s3 - 2);  // slot 2 q + 1 (slot 7: none)
+        btap1 = i32x4_t{(int)(uint32_t)b1l, (int)(uint32_t)(b1l >> 32), (int)(uint32_t)b1h, (int)(uint32_t)(b1h >> 32)};
+        btap2 = i32x4_t{(int)(uint32_t)b2l, (int)(uint32_t)(b2l >> 32), (int)(uint32_t)b2h, (int)(uint32_t)(b2h >> 32)};
+        // the lane's byte of the tile's column words: lanes l and l ^ 16 hold the two nibbles of a byte (see the frame loop)
+        const int bi = 4 * (wv >> 2) + 2 * (mq & 1) + (mq >> 1);
+        bdst = (uint32_t)((16 * cb + mn) * 8 + bi);
+        // (C held in four registers, not moved in per product)
+        asrc2b = asrc2 + G::moff(1) * G::GS * 4;
+        asrc3b = asrc3 + G::moff(1) * G::GS * 4;
+        asm volatile("" : "+v"(asrc), "+v"(asrc2), "+v"(asrc3), "+v"(asrc2b), "+v"(asrc3b), "+v"(bdst), "+v"(btap1), "+v"(btap2), "+v"(mc0));
     }
 
     // background of the wave's 8 rows x 64 columns -> registers (as k_pix)
+    // Eight waves: the block products' layout -- pixel 4 i + r of a lane is row 4 (l / 16) + r of column l % 16 of
+    // the wave's block i
     double bg[RW];
     ChainCtx cc;
+    auto load_bg8 = [&]() __attribute__((always_inline)) {
+        const double* bgi = a.bg_in + (size_t)s * plane;
+        const int mn = ln & 15, mq = ln >> 4, cb = wv & 3;
+        const int x = x0 + 16 * cb + mn, yl = y0 + G::MROWS * (wv >> 2) + 4 * mq;
+        cc.colmask = 0;
+        cc.rowvalid = 0;
+        cc.keep_lo = cc.keep_hi = cc.keep_2 = cc.keep_3 = 0;
+        cc.hk = __builtin_amdgcn_readfirstlane(hk ? 1 : 0) != 0;
+#pragma unroll
+        for (int j = 0; j < RW; j++) {
+            const int y = yl + G::moff(j >> 2) + (j & 3);
+            const bool in = x < w && y < h;
+            bg[j] = in ? bgi[(size_t)y * w + x] : 0.0;
+            const uint32_t kb = (!hk || (in && keep[(size_t)y * w + x] != 0)) ? 0xFFu : 0u;
+            if (j < 4) cc.keep_lo |= kb << (8 * j);
+            else cc.keep_hi |= kb << (8 * (j - 4));
+        }
+        // rows and columns past the image hold zero bits: the mask of the byte this lane stores (rows 8 bi .. + 7)
+        const int yb = y0 + 8 * (int)(bdst & 7);
+        cc.tbmask = x < w ? (yb + 8 <= h ? 0xFFu : yb < h ? (1u << (h - yb)) - 1u : 0u) : 0u;
+        li0 = (long long)yl * w + x;
+        const long long last = (long long)(y0 + G::MROWS * (wv >> 2) + G::MROWS - 1) * w + x0 + 16 * cb + 15;
+        cc.vec = (uint32_t)__builtin_amdgcn_readfirstlane(last < a.acc_vec_end ? 1 : 0);
+#pragma unroll
+        for (int j = 0; j < RW; j++) asm volatile("" : "+v"(bg[j]));
+        asm volatile("" : "+v"(cc.keep_lo), "+v"(cc.keep_hi));
+    };
     auto load_bg = [&]() __attribute__((always_inline)) {
         const double* bgi = a.bg_in + (size_t)s * plane;
         const int x = x0 + ln;
@@ -1101,24 +1162,27 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             gb[gdst[i]] = gray4<NWB == 8>(rw.v[i].x, rw.v[i].y, rw.v[i].z);  // (eight waves: signed bytes)
         }
     };
-    // Eight waves: block i of the wave in pieces -- the operand read (ds_read_b64), the product, and the lane's four
-    // results (rows 4 (l / 16) .. + 3 of one column = two of the chain's row pairs) packed by one v_perm a pair and
-    // stored by one ds_write2st64_b32.  H / 16 stays as it is: chain_blur<.., H16>.
-    auto mf_read = [&](const uint32_t* gb, auto ic) __attribute__((always_inline)) {
+    // Eight waves: block i of the wave in pieces -- the operand reads (one ds_read_b128, two ds_read_b64) and the
+    // two products; the lane's four results (rows 4 (l / 16) .. + 3 of column l % 16) are 256 blur + fraction and
+    // stay in registers: they are the chain's accumulators of the next frame phase.
+    // (The second block's slot addresses stand in registers of their own: from one register and two immediate
+    // offsets the compiler merges the blocks' reads of a slot into a ds_read2_b64, whose halves belong to different
+    // operands -- six v_mov per frame to sort them.)
+    auto mf_read = [&](const uint32_t* gb, auto ic, i32x4_t& a1, i32x4_t& a2) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;
-        return *reinterpret_cast<const long*>(reinterpret_cast<const uint8_t*>(gb) + asrc + G::moff(i) * G::GS * 4);
+        const uint8_t* g8 = reinterpret_cast<const uint8_t*>(gb);
+        a1 = *reinterpret_cast<const i32x4_t*>(g8 + asrc + G::moff(i) * G::GS * 4);
+        const uint2 lo = *reinterpret_cast<const uint2*>(g8 + (i == 0 ? asrc2 : asrc2b));
+        const uint2 hi = *reinterpret_cast<const uint2*>(g8 + (i == 0 ? asrc3 : asrc3b));
+        a2 = i32x4_t{(int)lo.x, (int)lo.y, (int)hi.x, (int)hi.y};
     };
-    auto mf_mul = [&](long av) __attribute__((always_inline)) {
-        return __builtin_amdgcn_mfma_i32_16x16x32_i8(av, btap, mc0, 0, 0, 0);
-    };
-    auto mf_store = [&](uint16_t* Hb, auto ic, i32x4_t d) __attribute__((always_inline)) {
-        constexpr int i = decltype(ic)::value;
-        uint32_t* hp = reinterpret_cast<uint32_t*>(Hb) + mdst + G::moff(i) / 2 * TS;
-        hp[0] = __builtin_amdgcn_perm((uint32_t)d.y, (uint32_t)d.x, 0x05040100u);
-        hp[TS] = __builtin_amdgcn_perm((uint32_t)d.w, (uint32_t)d.z, 0x05040100u);
-    };
-    auto mf_stage = [&](const uint32_t* gb, uint16_t* Hb) __attribute__((always_inline)) {
-        static_for<G::MB>([&](auto ic) { mf_store(Hb, ic, mf_mul(mf_read(gb, ic))); });
+    // both blocks' first products, then their second ones: no product waits for the one issued just before it
+    auto mf_mul2 = [&](i32x4_t (&d)[2], const i32x4_t& a01, const i32x4_t& a02, const i32x4_t& a11, const i32x4_t& a12)
+        __attribute__((always_inline)) {
+        const i32x4_t e0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a01, btap1, mc0, 0, 0, 0);
+        const i32x4_t e1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a11, btap1, mc0, 0, 0, 0);
+        d[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a02, btap2, e0, 0, 0, 0);
+        d[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a12, btap2, e1, 0, 0, 0);
     };
     // A tap job in pieces (tap_stage runs them in turn; the 8-wave frame body reads first and sums later).
     // edge: the tile holds a REFLECT_101 quad -- a bool, or a std::bool_constant where the kind of tile is compiled in
@@ -1167,13 +1231,21 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
     // t+3 into the registers gray(t+2) just consumed (one iteration in flight).  Loads are
     // unconditional, frame indices clamped to the batch (see load).
     auto run = [&](auto edge) __attribute__((always_inline)) {
-        if constexpr (NWB == 8) load_bg();  // (in each copy: the background stays in the registers it was loaded into)
+        if constexpr (NWB == 8) load_bg8();
         load((size_t)t0 * S + s);
         gray_stage(gray);
         load((size_t)min(t0 + 1, t1 - 1) * S + s);
         __syncthreads();  // atab, gray(t0)
-        if constexpr (NWB == 8) mf_stage(gray, Hs);
-        else tap_stage(edge, gray, Hs);
+        // Eight waves: frame t's blur (256 blur + fraction) of the lane's 2 x 4 pixels, formed in phase t - 1
+        i32x4_t dblk[2] = {mc0, mc0};
+        if constexpr (NWB == 8) {
+            i32x4_t a01, a02, a11, a12;
+            mf_read(gray, IntC<0>{}, a01, a02);
+            mf_read(gray, IntC<1>{}, a11, a12);
+            mf_mul2(dblk, a01, a02, a11, a12);
+        } else {
+            tap_stage(edge, gray, Hs);
+        }
         if (t0 + 1 < t1) gray_stage(gray + G::GBUF);
         load((size_t)min(t0 + 2, t1 - 1) * S + s);
 
@@ -1194,62 +1266,73 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             var = __builtin_amdgcn_readfirstlane(var);
             if constexpr (KEEP) asm volatile("" : "+v"(ccf.keep_lo), "+v"(ccf.keep_hi));
             if constexpr (KEEP && RW > 8) asm volatile("" : "+v"(ccf.keep_2), "+v"(ccf.keep_3));
-            const uint32_t* Hp = reinterpret_cast<const uint32_t*>(Hs + b * G::HBUF);
             if constexpr (NWB == 8) {
                 const uint32_t* gn = gray + (b ^ 1) * G::GBUF;
-                uint16_t* Hn = Hs + (b ^ 1) * G::HBUF;
                 // Four waves per SIMD, barrier-locked to one phase, cover little of an LDS round trip, so the wave
-                // covers its own: behind the barrier it issues every read whose address it knows (the three blocks'
-                // operand rows, the chain's pairs); the table reads, whose addresses are the blur values, go out four
-                // rows at a time.  The block products go to the matrix pipe first -- a blur4 and a chain4 group run
-                // before anything reads a result -- and the packs and stores stand between the second group's table
-                // reads and the rows that use them.  (The products after the first group's table reads instead: the
-                // launch alone 443 vs 437 us, beside the contour pass the same.)  One basic block, pinned in this order
-                // (the scheduler would otherwise sink the table reads): chain(t), taps(t+1) and gray(t+2) are
-                // independent, and the taps run past the batch's last frame too (into an H buffer nothing reads), like
-                // gray and the loads.
-                static_assert(G::MB == 3 && RW == 8, "three blocks a wave");
-                uint32_t P[np_rows<KC, RW>()], acc[4], tb = 0, tb2 = 0;
+                // covers its own: behind the barrier it issues the operand reads of frame t + 1's products (their
+                // addresses are frame invariant), then runs frame t's chain on the results carried over from the
+                // last phase, block by block: four table reads (their addresses are the blur values), then the four
+                // rows that use them.  The products of frame t + 1 follow the chain into the registers it has just
+                // consumed and run on the matrix pipe under the gray stage; nothing reads them before the barrier.
+                // One basic block, pinned in this order (the scheduler would otherwise sink the table reads):
+                // chain(t), products(t+1) and gray(t+2) are independent, and the products run past the batch's last
+                // frame too (on a gray buffer nothing wrote, into results nothing reads), like gray and the loads.
+                static_assert(G::MB == 2 && RW == 8, "two blocks a wave");
+                uint32_t acc[4], tb = 0, tb2 = 0;
                 double bl[4];
                 const double beta = a.beta;
                 const uint32_t bias = (uint32_t)(255 - min(max(a.thresh, -1), 255));
-                auto blur4 = [&](auto j0) __attribute__((always_inline)) {
+                // the block's four rows: the keep-mask applied, and where blur x alpha lies in the table -- the blur
+                // is byte 1 of the product, times 8 in ONE SDWA shift (the table is static LDS at address 0)
+                auto blur4 = [&](auto ic) __attribute__((always_inline)) {
+                    constexpr int i = decltype(ic)::value;
                     static_for<4>([&](auto jc) {
-                        constexpr int jj = decltype(jc)::value, j = decltype(j0)::value + jj;
+                        constexpr int jj = decltype(jc)::value;
+                        acc[jj] = (uint32_t)dblk[i][jj];
+                        if (KEEP) acc[jj] &= (uint32_t)__builtin_amdgcn_sbfe((int)(i == 0 ? ccf.keep_lo : ccf.keep_hi), 8 * jj, 8);
                         uint32_t tix;
-                        chain_blur<KC, KEEP, true, j, true>(P, ccf, acc[jj], tix);
+                        asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"
+                            : "=v"(tix) : "v"(acc[jj]));
                         bl[jj] = chain_tab<true>(atab, tix);
                     });
                     __builtin_amdgcn_sched_barrier(0);
                 };
-                auto rows4 = [&](auto j0, auto tail) __attribute__((always_inline)) {
+                // block 0's bits go to bits 0..3 of tb, block 1's to bits 0..3 of tb2
+                auto rows4 = [&](auto ic, auto tail) __attribute__((always_inline)) {
+                    constexpr int i = decltype(ic)::value;
                     static_for<4>([&](auto jc) {
-                        constexpr int jj = decltype(jc)::value, j = decltype(j0)::value + jj;
-                        chain_bit<j>(acc[jj], bg[j], bias, tb, tb2);
-                        bg[j] = chain_bg<decltype(tail)::value, RW, j>(a, bg[j], beta, bl[jj], wvf, ln, x0f, y0f, w);
+                        constexpr int jj = decltype(jc)::value, j = 4 * i + jj;
+                        chain_bit<8 * i + jj, 1>(acc[jj], bg[j], bias, tb, tb2);
+                        double nb = bg_fma(bg[j], beta, bl[jj]);
+                        if constexpr (decltype(tail)::value) {
+                            if (li0 + (long long)(G::moff(i) + jj) * w >= a.acc_vec_end) nb = __dadd_rn(bl[jj], __dmul_rn(bg[j], beta));
+                        }
+                        bg[j] = nb;
                     });
                 };
-                auto chain4 = [&](auto j0) __attribute__((always_inline)) {
-                    if (!TAIL || var == 0) rows4(j0, std::false_type{});
-                    else rows4(j0, std::true_type{});
+                auto chain4 = [&](auto ic) __attribute__((always_inline)) {
+                    if (!TAIL || var == 0) rows4(ic, std::false_type{});
+                    else rows4(ic, std::true_type{});
                     __builtin_amdgcn_sched_barrier(0);
                 };
-                const long a0 = mf_read(gn, IntC<0>{}), a1 = mf_read(gn, IntC<1>{}), a2 = mf_read(gn, IntC<2>{});
-                chain_pairs<RW>(P, Hp, wvf, ln);
+                i32x4_t a01, a02, a11, a12;
+                mf_read(gn, IntC<0>{}, a01, a02);
+                mf_read(gn, IntC<1>{}, a11, a12);
                 __builtin_amdgcn_sched_barrier(0);
-                const i32x4_t d0 = mf_mul(a0), d1 = mf_mul(a1), d2 = mf_mul(a2);
+                blur4(IntC<0>{});
+                chain4(IntC<0>{});
+                blur4(IntC<1>{});
+                chain4(IntC<1>{});
+                mf_mul2(dblk, a01, a02, a11, a12);
+                // A lane holds a nibble of each block's column word; rows 4 q .. + 3 of lane l and 4 (q ^ 1) .. of lane
+                // l ^ 16 make a byte.  One v_permlane16_swap gives the lanes of an even q both nibbles of block 0 and
+                // those of an odd q both of block 1, in place: every lane stores one byte (bdst).
+                const auto sw = __builtin_amdgcn_permlane16_swap(tb, tb2, false, false);
+                colbits = (sw[0] | sw[1] << 4) & ccf.tbmask;
+                asm volatile("" : "+v"(colbits));  // (pinned here, as chain_flags does)
                 __builtin_amdgcn_sched_barrier(0);
-                blur4(std::integral_constant<int, 0>{});
-                __builtin_amdgcn_sched_barrier(0);
-                chain4(std::integral_constant<int, 0>{});
-                blur4(std::integral_constant<int, 4>{});
-                mf_store(Hn, IntC<0>{}, d0);
-                mf_store(Hn, IntC<1>{}, d1);
-                mf_store(Hn, IntC<2>{}, d2);
-                __builtin_amdgcn_sched_barrier(0);
-                chain4(std::integral_constant<int, 4>{});
-                chain_flags<RW>(tb, tb2, ccf, colbits);
             } else {
+                const uint32_t* Hp = reinterpret_cast<const uint32_t*>(Hs + b * G::HBUF);
                 if (!TAIL || var == 0)
                     chain_rows_w<KC, KEEP, false, true, RW>(a, Hp, atab, bg, wvf, ln, x0f, y0f, ccf, colbits);
                 else
@@ -1263,8 +1346,8 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
             // the frame's bits, stored after gray(t+2) consumed the loads and before the next ones:
             // vmcnt counts stores and loads in issue order, so a store issued after the prefetch
             // would be waited for with it
-            if constexpr (RW == 8)
-                reinterpret_cast<uint8_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 8 + wv] = (uint8_t)colbits;
+            if constexpr (RW == 8)  // the lane's byte of its column's word (bdst: column * 8 + byte)
+                reinterpret_cast<uint8_t*>(a.bits)[(f * a.ntiles + ti) * TS * 8 + bdst] = (uint8_t)colbits;
             else  // bytes 2wv, 2wv + 1 of the column word
                 reinterpret_cast<uint16_t*>(a.bits)[((f * a.ntiles + ti) * TS + ln) * 4 + wv] = (uint16_t)colbits;
             // unconditional (see load): past the batch's last frame it re-reads that frame
@@ -1277,10 +1360,10 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(kPixWP
     else run(edge_tile);
 
     double* bgo = a.bg_out + (size_t)s * plane;
-    const int x = x0 + ln;
+    const int x = NWB == 8 ? x0 + 16 * (wv & 3) + (ln & 15) : x0 + ln;
 #pragma unroll
     for (int j = 0; j < RW; j++) {
-        const int y = y0 + RW * wv + j;
+        const int y = NWB == 8 ? y0 + G::MROWS * (wv >> 2) + 4 * (ln >> 4) + G::moff(j >> 2) + (j & 3) : y0 + RW * wv + j;
         if (x < w && y < h) bgo[(size_t)y * w + x] = bg[j];
     }
     kstamp_end(a.kstamp);
