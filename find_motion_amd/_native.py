@@ -46,6 +46,7 @@ EXPORTED = (
     "fm_yolo_route_in_place", "fm_yolo_last_ms", "fm_yolo_create_precision", "fm_yolo_precision",
     "fm_plan", "fm_read_threshold_bits",
     "fm_resize_kind", "fm_area_up_taps", "fm_haar_set_roi_upscale", "fm_yolo_set_roi_upscale",
+    "fm_gaussian_taps",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -154,6 +155,7 @@ def load() -> C.CDLL:
     L.fm_plan.argtypes = [C.POINTER(FMParams), C.POINTER(FMPlan)]
     L.fm_resize_kind.argtypes = [C.POINTER(FMParams), C.POINTER(i32)]
     L.fm_area_up_taps.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.fm_gaussian_taps.argtypes = [i32, vp]
     L.fm_haar_set_roi_upscale.argtypes = [vp, i32]
     L.fm_yolo_set_roi_upscale.argtypes = [vp, i32]
     L.fm_last_fallbacks.argtypes = [vp]
@@ -328,6 +330,17 @@ def area_up_taps(ssize: int, dsize: int):
     if rc != FM_OK:
         raise FMError(rc, L.fm_last_error(None).decode())
     return tuple(out)
+
+
+def gaussian_taps(ksize: int) -> np.ndarray:
+    """The fixed-point Gaussian taps of an odd ksize in [1, 255] as the library builds them for every pixel path
+    (fm_gaussian_taps: host only): int32, ksize values that sum to 256.  FMError(FM_EINVAL) for any other ksize."""
+    L = load()
+    out = np.zeros(max(int(ksize), 1), np.int32)
+    rc = L.fm_gaussian_taps(int(ksize), _ptr(out))
+    if rc != FM_OK:
+        raise FMError(rc, L.fm_last_error(None).decode())
+    return out
 
 
 @dataclass

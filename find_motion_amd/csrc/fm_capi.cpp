@@ -481,7 +481,8 @@ static int plan_context(fm_ctx* c, const fm_params& p) {
     const int tiles = ((c->w + 63) / 64) * ((c->h + 63) / 64);
     c->use_fused = p.ksize <= fused_max_ksize() && fused_lds_bytes(p.ksize) <= 160 * 1024 &&
                    tiles <= 8192;  // region labelling holds the tile grid in LDS
-    // small work images (mode D: 1080p -> 100 x 56), any k: frame-parallel blur + per-pixel scan
+    // small work images (mode D: 1080p -> 100 x 56), k <= 49 (use_fused; k > 49 goes to the per-frame k_pixel, or
+    // to the wide path, which no image this small reaches): frame-parallel blur + per-pixel scan
     // (fm_small.hip; mode D 634 -> 746 k frames/s, round 5), unless the caller keeps the gray / blur /
     // delta planes (k_pix writes them).  Both it and k_pix write threshold bits for the dilating contour pass.
     c->use_small = c->use_fused && (size_t)c->h * c->w >= 16 && !(p.flags & FM_FLAG_KEEP_PLANES) &&
@@ -538,6 +539,14 @@ int fm_area_up_taps(int ssize, int dsize, int32_t* s0, int32_t* s1, int32_t* a0,
     std::copy(A.s1.begin(), A.s1.end(), s1);
     std::copy(A.a0.begin(), A.a0.end(), a0);
     std::copy(A.a1.begin(), A.a1.end(), a1);
+    return FM_OK;
+}
+
+int fm_gaussian_taps(int ksize, int32_t* out) {
+    std::vector<int32_t> taps;
+    if (!out) return failf(kNoCtx, FM_EINVAL, "null argument");
+    if (!gaussian_taps(ksize, taps)) return failf(kNoCtx, FM_EINVAL, "ksize %d must be odd and in [1, %d]", ksize, kMaxK);
+    std::copy(taps.begin(), taps.end(), out);
     return FM_OK;
 }
 

@@ -101,7 +101,7 @@ void fm_destroy(fm_ctx* ctx);
 
 /* What fm_create would set up for params, without touching a device: the same validation (and error codes)
  * and the same selection, by the same code.  pixel_path names the kernels of the per-pixel chain:
- *   "small"  k_small_blur + k_small_scan (work images of at most 16,384 pixels)
+ *   "small"  k_small_blur + k_small_scan (work images of at most 16,384 pixels, ksize up to 49)
  *   "pix"    k_pix (ksize 3, 5, 7, 21)
  *   "fused"  k_fused (other ksize up to 49)
  *   "wide"   k_wide_blur + k_small_scan (ksize above 49, more than 16 and at most 8,192 tiles of 64 x 64,
@@ -127,6 +127,9 @@ int fm_resize_kind(const fm_params* params, int* kind);
  * and the detectors build them (host only): per destination index the two source indices and their 11-bit
  * coefficients (a0 + a1 = 2048), dsize values each. */
 int fm_area_up_taps(int ssize, int dsize, int32_t* s0, int32_t* s1, int32_t* a0, int32_t* a1);
+/* The 8-bit fixed-point Gaussian taps every pixel path blurs with at this ksize (host only): ksize values that
+ * sum to 256.  FM_EINVAL for an even ksize, one below 1 or above 255, or a null pointer; out is then untouched. */
+int fm_gaussian_taps(int ksize, int32_t* out);
 
 /* Last error message for ctx (or the calling thread's last error if ctx is NULL). */
 const char* fm_last_error(const fm_ctx* ctx);

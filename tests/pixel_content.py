@@ -21,7 +21,8 @@ test_gpu_pixel_content.py runs, so the GPU module's inputs are proven without a 
 
 pixel_cases() lists the matrix (path x content / threshold / alpha), build_case() makes a case's frames and
 settings, and run_case() drives it: on the oracle alone, asserting the conditions, or beside an engine, comparing
-every batch bit for bit as well.
+every batch bit for bit as well.  run_frames() is run_case() on a geometry and frames given directly
+(ksize_sweep.py's cases, which are not registered in CASES).
 """
 import functools
 
@@ -361,19 +362,28 @@ def run_case(name, axis, value, eng=None):
     the oracle's planes.  With an engine (created by the caller with the case's settings) the same frames go
     through it and every batch is compared bit for bit: masks, counts, boxes, origins, the float64 background,
     and gray / blur / delta where the engine keeps planes.  Returns the measures the conditions were read from."""
+    content = value if axis == "content" else "delta_sweep" if axis == "threshold" else "cells"
+    return run_frames(case_id((name, axis, value)), CASES[name][:5], build_case(name, axis, value), content, eng=eng)
+
+
+def run_frames(cid, geom, c, content, eng=None, T=T, NB=NB):
+    """run_case on a geometry (W, H, box, k, keep_planes) that need not be registered in CASES and a build_case
+    dict whose frames are [NB * T][S][H][W][3] (any S); `cid` names the case in messages.  The content `patches`
+    (ksize_sweep.py: gray_edges in squares of a quarter of the kernel) has two conditions: a steady frame whose
+    mask is partial, as the others, and a blur plane that spans at least 40 levels on every steady frame."""
     from find_motion_amd._native import PLANE_BLUR, PLANE_DELTA, PLANE_GRAY
 
-    W, H, box, k, h = geometry(name)
-    c = build_case(name, axis, value)
+    W, H, box, k, planes = geom
     fr, thresh, alpha = c["frames"], c["thresh"], c["alpha"]
+    S = fr.shape[1]
+    assert fr.shape[0] == NB * T
     cfg = oracle.OracleConfig(H=H, W=W, box=box, ksize=k, thresh=thresh, alpha=alpha)
     orc = [oracle.OracleStream(cfg) for _ in range(S)]
     if eng is not None:
         assert eng.work_shape == (cfg.h, cfg.w)
-        assert (eng.params.threshold, eng.params.avg, eng.keep_planes) == (thresh, alpha, CASES[name][4])
-    content = value if axis == "content" else "delta_sweep" if axis == "threshold" else "cells"
+        assert (eng.params.threshold, eng.params.avg, eng.keep_planes) == (thresh, alpha, planes)
     m = dict(fractions=[], blur255=0, blur0=0, run_row=0, run_col=0, ties=0, negative=0, above=0,
-             residues=None, deltas=None)
+             residues=None, deltas=None, blur_span=None)
     for b in range(NB):
         if c["write"] and c["write"][0] == b:
             for s, plane in enumerate(c["write"][1]):
@@ -391,7 +401,7 @@ def run_case(name, axis, value, eng=None):
                 first = not orc[s].initialized
                 bg_before = orc[s].bg.copy()
                 ref = orc[s].step(bfr[t, s])
-                at = f"{case_id((name, axis, value))}: batch {b} frame {t} stream {s}"
+                at = f"{cid}: batch {b} frame {t} stream {s}"
                 assert ref["count"] <= 4096, at
                 if eng is not None:
                     if eng.keep_planes:
@@ -430,6 +440,9 @@ def run_case(name, axis, value, eng=None):
                 if sweep and 0 <= thresh <= 254:
                     lo, hi = delta_counts(ref, thresh)
                     m["deltas"] = (lo, hi) if m["deltas"] is None else (min(lo, m["deltas"][0]), min(hi, m["deltas"][1]))
+                if content == "patches":
+                    span = int(ref["blur"].max()) - int(ref["blur"].min())
+                    m["blur_span"] = span if m["blur_span"] is None else min(span, m["blur_span"])
                 if content == "gray_edges":
                     rc = residue_counts(oracle.resize_area_bgr(bfr[t, s], box) if W != box else bfr[t, s])
                     m["residues"] = rc if m["residues"] is None else [min(p, q) for p, q in zip(rc, m["residues"])]
@@ -437,10 +450,9 @@ def run_case(name, axis, value, eng=None):
             for s in range(S):
                 bg = eng.background(s)
                 assert np.array_equal(bg, orc[s].bg), \
-                    f"{case_id((name, axis, value))}: batch {b}: background stream {s}: " \
+                    f"{cid}: batch {b}: background stream {s}: " \
                     f"{int((bg != orc[s].bg).sum())} values differ"
     # --- what the case must have shown ---
-    cid = case_id((name, axis, value))
     if c["expect"] == "partial":
         assert any(0.02 <= f <= 0.98 for f in m["fractions"]), f"{cid}: mask fractions {m['fractions']}"
     if content in ("cells", "white"):
@@ -453,6 +465,8 @@ def run_case(name, axis, value, eng=None):
             assert min(m["negative"], m["above"]) >= 100, f"{cid}: {m['negative']} negative, {m['above']} above 255"
     if content == "gray_edges":
         assert min(m["residues"]) >= 200, f"{cid}: residues {GRAY_RESIDUES} occur {m['residues']} times"
+    if content == "patches":
+        assert m["blur_span"] >= 40, f"{cid}: a steady frame's blur plane spans {m['blur_span']} levels"
     if content == "delta_sweep" and 0 <= thresh <= 254:
         assert min(m["deltas"]) >= 50, f"{cid}: {m['deltas']} pixels at delta {thresh} and {thresh + 1}"
     return m
