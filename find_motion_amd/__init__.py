@@ -30,6 +30,7 @@ def use_hw_queues(n: int = 8, force: bool = False) -> int:
 
 
 from ._native import (  # noqa: F401
+    CascadeBank,
     CascadeClassifier,
     Contour,
     FMError,

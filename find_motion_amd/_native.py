@@ -47,6 +47,10 @@ EXPORTED = (
     "fm_plan", "fm_read_threshold_bits",
     "fm_resize_kind", "fm_area_up_taps", "fm_haar_set_roi_upscale", "fm_yolo_set_roi_upscale",
     "fm_gaussian_taps",
+    "fm_haar_bank_create", "fm_haar_bank_destroy", "fm_haar_bank_last_error", "fm_haar_bank_size",
+    "fm_haar_bank_detect", "fm_haar_bank_set_roi_upscale", "fm_haar_bank_detect_frames",
+    "fm_haar_bank_detect_frame_list", "fm_haar_bank_detect_frame_list_async", "fm_haar_bank_collect",
+    "fm_haar_bank_candidates", "fm_haar_bank_last_ms",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -178,6 +182,21 @@ def load() -> C.CDLL:
     L.fm_haar_last_ms.argtypes = [vp]
     L.fm_haar_last_ms.restype = C.c_double
     L.fm_haar_last_sweep.argtypes = [vp]
+    L.fm_haar_bank_create.argtypes = [i32, C.POINTER(FMHaarDesc), i32, C.POINTER(vp)]
+    L.fm_haar_bank_destroy.argtypes = [vp]
+    L.fm_haar_bank_destroy.restype = None
+    L.fm_haar_bank_last_error.argtypes = [vp]
+    L.fm_haar_bank_last_error.restype = C.c_char_p
+    L.fm_haar_bank_size.argtypes = [vp]
+    L.fm_haar_bank_detect.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_double, i32, vp, i32, vp]
+    L.fm_haar_bank_set_roi_upscale.argtypes = [vp, i32]
+    L.fm_haar_bank_detect_frames.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_double, i32, vp, i32, vp, vp]
+    L.fm_haar_bank_detect_frame_list.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, i32, vp, i32, vp, vp]
+    L.fm_haar_bank_detect_frame_list_async.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, i32, vp]
+    L.fm_haar_bank_collect.argtypes = [vp, vp, i32, vp, i32]
+    L.fm_haar_bank_candidates.argtypes = [vp, i32, vp, i32]
+    L.fm_haar_bank_last_ms.argtypes = [vp]
+    L.fm_haar_bank_last_ms.restype = C.c_double
     L.fm_mjpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fm_mjpeg_destroy.argtypes = [vp]
     L.fm_mjpeg_destroy.restype = None
@@ -225,7 +244,7 @@ def load() -> C.CDLL:
     L.fm_yolo_last_ms.restype = C.c_double
     for name in EXPORTED:
         if name not in ("fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_last_ms", "fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
-                        "fm_haar_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
+                        "fm_haar_last_ms", "fm_haar_bank_destroy", "fm_haar_bank_last_error", "fm_haar_bank_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
                         "fm_mjpeg_enc_destroy", "fm_mjpeg_enc_last_error", "fm_mjpeg_enc_last_ms"):
             getattr(L, name).restype = i32
     _lib = L
@@ -909,6 +928,156 @@ class CascadeClassifier:
     def close(self):
         if self._h:
             load().fm_haar_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def haar_desc(cs):
+    """A cascade.Cascade as (FMHaarDesc, keep-alive list of its arrays)."""
+    keep = [np.ascontiguousarray(a) for a in (
+        cs.stage_ntrees, cs.stage_threshold, cs.tree_nodes, cs.node_left, cs.node_right, cs.node_feature,
+        cs.node_threshold, cs.leaves, cs.feat_rects, cs.feat_weights, cs.feat_tilted)]
+    d = FMHaarDesc(cs.win_w, cs.win_h, len(cs.stage_ntrees), len(cs.tree_nodes), len(cs.node_left),
+                   len(cs.leaves), len(cs.feat_tilted), *[_ptr(a) for a in keep])
+    return d, keep
+
+
+class CascadeBank:
+    """Several HAAR cascades over the same frames in one GPU pass (fm_haar_bank_*): the frames are uploaded
+    and resized once, one pyramid and one set of integral images serve every member, and one launch sweeps
+    all their windows.  Each member's results are those of a CascadeClassifier built from the same cascade.
+
+    `CascadeBank(cascades)` takes 1..32 XML paths or cascade.Cascade objects.  The methods mirror
+    CascadeClassifier's (default min and max sizes) and return a list per member of lists per image of
+    (k, 4) int32 arrays.  A cascade whose window does not fit the tiled sweep is refused (FM_ENOTSUP):
+    keep a CascadeClassifier for it."""
+
+    def __init__(self, cascades, device: int = 0, roi_upscale: bool = False):
+        from .cascade import Cascade, parse
+        self.cascades = [c if isinstance(c, Cascade) else parse(c) for c in cascades]
+        self._h = None
+        L = load()
+        descs, self._keep = (FMHaarDesc * max(len(self.cascades), 1))(), []
+        for i, cs in enumerate(self.cascades):
+            descs[i], keep = haar_desc(cs)
+            self._keep.append(keep)
+        h = C.c_void_p()
+        rc = L.fm_haar_bank_create(int(device), descs, len(self.cascades), C.byref(h))
+        if rc != FM_OK:
+            msg = L.fm_haar_bank_last_error(h).decode() if h else ""
+            L.fm_haar_bank_destroy(h)
+            raise FMError(rc, f"fm_haar_bank_create: {msg}")
+        self._h = h
+        if roi_upscale:
+            self.set_roi_upscale(True)
+
+    def __len__(self) -> int:
+        return len(self.cascades)
+
+    def set_roi_upscale(self, on: bool) -> None:
+        load().fm_haar_bank_set_roi_upscale(self._h, int(bool(on)))
+
+    def _results(self, what: str, n: int, cap: int, call):
+        """call(rects, cap, counts) -> rc, repeated with a larger cap while some count exceeds it."""
+        L, M = load(), len(self.cascades)
+        while True:
+            rects = np.zeros((M, n, cap, 4), np.int32)
+            counts = np.zeros((M, n), np.int32)
+            rc = call(_ptr(rects), cap, _ptr(counts))
+            if rc != FM_OK:
+                raise FMError(rc, f"{what}: {L.fm_haar_bank_last_error(self._h).decode()}")
+            if counts.max(initial=0) <= cap:
+                return [[rects[m, i, :counts[m, i]].copy() for i in range(n)] for m in range(M)]
+            cap = int(counts.max())
+
+    def detect_batch(self, images: np.ndarray, scaleFactor=1.1, minNeighbors=5, cap: int = 256):
+        """images: [n, H, W, 3] BGR or [n, H, W] gray u8 -> per member, per image, (k, 4) int32 rects."""
+        L = load()
+        imgs = np.ascontiguousarray(images, np.uint8)
+        if imgs.ndim not in (3, 4) or (imgs.ndim == 4 and imgs.shape[3] != 3):
+            raise ValueError("images must be [n, H, W, 3] BGR or [n, H, W] gray")
+        ch = 3 if imgs.ndim == 4 else 1
+        n, H, W = imgs.shape[:3]
+        return self._results("fm_haar_bank_detect", n, cap, lambda r, c, k: L.fm_haar_bank_detect(
+            self._h, _ptr(imgs), n, H, W, ch, 0, float(scaleFactor), int(minNeighbors), r, c, k))
+
+    def detect_frames(self, frames, roi_w: int = 300, scaleFactor=1.1, minNeighbors=5, cap: int = 256):
+        """CascadeClassifier.detect_frames for every member: raw BGR frames [n, H, W, 3] as a host array, a
+        contiguous uint8 torch tensor on the bank's GPU, or a tuple (device address, n, H, W); one INTER_AREA
+        resize to width roi_w, rects in ROI coordinates."""
+        L = load()
+        if isinstance(frames, tuple):
+            ptr, n, H, W = frames
+            fr, ptr, on_dev = None, C.c_void_p(ptr), 1
+        elif getattr(frames, "is_cuda", False):
+            import torch
+            if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+                raise ValueError("device frames must be a contiguous uint8 tensor [n, H, W, 3]")
+            torch.cuda.current_stream(frames.device).synchronize()
+            fr, ptr, on_dev = frames, C.c_void_p(frames.data_ptr()), 1
+            n, H, W = frames.shape[:3]
+        else:
+            fr = np.ascontiguousarray(frames, np.uint8)
+            if fr.ndim != 4 or fr.shape[3] != 3:
+                raise ValueError("frames must be [n, H, W, 3] BGR")
+            ptr, on_dev = _ptr(fr), 0
+            n, H, W = fr.shape[:3]
+        n, H, W = int(n), int(H), int(W)
+        rh = C.c_int32()
+        return self._results("fm_haar_bank_detect_frames", n, cap, lambda r, c, k: L.fm_haar_bank_detect_frames(
+            self._h, ptr, n, H, W, on_dev, int(roi_w), float(scaleFactor), int(minNeighbors), r, c, k, C.byref(rh)))
+
+    def detect_frame_list(self, ptrs, H: int, W: int, roi_w: int = 300, scaleFactor=1.1, minNeighbors=5,
+                          cap: int = 256):
+        """detect_frames over frames already in device memory at separate addresses `ptrs` (each [H, W, 3])."""
+        L = load()
+        n = len(ptrs)
+        arr = (C.c_void_p * max(n, 1))(*[int(p) for p in ptrs])
+        rh = C.c_int32()
+        return self._results("fm_haar_bank_detect_frame_list", n, cap, lambda r, c, k: L.fm_haar_bank_detect_frame_list(
+            self._h, C.cast(arr, C.c_void_p), n, int(H), int(W), int(roi_w), float(scaleFactor), int(minNeighbors),
+            r, c, k, C.byref(rh)))
+
+    def detect_frame_list_async(self, ptrs, H: int, W: int, roi_w: int = 300, scaleFactor=1.1, minNeighbors=5) -> int:
+        """detect_frame_list queued on the bank's stream without waiting; `collect` returns its results.  One
+        detection in flight per bank; the frames stay in place until it is collected.  Returns the frame count."""
+        L = load()
+        n = len(ptrs)
+        arr = (C.c_void_p * max(n, 1))(*[int(p) for p in ptrs])
+        rh = C.c_int32()
+        rc = L.fm_haar_bank_detect_frame_list_async(self._h, C.cast(arr, C.c_void_p), n, int(H), int(W), int(roi_w),
+                                                    float(scaleFactor), int(minNeighbors), C.byref(rh))
+        if rc != FM_OK:
+            raise FMError(rc, f"fm_haar_bank_detect_frame_list_async: {L.fm_haar_bank_last_error(self._h).decode()}")
+        return n
+
+    def collect(self, n: int, cap: int = 256):
+        """The queued detection's results (waits for it), as detect_frame_list returns them."""
+        L = load()
+        return self._results("fm_haar_bank_collect", int(n), cap,
+                             lambda r, c, k: L.fm_haar_bank_collect(self._h, r, c, k, int(n)))
+
+    def candidates(self, member: int) -> np.ndarray:
+        """Ungrouped candidates of image 0 of the last call, for one member (parity tests)."""
+        L = load()
+        if not 0 <= int(member) < len(self.cascades):
+            raise IndexError(f"member {member} of {len(self.cascades)}")
+        n = L.fm_haar_bank_candidates(self._h, int(member), None, 0)
+        out = np.zeros((max(n, 1), 4), np.int32)
+        L.fm_haar_bank_candidates(self._h, int(member), _ptr(out), n)
+        return out[:n]
+
+    def last_ms(self) -> float:
+        return float(load().fm_haar_bank_last_ms(self._h))
+
+    def close(self):
+        if self._h:
+            load().fm_haar_bank_destroy(self._h)
             self._h = None
 
     def __del__(self):

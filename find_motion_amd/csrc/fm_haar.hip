@@ -16,6 +16,8 @@
 //              with float32 feature sums without FMA and double leaf sums;
 //              survivors are compacted into a list
 //   k_heval_tail  the remaining stages over the survivors (dense waves)
+// Several cascades over the same frames: the bank at the end of this file (k_bdetect, k_bwalk, fm_haar_bank_*)
+// shares everything up to the integrals and sweeps all members' windows in one launch.
 // Host side: the x-skip of rows whose window was rejected by stage 0 and
 // groupRectangles (partition + class means + nested-rect filter), both
 // sequential by definition and tiny next to the window sweep.
@@ -660,39 +662,33 @@ static void linear_exact_taps(int ssize, int dsize, std::vector<int2>& out) {
     }
 }
 
-extern "C" {
-
-int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
-    if (!out) return FM_EINVAL;
-    *out = nullptr;
-    auto* h = new fm_haar();
-    *out = h;
-    h->times = fm::dev_env("FM_HAAR_TIMES") != nullptr;  // (dev build only)
+// fm_haar_create's checks of a cascade description (no HIP call); *tilted_out: some feature is tilted
+static int check_desc(const fm_haar_desc* d, std::string* err, int* tilted_out) {
     if (!d || d->win_w < 3 || d->win_h < 3 || d->n_stages < 1 || d->n_trees < 1 || d->n_nodes < 1 ||
         d->n_features < 1 || d->n_leaves != d->n_trees + d->n_nodes)
-        return fm::failf(&h->err, FM_EINVAL, "bad cascade description (window >= 3x3, stages/trees/nodes/features >= 1, "
+        return fm::failf(err, FM_EINVAL, "bad cascade description (window >= 3x3, stages/trees/nodes/features >= 1, "
                                    "leaves == trees + nodes)");
     int tsum = 0;
     for (int s = 0; s < d->n_stages; ++s) {
-        if (d->stage_ntrees[s] < 1) return fm::failf(&h->err, FM_EINVAL, "stage %d has no trees", s);
+        if (d->stage_ntrees[s] < 1) return fm::failf(err, FM_EINVAL, "stage %d has no trees", s);
         tsum += d->stage_ntrees[s];
     }
-    if (tsum != d->n_trees) return fm::failf(&h->err, FM_EINVAL, "stage tree counts sum to %d, not n_trees %d", tsum, d->n_trees);
+    if (tsum != d->n_trees) return fm::failf(err, FM_EINVAL, "stage tree counts sum to %d, not n_trees %d", tsum, d->n_trees);
     int nsum = 0;
     for (int t = 0; t < d->n_trees; ++t) {
-        if (d->tree_nodes[t] < 1) return fm::failf(&h->err, FM_EINVAL, "tree %d has no nodes", t);
+        if (d->tree_nodes[t] < 1) return fm::failf(err, FM_EINVAL, "tree %d has no nodes", t);
         nsum += d->tree_nodes[t];
     }
-    if (nsum != d->n_nodes) return fm::failf(&h->err, FM_EINVAL, "tree node counts sum to %d, not n_nodes %d", nsum, d->n_nodes);
+    if (nsum != d->n_nodes) return fm::failf(err, FM_EINVAL, "tree node counts sum to %d, not n_nodes %d", nsum, d->n_nodes);
     // node links stay inside their tree; features inside the window
     for (int t = 0, o = 0; t < d->n_trees; o += d->tree_nodes[t], ++t)
         for (int k = 0; k < d->tree_nodes[t]; ++k) {
             const int l = d->node_left[o + k], r = d->node_right[o + k], f = d->node_feature[o + k];
             if (l >= d->tree_nodes[t] || r >= d->tree_nodes[t] || l < -d->tree_nodes[t] || r < -d->tree_nodes[t] ||
                 f < 0 || f >= d->n_features)
-                return fm::failf(&h->err, FM_EINVAL, "tree %d node %d: link or feature out of range", t, k);
+                return fm::failf(err, FM_EINVAL, "tree %d node %d: link or feature out of range", t, k);
             if ((l > 0 && l <= k) || (r > 0 && r <= k))
-                return fm::failf(&h->err, FM_EINVAL, "tree %d node %d: links must point forward", t, k);
+                return fm::failf(err, FM_EINVAL, "tree %d node %d: links must point forward", t, k);
         }
     int tilted = 0;
     for (int i = 0; i < d->n_features; ++i) {
@@ -705,26 +701,16 @@ int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
             const bool ok = !tl ? (x >= 0 && y >= 0 && w >= 0 && hh >= 0 && x + w <= d->win_w && y + hh <= d->win_h)
                                 : (w >= 0 && hh >= 0 && x - hh >= 0 && x + w <= d->win_w && y >= 0 &&
                                    y + w + hh <= d->win_h);
-            if (!ok) return fm::failf(&h->err, FM_EINVAL, "feature %d rect %d outside the %dx%d window", i, j, d->win_w, d->win_h);
+            if (!ok) return fm::failf(err, FM_EINVAL, "feature %d rect %d outside the %dx%d window", i, j, d->win_w, d->win_h);
         }
     }
-    h->device = device;
-    FM_HIP_TRY(&h->err, hipSetDevice(device));
-    {   // the detector's stream at the pixel stream's (high) priority: a motion engine on the same device
-        // always has a pixel launch queued at high priority, and at normal priority the cascade's
-        // launches waited behind them (configs[4]: a 1 ms call took 4.4 ms of wall time).  With the detection
-        // asynchronous (round 5) the priority no longer matters: 63.6-63.9 k frames/s either way.
-        int lo = 0, hi = 0;
-        FM_HIP_TRY(&h->err, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        FM_HIP_TRY(&h->err, hipStreamCreateWithPriority(h->stream.put(), hipStreamNonBlocking, hi));
-    }
-    FM_HIP_TRY(&h->err, hipEventCreate(h->e0.put()));
-    FM_HIP_TRY(&h->err, hipEventCreate(h->e1.put()));
-    h->win_w = d->win_w;
-    h->win_h = d->win_h;
-    h->n_stages = d->n_stages;
-    h->has_tilted = tilted;
+    *tilted_out = tilted;
+    return FM_OK;
+}
 
+// The checked description as one device blob and the CascadeDev that points into it (current device)
+static int upload_cascade(const fm_haar_desc* d, int tilted, fm::DevBuf<uint8_t>& blob_out, CascadeDev* cd,
+                          std::string* err) {
     std::vector<int> sfirst(d->n_stages), tno(d->n_trees), tlo(d->n_trees);
     for (int s = 0, t = 0; s < d->n_stages; t += d->stage_ntrees[s], ++s) sfirst[s] = t;
     for (int t = 0, no = 0, lo = 0; t < d->n_trees; ++t) {
@@ -803,15 +789,45 @@ int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
         std::memcpy(&blob[tot], recs.data(), recs.size() * sizeof(StumpRec));
         tot = blob.size();
     }
-    FM_HIP_TRY(&h->err, h->d_blob.reserve(tot));
-    FM_HIP_TRY(&h->err, hipMemcpy(h->d_blob, blob.data(), tot, hipMemcpyHostToDevice));
-    const uint8_t* b = h->d_blob;
-    h->cd = CascadeDev{d->win_w, d->win_h, d->n_stages, tilted, stumps,
+    FM_HIP_TRY(err, blob_out.reserve(tot));
+    FM_HIP_TRY(err, hipMemcpy(blob_out, blob.data(), tot, hipMemcpyHostToDevice));
+    const uint8_t* b = blob_out;
+    *cd = CascadeDev{d->win_w, d->win_h, d->n_stages, tilted, stumps,
                        (const int*)(b + off[0]), (const int*)(b + off[1]), (const float*)(b + off[2]),
                        (const int*)(b + off[3]), (const int*)(b + off[4]), (const Node*)(b + off[5]),
                        (const float*)(b + off[6]), (const Feat*)(b + off[7]),
                        stumps ? (const StumpRec*)(b + rec_off) : nullptr, stumps ? d->n_trees : 0};
     return FM_OK;
+}
+
+extern "C" {
+
+int fm_haar_create(int device, const fm_haar_desc* d, fm_haar** out) {
+    if (!out) return FM_EINVAL;
+    *out = nullptr;
+    auto* h = new fm_haar();
+    *out = h;
+    h->times = fm::dev_env("FM_HAAR_TIMES") != nullptr;  // (dev build only)
+    int tilted = 0;
+    if (int rc = check_desc(d, &h->err, &tilted)) return rc;
+    h->device = device;
+    FM_HIP_TRY(&h->err, hipSetDevice(device));
+    {   // the detector's stream at the pixel stream's (high) priority: a motion engine on the same device
+        // always has a pixel launch queued at high priority, and at normal priority the cascade's
+        // launches waited behind them (configs[4]: a 1 ms call took 4.4 ms of wall time).  With the detection
+        // asynchronous (round 5) the priority no longer matters: 63.6-63.9 k frames/s either way.
+        int lo = 0, hi = 0;
+        FM_HIP_TRY(&h->err, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        FM_HIP_TRY(&h->err, hipStreamCreateWithPriority(h->stream.put(), hipStreamNonBlocking, hi));
+    }
+    FM_HIP_TRY(&h->err, hipEventCreate(h->e0.put()));
+    FM_HIP_TRY(&h->err, hipEventCreate(h->e1.put()));
+    h->win_w = d->win_w;
+    h->win_h = d->win_h;
+    h->n_stages = d->n_stages;
+    h->has_tilted = tilted;
+
+    return upload_cascade(d, tilted, h->d_blob, &h->cd, &h->err);
 }
 
 void fm_haar_destroy(fm_haar* h) { delete h; }
@@ -1001,6 +1017,108 @@ static int detect_enqueue(fm_haar* h, const uint8_t* images, int n, int H, int W
     return rc;
 }
 
+// One image's host post-pass for a cascade of window win_w x win_h on the window grids of g (n, step, gw, gh,
+// woff): OpenCV's visiting order from the device's candidate list L[nc0] (sorted here), or -- R != nullptr -- the
+// row scan with the stage-0 skip over the image's result grid; then groupRectangles(min_neighbors, eps 0.2).
+// c: the ungrouped candidates, outr: the detections (x, y, w, h each).
+static void post_pass(const std::vector<float>& sc, const Geo& g, int win_w, int win_h, int min_neighbors, int* L,
+                      int nc0, const int8_t* R, std::vector<int32_t>& c, std::vector<int32_t>& outr) {
+    const double eps = 0.2;
+    c.clear();
+    outr.clear();
+    auto emit = [&](int s, int gy, int gx) {
+        const float f = sc[s];
+        const int wsw = rne_f((float)win_w * f), wsh = rne_f((float)win_h * f);
+        const int x = gx * g.step[s], y = gy * g.step[s];
+        c.insert(c.end(), {rne_f((float)x * f), rne_f((float)y * f), wsw, wsh});
+    };
+    if (!R) {  // the device's list: sorted window indices are OpenCV's visiting order
+        std::sort(L, L + nc0);
+        for (int k = 0, s = 0; k < nc0; ++k) {
+            while (s + 1 < g.n && L[k] >= g.woff[s + 1]) ++s;
+            const int q = L[k] - g.woff[s], gy = q / g.gw[s];
+            emit(s, gy, q - gy * g.gw[s]);
+        }
+    } else {
+        for (int s = 0; s < g.n; ++s)
+            for (int gy = 0; gy < g.gh[s]; ++gy)
+                for (int gx = 0; gx < g.gw[s];) {
+                    const int8_t v = R[g.woff[s] + gy * g.gw[s] + gx];
+                    if (v > 0) emit(s, gy, gx);
+                    gx += v == 0 ? 2 : 1;
+                }
+    }
+    const int nc = (int)c.size() / 4;
+    if (min_neighbors <= 0) {
+        outr = c;
+    } else if (nc > 0) {
+        auto similar = [&](int a, int b) {
+            const int32_t* r1 = &c[4 * a];
+            const int32_t* r2 = &c[4 * b];
+            const double delta = eps * (std::min(r1[2], r2[2]) + std::min(r1[3], r2[3])) * 0.5;
+            return std::abs(r1[0] - r2[0]) <= delta && std::abs(r1[1] - r2[1]) <= delta &&
+                   std::abs(r1[0] + r1[2] - r2[0] - r2[2]) <= delta && std::abs(r1[1] + r1[3] - r2[1] - r2[3]) <= delta;
+        };
+        // cv::partition
+        std::vector<int> par(nc, -1), rk(nc, 0);
+        auto root = [&](int i) {
+            while (par[i] >= 0) i = par[i];
+            return i;
+        };
+        for (int i = 0; i < nc; ++i) {
+            int r = root(i);
+            for (int j = 0; j < nc; ++j) {
+                if (i == j || !similar(i, j)) continue;
+                int r2 = root(j);
+                if (r2 == r) continue;
+                if (rk[r] > rk[r2]) {
+                    par[r2] = r;
+                } else {
+                    par[r] = r2;
+                    rk[r2] += rk[r] == rk[r2];
+                    r = r2;
+                }
+                for (int k = j, p; (p = par[k]) >= 0; k = p) par[k] = r;
+                for (int k = i, p; (p = par[k]) >= 0; k = p) par[k] = r;
+            }
+        }
+        std::vector<int> lab(nc), cls_of_root(nc, -1);
+        int ncls = 0;
+        for (int i = 0; i < nc; ++i) {
+            const int r = root(i);
+            if (cls_of_root[r] < 0) cls_of_root[r] = ncls++;
+            lab[i] = cls_of_root[r];
+        }
+        std::vector<long long> acc(4 * (size_t)ncls, 0);
+        std::vector<int> cnt(ncls, 0);
+        for (int i = 0; i < nc; ++i) {
+            for (int k = 0; k < 4; ++k) acc[4 * lab[i] + k] += c[4 * i + k];
+            cnt[lab[i]]++;
+        }
+        std::vector<int32_t> avg(4 * (size_t)ncls);
+        for (int l = 0; l < ncls; ++l) {
+            const float sinv = 1.f / (float)cnt[l];
+            for (int k = 0; k < 4; ++k) avg[4 * l + k] = rne_f((float)(int)acc[4 * l + k] * sinv);
+        }
+        for (int i = 0; i < ncls; ++i) {
+            const int32_t* r1 = &avg[4 * i];
+            const int n1 = cnt[i];
+            if (n1 <= min_neighbors) continue;
+            int j = 0;
+            for (; j < ncls; ++j) {
+                const int n2 = cnt[j];
+                if (j == i || n2 <= min_neighbors) continue;
+                const int32_t* r2 = &avg[4 * j];
+                const int dx = rne_d(r2[2] * eps), dy = rne_d(r2[3] * eps);
+                if (r1[0] >= r2[0] - dx && r1[1] >= r2[1] - dy && r1[0] + r1[2] <= r2[0] + r2[2] + dx &&
+                    r1[1] + r1[3] <= r2[1] + r2[3] + dy && (n2 > std::max(3, n1) || n1 < 3))
+                    break;
+            }
+            if (j == ncls) outr.insert(outr.end(), r1, r1 + 4);
+        }
+    }
+}
+
 // Waits for the queued detection and runs the host post-pass: OpenCV's row walk order from the device's
 // sorted candidate lists (or the whole result grid when a list overflowed), then groupRectangles.
 static int detect_finish(fm_haar* h) {
@@ -1026,105 +1144,11 @@ static int detect_finish(fm_haar* h) {
 
     // per image: the row scan with the stage-0 skip, then groupRectangles (eps 0.2); images are
     // independent (each writes only its own counts / rects), so a batch spreads them over threads
-    const double eps = 0.2;
     auto post = [&](int img) {
-        std::vector<int32_t> c;
-        auto emit = [&](int s, int gy, int gx) {
-            const float f = sc[s];
-            const int wsw = rne_f((float)h->win_w * f), wsh = rne_f((float)h->win_h * f);
-            const int x = gx * g.step[s], y = gy * g.step[s];
-            c.insert(c.end(), {rne_f((float)x * f), rne_f((float)y * f), wsw, wsh});
-        };
-        if (!overflow) {  // the device's lists: sorted window indices are OpenCV's visiting order
-            const int nc0 = h->h_ccnt[img];
-            int* L = h->h_cand + (size_t)img * kCandCap;
-            std::sort(L, L + nc0);
-            for (int k = 0, s = 0; k < nc0; ++k) {
-                while (s + 1 < g.n && L[k] >= g.woff[s + 1]) ++s;
-                const int q = L[k] - g.woff[s], gy = q / g.gw[s];
-                emit(s, gy, q - gy * g.gw[s]);
-            }
-        } else {
-            const int8_t* R = h->h_res.data() + (size_t)img * g.NW;
-            for (int s = 0; s < g.n; ++s)
-                for (int gy = 0; gy < g.gh[s]; ++gy)
-                    for (int gx = 0; gx < g.gw[s];) {
-                        const int8_t v = R[g.woff[s] + gy * g.gw[s] + gx];
-                        if (v > 0) emit(s, gy, gx);
-                        gx += v == 0 ? 2 : 1;
-                    }
-        }
+        std::vector<int32_t> c, outr;
+        post_pass(sc, g, h->win_w, h->win_h, min_neighbors, h->h_cand + (size_t)img * kCandCap, overflow ? 0 : h->h_ccnt[img],
+                  overflow ? h->h_res.data() + (size_t)img * g.NW : nullptr, c, outr);
         if (img == 0) h->cand = c;
-        const int nc = (int)c.size() / 4;
-        std::vector<int32_t> outr;
-        if (min_neighbors <= 0) {
-            outr = c;
-        } else if (nc > 0) {
-            auto similar = [&](int a, int b) {
-                const int32_t* r1 = &c[4 * a];
-                const int32_t* r2 = &c[4 * b];
-                const double delta = eps * (std::min(r1[2], r2[2]) + std::min(r1[3], r2[3])) * 0.5;
-                return std::abs(r1[0] - r2[0]) <= delta && std::abs(r1[1] - r2[1]) <= delta &&
-                       std::abs(r1[0] + r1[2] - r2[0] - r2[2]) <= delta && std::abs(r1[1] + r1[3] - r2[1] - r2[3]) <= delta;
-            };
-            // cv::partition
-            std::vector<int> par(nc, -1), rk(nc, 0);
-            auto root = [&](int i) {
-                while (par[i] >= 0) i = par[i];
-                return i;
-            };
-            for (int i = 0; i < nc; ++i) {
-                int r = root(i);
-                for (int j = 0; j < nc; ++j) {
-                    if (i == j || !similar(i, j)) continue;
-                    int r2 = root(j);
-                    if (r2 == r) continue;
-                    if (rk[r] > rk[r2]) {
-                        par[r2] = r;
-                    } else {
-                        par[r] = r2;
-                        rk[r2] += rk[r] == rk[r2];
-                        r = r2;
-                    }
-                    for (int k = j, p; (p = par[k]) >= 0; k = p) par[k] = r;
-                    for (int k = i, p; (p = par[k]) >= 0; k = p) par[k] = r;
-                }
-            }
-            std::vector<int> lab(nc), cls_of_root(nc, -1);
-            int ncls = 0;
-            for (int i = 0; i < nc; ++i) {
-                const int r = root(i);
-                if (cls_of_root[r] < 0) cls_of_root[r] = ncls++;
-                lab[i] = cls_of_root[r];
-            }
-            std::vector<long long> acc(4 * (size_t)ncls, 0);
-            std::vector<int> cnt(ncls, 0);
-            for (int i = 0; i < nc; ++i) {
-                for (int k = 0; k < 4; ++k) acc[4 * lab[i] + k] += c[4 * i + k];
-                cnt[lab[i]]++;
-            }
-            std::vector<int32_t> avg(4 * (size_t)ncls);
-            for (int l = 0; l < ncls; ++l) {
-                const float sinv = 1.f / (float)cnt[l];
-                for (int k = 0; k < 4; ++k) avg[4 * l + k] = rne_f((float)(int)acc[4 * l + k] * sinv);
-            }
-            for (int i = 0; i < ncls; ++i) {
-                const int32_t* r1 = &avg[4 * i];
-                const int n1 = cnt[i];
-                if (n1 <= min_neighbors) continue;
-                int j = 0;
-                for (; j < ncls; ++j) {
-                    const int n2 = cnt[j];
-                    if (j == i || n2 <= min_neighbors) continue;
-                    const int32_t* r2 = &avg[4 * j];
-                    const int dx = rne_d(r2[2] * eps), dy = rne_d(r2[3] * eps);
-                    if (r1[0] >= r2[0] - dx && r1[1] >= r2[1] - dy && r1[0] + r1[2] <= r2[0] + r2[2] + dx &&
-                        r1[1] + r1[3] <= r2[1] + r2[3] + dy && (n2 > std::max(3, n1) || n1 < 3))
-                        break;
-                }
-                if (j == ncls) outr.insert(outr.end(), r1, r1 + 4);
-            }
-        }
         h->out[img] = std::move(outr);
     };
     // (64 1080p ROI frames of frontalface: 12.1 ms per call single-threaded beside 3.1 ms of kernels, when
@@ -1258,5 +1282,659 @@ int fm_haar_collect(fm_haar* h, int32_t* rects, int cap, int32_t* counts, int n)
     detect_copy(h, rects, cap, counts);
     return FM_OK;
 }
+
+}  // extern "C"
+
+// ---- The cascade bank: several cascades over one frame in one launch chain --------------------------------
+// find_objects runs every loaded cascade on the same ROI frame.  detectMultiScale's scaled image sizes depend
+// on the frame alone, so the upload, the ROI resize, gray, the pyramid and the integrals are computed once for
+// the longest scale list any member needs; each member sweeps the prefix of that list its window fits, on its
+// own window grids.  One sweep launch (k_bdetect) covers every (member, scale, tile, image), one row walk
+// (k_bwalk) every (member, scale, row, image), and one synchronisation and copy return every list.
+namespace fm {
+namespace haar {
+
+constexpr int kBankMax = 32;  // members per bank
+
+// The bank's geometry in device memory (uploaded per call through page-locked staging: by value it would be
+// kernel arguments of 3 KB per member)
+struct BankMember {
+    CascadeDev c;
+    int n;               // scales this member sweeps: a prefix of the bank's list
+    int pw_max, split;   // LDS row stride its StumpRec offsets were built for; stages before the packed tail
+    int wbase;           // its first window within one image's result grid
+    int gw[MAXSC], gh[MAXSC], woff[MAXSC], toff[MAXSC], tnx[MAXSC], roff[MAXSC];  // as Geo's, from its own window
+};
+struct BankDev {
+    int nm;          // members
+    int NW, NT, NR;  // per image totals over the members: windows, window tiles, window rows
+    int I;           // integral elements per image
+    int toff[kBankMax + 1], roff[kBankMax + 1];  // first tile / first window row of each member
+    int sw[MAXSC], sh[MAXSC], step[MAXSC], ioff[MAXSC];  // the shared pyramid
+    BankMember m[kBankMax];
+};
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+template <class P>
+__device__ __forceinline__ const P* uni_ptr(const P* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return (const P*)(((unsigned long long)hi << 32) | lo);
+}
+
+// k_hdetect's tile with its geometry as scalars: tile index `tile` of a scale whose integral image (stride st, ih
+// rows) starts at S/Q/T + base and whose window grid (gw x gh on the `step` grid, tnx tiles per tile row) starts
+// at res + wbase.  Everything but the thread id is workgroup-uniform.  (A copy of k_hdetect's body, not a
+// function both call: called from k_hdetect it changed that kernel's registers and schedule)
+__device__ __forceinline__ void sweep_tile(const uint32_t* __restrict__ S, const uint32_t* __restrict__ Q,
+                                           const uint32_t* __restrict__ T, int8_t* __restrict__ res, int split,
+                                           const CascadeDev& c, int pw_max, int tile, int tnx, int step, int st, int ih,
+                                           int gw, int gh, size_t base, long long wbase) {
+    extern __shared__ uint32_t patch[];  // S patch [ph][pw], then T patch (tilted cascades)
+    __shared__ int s_live[2][TW * TH];   // the windows (thread ids) a phase runs, double-buffered
+    __shared__ int s_n[4];               // their count, per phase
+    __shared__ float s_vnf[TW * TH];
+    const int tyi = tile / tnx, txi = tile - tyi * tnx;
+    const int gx0 = txi * TW, gy0 = tyi * TH;
+    const int px0 = gx0 * step, py0 = gy0 * step;
+    const int pw = min((TW - 1) * step + c.win_w + 1, st - px0), ph = min((TH - 1) * step + c.win_h + 1, ih - py0);
+    const int tid = threadIdx.x;
+    if (tid < 4) s_n[tid] = 0;
+    for (int i = tid; i < pw * ph; i += TW * TH) {
+        const int y = i / pw, x = i - y * pw;
+        const size_t gi = base + (size_t)(py0 + y) * st + px0 + x;
+        patch[y * pw_max + x] = S[gi];
+        if (c.has_tilted) patch[ph * pw_max + y * pw_max + x] = T[gi];
+    }
+    __syncthreads();
+    const uint32_t* PT = c.has_tilted ? patch + ph * pw_max : nullptr;
+    {
+        // HaarEvaluator::setWindow of this thread's window: sum from the patch, squared sum from Q; a window
+        // that is not flat joins the first phase's list
+        const int gx = gx0 + (tid % TW), gy = gy0 + tid / TW;
+        if (gx < gw && gy < gh) {
+            const int nr[4] = {1, 1, c.win_w - 2, c.win_h - 2};
+            const int32_t valsum = rsum(patch, pw_max, (gx - gx0) * step, (gy - gy0) * step, nr, false);
+            const uint32_t valsq = (uint32_t)rsum(Q + base, st, gx * step, gy * step, nr, false);
+            const double area = (double)((c.win_w - 2) * (c.win_h - 2));
+            double nf = area * (double)valsq - (double)valsum * (double)valsum;
+            bool ok = nf > 0.;
+            float vnf = 1.f;
+            if (ok) {
+                nf = sqrt(nf);
+                vnf = (float)(1. / nf);
+                ok = area * (double)vnf < 1e-1;
+            }
+            if (ok) {
+                s_live[0][atomicAdd(&s_n[0], 1)] = tid;
+                s_vnf[tid] = vnf;
+            } else {
+                res[wbase + (long long)gy * gw + gx] = -1;
+            }
+        }
+    }
+    __syncthreads();
+    // Phases of stages: each runs on the windows the previous one left alive, compacted into the first threads
+    // (one window each), so the lanes a wave issues for are mostly live ones: stages [0, 1), [1, 2), [2, split)
+    // and [split, n_stages) with FM_HAAR_HEADC, else [0, split) and [split, n_stages).  Each window's stages,
+    // stumps and sums are the same in any phase split (only which thread runs them changes).
+    int bnd[4], nb = 0;  // end stage of each phase (workgroup-uniform)
+    if (FM_HAAR_HEADC) {
+        bnd[nb++] = 1;
+        if (split > 1) bnd[nb++] = min(2, split);
+        if (split > 2) bnd[nb++] = split;
+    } else {
+        bnd[nb++] = split;
+    }
+    if (split < c.n_stages) bnd[nb++] = c.n_stages;
+    int sb = 0;
+    for (int p = 0; p < nb; ++p) {
+        const int e = bnd[p], n = s_n[p];
+        const bool last = e >= c.n_stages;
+        // the last phase's windows packed into the first waves (FM_HAAR_TAIL_SPREAD: window k -> wave k % 4,
+        // a few deep windows in parallel on the four SIMDs)
+        constexpr int NWV = TW * TH / 64;
+        const int k = (last && FM_HAAR_TAIL_SPREAD) ? (tid & 63) * NWV + (tid >> 6) : tid;
+        if (k < n) {
+            const int t2 = s_live[p & 1][k];
+            const int gx2 = gx0 + (t2 % TW), gy2 = gy0 + t2 / TW;
+            Win v;
+            v.st = pw_max;
+            v.x = (gx2 - gx0) * step;
+            v.y = (gy2 - gy0) * step;
+            v.S = patch;
+            v.T = PT;
+            v.vnf = s_vnf[t2];
+            const long long wi2 = wbase + (long long)gy2 * gw + gx2;
+            const int f = (FM_HAAR_REC && c.recs) ? run_stages_rec(c, patch + v.y * pw_max + v.x,
+                                                                   PT ? PT + v.y * pw_max + v.x : nullptr, v.vnf, sb, e)
+                                                  : run_stages(c, v, sb, e);
+            if (f >= 0) res[wi2] = f == 0 ? 0 : -1;  // 0: rejected by stage 0 (the row walk's skip)
+            else if (!last) s_live[(p + 1) & 1][atomicAdd(&s_n[p + 1], 1)] = t2;
+            else res[wi2] = 1;
+        }
+        if (p + 1 < nb) __syncthreads();  // (uniform: nb and bnd depend on split and the cascade only)
+        sb = e;
+    }
+}
+
+// The bank's sweep: workgroup blockIdx.x is one window tile of one scale of one member, blockIdx.y the image.
+// Member and scale come from two scalar searches over the tile offsets; from there the tile is k_hdetect's.
+// Everything read from the table is the same in every lane: readfirstlane says so to the compiler, so that the
+// cascade's fields, the record base (run_stages_rec's buffer descriptor) and the grids stay in SGPRs.
+__global__ __launch_bounds__(TW * TH) void k_bdetect(const uint32_t* __restrict__ S, const uint32_t* __restrict__ Q,
+                                                     const uint32_t* __restrict__ T, int8_t* __restrict__ res,
+                                                     const BankDev* __restrict__ B) {
+    const int img = blockIdx.y, bx = blockIdx.x;
+    const int nm = uni(B->nm);
+    int m = 0;
+    while (m + 1 < nm && uni(B->toff[m + 1]) <= bx) ++m;
+    const BankMember& M = B->m[m];
+    const int bt = bx - uni(B->toff[m]), ns = uni(M.n);
+    int s = 0;
+    while (s + 1 < ns && uni(M.toff[s + 1]) <= bt) ++s;
+    CascadeDev c;
+    c.win_w = uni(M.c.win_w);
+    c.win_h = uni(M.c.win_h);
+    c.n_stages = uni(M.c.n_stages);
+    c.has_tilted = uni(M.c.has_tilted);
+    c.stumps = uni(M.c.stumps);
+    c.stage_first = uni_ptr(M.c.stage_first);
+    c.stage_ntrees = uni_ptr(M.c.stage_ntrees);
+    c.stage_thr = uni_ptr(M.c.stage_thr);
+    c.tree_node_ofs = uni_ptr(M.c.tree_node_ofs);
+    c.tree_leaf_ofs = uni_ptr(M.c.tree_leaf_ofs);
+    c.nodes = uni_ptr(M.c.nodes);
+    c.leaves = uni_ptr(M.c.leaves);
+    c.feats = uni_ptr(M.c.feats);
+    c.recs = uni_ptr(M.c.recs);
+    c.n_recs = uni(M.c.n_recs);
+    sweep_tile(S, Q, T, res, uni(M.split), c, uni(M.pw_max), bt - uni(M.toff[s]), uni(M.tnx[s]), uni(B->step[s]),
+               uni(B->sw[s]) + 1, uni(B->sh[s]) + 1, uni(M.gw[s]), uni(M.gh[s]),
+               (size_t)img * (size_t)uni(B->I) + (size_t)uni(B->ioff[s]),
+               (long long)img * uni(B->NW) + uni(M.wbase) + uni(M.woff[s]));
+}
+
+// k_hwalk over every (member, scale, row, image): list (member, image) holds the accepted windows' indices in
+// the member's own window grid, cnt[member * nimg + image] their number
+__global__ __launch_bounds__(64) void k_bwalk(const int8_t* __restrict__ res, int* __restrict__ cnt,
+                                              int* __restrict__ cand, const BankDev* __restrict__ B, int nimg) {
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    const int NR = B->NR;
+    if (i >= (long long)nimg * NR) return;
+    const int img = (int)(i / NR), r = (int)(i - (long long)img * NR);
+    const int m = find_scale(B->roff, B->nm, r);
+    const BankMember& M = B->m[m];
+    const int rr = r - B->roff[m];
+    const int s = find_scale(M.roff, M.n, rr);
+    const int gy = rr - M.roff[s], gw = M.gw[s];
+    const int base = M.woff[s] + gy * gw;
+    const int8_t* R = res + (size_t)img * B->NW + M.wbase + base;
+    const size_t list = (size_t)m * nimg + img;
+    for (int gx = 0; gx < gw;) {
+        const int8_t v = R[gx];
+        if (v > 0) {
+            const int k = atomicAdd(&cnt[list], 1);
+            if (k < kCandCap) cand[list * kCandCap + k] = base + gx;
+        }
+        gx += v == 0 ? 2 : 1;
+    }
+}
+
+}  // namespace haar
+}  // namespace fm
+
+struct fm_haar_bank {
+    struct Member {
+        int win_w = 0, win_h = 0, n_stages = 0, has_tilted = 0;
+        int pw_max = 0;
+        fm::DevBuf<uint8_t> d_blob;
+        CascadeDev cd{};
+        // the last detection: this member's window grids, candidates of image 0, grouped rects per image
+        Geo g{};
+        int wbase = 0;
+        std::vector<int32_t> cand;
+        std::vector<std::vector<int32_t>> out;
+    };
+    int device = 0;
+    fm::Stream stream;  // (before the buffers used on it: they are released first)
+    std::string err;
+    std::vector<Member> mem;
+    int any_tilted = 0;
+    size_t lds = 0;  // the largest member patch: k_bdetect's dynamic LDS
+    fm::DevBuf<uint8_t> d_src, d_gray, d_rimg;
+    fm::DevBuf<uint32_t> d_S, d_Q, d_T;
+    fm::DevBuf<int8_t> d_res;
+    fm::DevBuf<int2> d_taps;
+    fm::DevBuf<BankDev> d_tab;  // the geometry table and its page-locked staging copy
+    fm::PinBuf<BankDev> h_tab;
+    fm::RoiStage roi{true};
+    std::vector<int8_t> h_res;
+    fm::DevBuf<int> d_ccnt, d_cand;  // k_bwalk: [member][image] counts and lists
+    fm::PinBuf<int> h_ccnt, h_cand;
+    double last_ms = 0.;
+    fm::Event e0, e1;
+    bool pending = false;
+    int pend_n = 0, pend_min_neighbors = 0;
+    long long pend_NW = 0;  // windows per image over all members (0: nothing was launched)
+    std::vector<float> pend_sc;
+
+    ~fm_haar_bank() {
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
+};
+
+// the tiled sweep's LDS patch of a window (k_hdetect's and k_bdetect's dynamic LDS)
+static size_t patch_lds(int win_w, int win_h, int tilted) {
+    const int pw_max = (TW - 1) * 2 + win_w + 1, ph_max = (TH - 1) * 2 + win_h + 1;
+    return (size_t)pw_max * ph_max * 4 * (tilted ? 2 : 1);
+}
+constexpr size_t kPatchLdsMax = 56 * 1024;
+
+extern "C" {
+
+int fm_haar_bank_create(int device, const fm_haar_desc* descs, int n_members, fm_haar_bank** out) {
+    if (!out) return FM_EINVAL;
+    *out = nullptr;
+    auto* b = new fm_haar_bank();
+    *out = b;
+    if (!descs || n_members < 1 || n_members > kBankMax)
+        return fm::failf(&b->err, FM_EINVAL, "a bank holds 1..%d cascades, not %d", kBankMax, n_members);
+    std::vector<int> tilted(n_members, 0);
+    for (int m = 0; m < n_members; ++m) {  // every member is checked before the first HIP call
+        std::string e;
+        if (int rc = check_desc(&descs[m], &e, &tilted[m])) return fm::failf(&b->err, rc, "member %d: %s", m, e.c_str());
+    }
+    for (int m = 0; m < n_members; ++m) {
+        const size_t lds = patch_lds(descs[m].win_w, descs[m].win_h, tilted[m]);
+        if (lds > kPatchLdsMax)
+            return fm::failf(&b->err, FM_ENOTSUP, "member %d: the %dx%d%s window's LDS patch (%zu bytes) does not fit the "
+                             "tiled sweep (%zu): keep a separate detector for it", m, descs[m].win_w, descs[m].win_h,
+                             tilted[m] ? " tilted" : "", lds, kPatchLdsMax);
+        b->lds = std::max(b->lds, lds);
+        b->any_tilted |= tilted[m];
+    }
+    b->device = device;
+    FM_HIP_TRY(&b->err, hipSetDevice(device));
+    {
+        int lo = 0, hi = 0;  // (the single detector's stream priority)
+        FM_HIP_TRY(&b->err, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        FM_HIP_TRY(&b->err, hipStreamCreateWithPriority(b->stream.put(), hipStreamNonBlocking, hi));
+    }
+    FM_HIP_TRY(&b->err, hipEventCreate(b->e0.put()));
+    FM_HIP_TRY(&b->err, hipEventCreate(b->e1.put()));
+    FM_HIP_TRY(&b->err, fm::reserve_all(1, 1, b->d_tab, b->h_tab));
+    std::vector<fm_haar_bank::Member> mem(n_members);
+    for (int m = 0; m < n_members; ++m) {
+        fm_haar_bank::Member& M = mem[m];
+        M.win_w = descs[m].win_w;
+        M.win_h = descs[m].win_h;
+        M.n_stages = descs[m].n_stages;
+        M.has_tilted = tilted[m];
+        M.pw_max = (TW - 1) * 2 + M.win_w + 1;
+        if (int rc = upload_cascade(&descs[m], tilted[m], M.d_blob, &M.cd, &b->err)) return rc;
+    }
+    b->mem = std::move(mem);  // (a bank without members is one that failed to build)
+    return FM_OK;
+}
+
+void fm_haar_bank_destroy(fm_haar_bank* b) { delete b; }
+
+const char* fm_haar_bank_last_error(const fm_haar_bank* b) { return b ? b->err.c_str() : "null bank"; }
+
+int fm_haar_bank_size(const fm_haar_bank* b) { return b ? (int)b->mem.size() : 0; }
+
+}  // extern "C"
+
+// fm_haar's detect_enqueue_impl for a bank: one pyramid for the longest scale list, each member's window
+// geometry from its own window, everything queued on the bank's stream
+static int bank_enqueue_impl(fm_haar_bank* b, const uint8_t* images, int n, int H, int W, int channels, int on_device,
+                             double scale_factor, int min_neighbors) {
+    if (!b || b->mem.empty()) return FM_EINVAL;
+    if (!images || n < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3) || !(scale_factor > 1.0))
+        return fm::failf(&b->err, FM_EINVAL, "bad arguments (n >= 1, 1 or 3 channels, scale_factor > 1)");
+    if (b->pending) return fm::failf(&b->err, FM_ESTATE, "a detection is already queued: collect it first");
+    FM_HIP_TRY(&b->err, hipSetDevice(b->device));
+    const int nm = (int)b->mem.size();
+    for (auto& M : b->mem) {
+        M.out.assign(n, {});
+        M.cand.clear();
+        M.g = Geo{};
+        M.wbase = 0;
+    }
+    b->pend_n = n;
+    b->pend_min_neighbors = min_neighbors;
+    b->pend_sc.clear();
+    b->pend_NW = 0;
+    b->pending = true;  // (a detection with no window finishes with empty results)
+    // The scale list (detectMultiScaleNoGrouping), continued until no member's window fits; member m sweeps
+    // its first ns[m] scales, the ones fm_haar would build for its window
+    std::vector<float> sc;
+    std::vector<int> ns(nm, 0);
+    for (double f = 1;; f *= scale_factor) {
+        bool any = false;
+        for (int m = 0; m < nm; ++m) {
+            const auto& M = b->mem[m];
+            if (ns[m] == (int)sc.size() && rne_d(M.win_w * f) <= W && rne_d(M.win_h * f) <= H) {
+                ns[m]++;
+                any = true;
+            }
+        }
+        if (!any) break;
+        sc.push_back((float)f);
+        if ((int)sc.size() > 4096) break;
+    }
+    int nsc = 0;
+    for (int m = 0; m < nm; ++m) {
+        const auto& M = b->mem[m];
+        for (int k = 0; k < ns[m]; ++k)  // (the default maximum size, the image's)
+            if (rne_f((float)M.win_w * sc[k]) > W || rne_f((float)M.win_h * sc[k]) > H) {
+                ns[m] = k;
+                break;
+            }
+        nsc = std::max(nsc, ns[m]);
+    }
+    sc.resize(nsc);
+    if (sc.empty()) return FM_OK;
+    if (nsc > MAXSC) return fm::failf(&b->err, FM_ENOTSUP, "%d scales (max %d)", nsc, MAXSC);
+    Geo g{};  // the shared pyramid: sizes, steps, image / integral / tap offsets
+    g.n = nsc;
+    std::vector<int2> taps;
+    for (int s = 0; s < g.n; ++s) {
+        g.sw[s] = rne_f((float)W / sc[s]);
+        g.sh[s] = rne_f((float)H / sc[s]);
+        g.step[s] = sc[s] >= 2.f ? 1 : 2;
+        g.poff[s] = g.P;
+        g.ioff[s] = g.I;
+        g.P += g.sw[s] * g.sh[s];
+        g.I += (g.sw[s] + 1) * (g.sh[s] + 1);
+        g.xtab[s] = (int)taps.size();
+        linear_exact_taps(W, g.sw[s], taps);
+        g.ytab[s] = (int)taps.size();
+        linear_exact_taps(H, g.sh[s], taps);
+    }
+    BankDev& D = *b->h_tab.get();
+    D.nm = nm;
+    D.I = g.I;
+    std::memcpy(D.sw, g.sw, sizeof D.sw);
+    std::memcpy(D.sh, g.sh, sizeof D.sh);
+    std::memcpy(D.step, g.step, sizeof D.step);
+    std::memcpy(D.ioff, g.ioff, sizeof D.ioff);
+    long long NW = 0, NT = 0, NR = 0;
+    int nsc_tilted = 0;  // T is needed for the scales the tilted members sweep
+    for (int m = 0; m < nm; ++m) {
+        auto& M = b->mem[m];
+        Geo& q = M.g;  // this member's window grids, as detect_enqueue_impl computes them from its window
+        q = g;
+        q.n = ns[m];
+        int ww0 = 0;
+        for (int s = 0; s < q.n; ++s) {
+            const int ww = std::max(q.sw[s] + 1 - M.win_w, 0);
+            if (s == 0) ww0 = ww;
+            q.gw[s] = (ww + q.step[s] - 1) / q.step[s];
+        }
+        const int nstripes = (ww0 + 31) / 32;
+        for (int s = 0; s < q.n; ++s) {
+            const int wh = std::max(q.sh[s] + 1 - M.win_h, 0);
+            const int stripe = nstripes ? std::max((wh / q.step[s] + nstripes - 1) / nstripes, 1) * q.step[s] : 0;
+            const int ylim = std::min(nstripes * stripe, wh);
+            q.gh[s] = (ylim + q.step[s] - 1) / q.step[s];
+            if (q.gw[s] == 0) q.gh[s] = 0;
+        }
+        q.NW = q.NT = q.NR = 0;
+        for (int s = 0; s < q.n; ++s) {
+            q.roff[s] = q.NR;
+            q.NR += q.gw[s] > 0 ? q.gh[s] : 0;
+            q.woff[s] = q.NW;
+            q.toff[s] = q.NT;
+            q.tnx[s] = (q.gw[s] + TW - 1) / TW;
+            q.NT += q.tnx[s] * ((q.gh[s] + TH - 1) / TH);
+            q.NW += q.gw[s] * q.gh[s];
+        }
+        if (NW + q.NW > 0x7fffffffLL || NT + q.NT > 0x7fffffffLL)
+            return fm::failf(&b->err, FM_ENOTSUP, "the bank's window grids exceed 2^31 windows per image");
+        M.wbase = (int)NW;
+        BankMember& dm = D.m[m];
+        dm.c = M.cd;
+        dm.n = q.n;
+        dm.pw_max = M.pw_max;
+        dm.split = std::max(1, std::min(4, M.n_stages));
+        dm.wbase = M.wbase;
+        std::memcpy(dm.gw, q.gw, sizeof dm.gw);
+        std::memcpy(dm.gh, q.gh, sizeof dm.gh);
+        std::memcpy(dm.woff, q.woff, sizeof dm.woff);
+        std::memcpy(dm.toff, q.toff, sizeof dm.toff);
+        std::memcpy(dm.tnx, q.tnx, sizeof dm.tnx);
+        std::memcpy(dm.roff, q.roff, sizeof dm.roff);
+        D.toff[m] = (int)NT;
+        D.roff[m] = (int)NR;
+        NW += q.NW;
+        NT += q.NT;
+        NR += q.NR;
+        if (M.has_tilted) nsc_tilted = std::max(nsc_tilted, q.n);
+    }
+    D.toff[nm] = (int)NT;
+    D.roff[nm] = (int)NR;
+    D.NW = (int)NW;
+    D.NT = (int)NT;
+    D.NR = (int)NR;
+    const size_t npx = (size_t)n * H * W;
+    FM_HIP_TRY(&b->err, b->d_gray.reserve(npx));
+    FM_HIP_TRY(&b->err, b->d_rimg.reserve((size_t)n * g.P));
+    FM_HIP_TRY(&b->err, b->d_taps.reserve(taps.size()));
+    FM_HIP_TRY(&b->err, b->d_res.reserve((size_t)n * NW));
+    FM_HIP_TRY(&b->err, b->d_S.reserve((size_t)n * g.I));
+    FM_HIP_TRY(&b->err, b->d_Q.reserve((size_t)n * g.I));
+    if (nsc_tilted) FM_HIP_TRY(&b->err, b->d_T.reserve((size_t)n * g.I));
+    const uint8_t* src = images;
+    if (!on_device) {
+        FM_HIP_TRY(&b->err, b->d_src.reserve(npx * channels));
+        FM_HIP_TRY(&b->err, hipMemcpyAsync(b->d_src, images, npx * channels, hipMemcpyHostToDevice, b->stream));
+        src = b->d_src;
+    }
+    FM_HIP_TRY(&b->err, hipMemcpyAsync(b->d_taps, taps.data(), taps.size() * sizeof(int2), hipMemcpyHostToDevice, b->stream));
+    // (only the members in use travel: the header and nm member records)
+    FM_HIP_TRY(&b->err, hipMemcpyAsync(b->d_tab, b->h_tab, offsetof(BankDev, m) + (size_t)nm * sizeof(BankMember),
+                                       hipMemcpyHostToDevice, b->stream));
+    FM_HIP_TRY(&b->err, hipEventRecord(b->e0, b->stream));
+    k_hgray<<<(unsigned)((npx + 255) / 256), 256, 0, b->stream>>>(src, b->d_gray, (long long)npx, channels);
+    const long long np = (long long)n * g.P;
+    k_hresize<<<(unsigned)((np + 255) / 256), 256, 0, b->stream>>>(b->d_gray, b->d_rimg, b->d_taps, g, W, H, n);
+    const int maxh = g.sh[0], maxw = g.sw[0];  // (scale 0 is the image itself)
+    k_hrows<<<dim3(maxh, g.n, n), 64, 0, b->stream>>>(b->d_rimg, b->d_S, b->d_Q, g, n, maxh);
+    k_hcols<<<dim3((maxw + 1 + 63) / 64, g.n, n), 64, 0, b->stream>>>(b->d_S, b->d_Q, g, n);
+    if (nsc_tilted)
+        k_htilt<<<dim3((unsigned)(((maxw + 1) * (maxh + 1) + 255) / 256), nsc_tilted, n), 256, 0, b->stream>>>(
+            b->d_S, b->d_T, g, n);
+    if (NT > 0)
+        hipLaunchKernelGGL(k_bdetect, dim3((unsigned)NT, (unsigned)n), dim3(TW * TH), b->lds, b->stream, b->d_S, b->d_Q,
+                           b->d_T, b->d_res, b->d_tab);
+    FM_HIP_TRY(&b->err, hipGetLastError());
+    FM_HIP_TRY(&b->err, hipEventRecord(b->e1, b->stream));
+    const size_t nl = (size_t)nm * n;
+    FM_HIP_TRY(&b->err, fm::reserve_all(nl, nl, b->d_ccnt, b->h_ccnt));
+    FM_HIP_TRY(&b->err, fm::reserve_all(nl * kCandCap, nl * kCandCap, b->d_cand, b->h_cand));
+    FM_HIP_TRY(&b->err, hipMemsetAsync(b->d_ccnt, 0, nl * sizeof(int), b->stream));
+    if (NW > 0 && NR > 0)
+        k_bwalk<<<(unsigned)(((long long)n * NR + 63) / 64), 64, 0, b->stream>>>(b->d_res, b->d_ccnt, b->d_cand, b->d_tab, n);
+    FM_HIP_TRY(&b->err, hipGetLastError());
+    FM_HIP_TRY(&b->err, hipMemcpyAsync(b->h_ccnt, b->d_ccnt, nl * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    FM_HIP_TRY(&b->err, hipMemcpyAsync(b->h_cand, b->d_cand, nl * kCandCap * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    b->pend_sc = sc;
+    b->pend_NW = NW;
+    return FM_OK;
+}
+
+static int bank_enqueue(fm_haar_bank* b, const uint8_t* images, int n, int H, int W, int channels, int on_device,
+                        double scale_factor, int min_neighbors) {
+    const int rc = bank_enqueue_impl(b, images, n, H, W, channels, on_device, scale_factor, min_neighbors);
+    if (rc != FM_OK && b && rc != FM_ESTATE) {  // (a failed call leaves nothing to collect)
+        b->pending = false;
+        for (auto& M : b->mem) M.out.clear();
+    }
+    return rc;
+}
+
+// One synchronisation and one copy of every member's counts and lists, then detect_finish's post-pass per
+// (member, image)
+static int bank_finish(fm_haar_bank* b) {
+    if (!b->pending) return FM_OK;
+    b->pending = false;
+    const int n = b->pend_n, nm = (int)b->mem.size();
+    if (b->pend_sc.empty()) return FM_OK;  // no scale for any member: no detections
+    FM_HIP_TRY(&b->err, hipStreamSynchronize(b->stream));
+    bool overflow = false;
+    long long ncand = 0;
+    for (int k = 0; k < nm * n; ++k) {
+        overflow |= b->h_ccnt[k] > kCandCap;
+        ncand += b->h_ccnt[k];
+    }
+    const long long NW = b->pend_NW;
+    if (overflow) {  // some list is longer than it holds: walk the whole grid here
+        b->h_res.resize((size_t)(n * NW));
+        FM_HIP_TRY(&b->err, hipMemcpy(b->h_res.data(), b->d_res, (size_t)(n * NW), hipMemcpyDeviceToHost));
+        ncand = n * NW;
+    }
+    float ms = 0.f;
+    FM_HIP_TRY(&b->err, hipEventElapsedTime(&ms, b->e0, b->e1));
+    b->last_ms = ms;
+    auto post = [&](int k) {  // pair k = member * n + image
+        const int m = k / n, img = k - m * n;
+        auto& M = b->mem[m];
+        std::vector<int32_t> c, outr;
+        post_pass(b->pend_sc, M.g, M.win_w, M.win_h, b->pend_min_neighbors, b->h_cand + (size_t)k * kCandCap,
+                  overflow ? 0 : b->h_ccnt[k], overflow ? b->h_res.data() + (size_t)img * NW + M.wbase : nullptr, c, outr);
+        if (img == 0) M.cand = std::move(c);
+        M.out[img] = std::move(outr);
+    };
+    const int np = nm * n;
+    const int nth = ncand < 4096 ? 1 : std::min(np, std::max(1, std::min(kPostThreads, (int)std::thread::hardware_concurrency())));
+    if (nth <= 1) {
+        for (int k = 0; k < np; ++k) post(k);
+    } else {
+        std::atomic<int> next{0};
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nth; ++t)
+            pool.emplace_back([&] {
+                for (int k; (k = next.fetch_add(1, std::memory_order_relaxed)) < np;) post(k);
+            });
+        for (auto& t : pool) t.join();
+    }
+    return FM_OK;
+}
+
+// the last detection's results: counts[member][image] (all of them), up to cap rects in rects[member][image]
+static void bank_copy(const fm_haar_bank* b, int n, int32_t* rects, int cap, int32_t* counts) {
+    for (int m = 0; m < (int)b->mem.size(); ++m)
+        for (int img = 0; img < n; ++img) {
+            const auto& o = b->mem[m].out[img];
+            const int no = (int)o.size() / 4, keep = std::min(no, cap);
+            counts[(size_t)m * n + img] = no;
+            if (keep > 0) std::memcpy(rects + ((size_t)m * n + img) * cap * 4, o.data(), sizeof(int32_t) * 4 * keep);
+        }
+}
+
+static bool bank_bad_out(fm_haar_bank* b, const int32_t* rects, int cap, const int32_t* counts) {
+    if (cap >= 0 && counts && (cap == 0 || rects)) return false;
+    fm::failf(&b->err, FM_EINVAL, "bad arguments (counts[members][n], rects[members][n][cap])");
+    return true;
+}
+
+static int bank_detect(fm_haar_bank* b, const uint8_t* images, int n, int H, int W, int channels, int on_device,
+                       double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts) {
+    if (int rc = bank_finish(b)) return rc;  // (a queued detection the caller never collected)
+    if (int rc = bank_enqueue(b, images, n, H, W, channels, on_device, scale_factor, min_neighbors)) return rc;
+    if (int rc = bank_finish(b)) return rc;
+    bank_copy(b, n, rects, cap, counts);
+    return FM_OK;
+}
+
+// fm_haar's detect_frames_impl for a bank: one ROI resize, then the bank's detection
+static int bank_frames_impl(fm_haar_bank* b, const uint8_t* frames, const uint8_t* const* list, int n, int H, int W,
+                            int on_device, int roi_w, double scale_factor, int min_neighbors, int32_t* rects, int cap,
+                            int32_t* counts, int* roi_h_out, bool async) {
+    if (!b || b->mem.empty()) return FM_EINVAL;
+    if (!async && bank_bad_out(b, rects, cap, counts)) return FM_EINVAL;
+    if (b->pending) {
+        if (async) return fm::failf(&b->err, FM_ESTATE, "a detection is already queued: collect it first");
+        if (int rc = bank_finish(b)) return rc;  // (queued and never collected)
+    }
+    if ((!frames && !list) || n < 1 || H < 1 || W < 1 || roi_w < 1)
+        return fm::failf(&b->err, FM_EINVAL, "bad arguments (n >= 1, frame and ROI sizes >= 1)");
+    FM_HIP_TRY(&b->err, hipSetDevice(b->device));
+    const uint8_t* roi = nullptr;
+    int rh = 0;
+    const int rc = b->roi.run(&b->err, b->stream, frames, list, n, H, W, on_device != 0, roi_w, &roi, &rh);
+    if (roi_h_out) *roi_h_out = rh;
+    if (rc) return rc;
+    if (async) return bank_enqueue(b, roi, n, rh, roi_w, 3, 1, scale_factor, min_neighbors);
+    return bank_detect(b, roi, n, rh, roi_w, 3, 1, scale_factor, min_neighbors, rects, cap, counts);
+}
+
+static int bank_check_list(fm_haar_bank* b, const uint8_t* const* frames, int n) {
+    if (!b) return FM_EINVAL;
+    if (!frames) return fm::failf(&b->err, FM_EINVAL, "null frame list");
+    for (int i = 0; i < n; i++)
+        if (!frames[i]) return fm::failf(&b->err, FM_EINVAL, "frame %d: null address", i);
+    return FM_OK;
+}
+
+extern "C" {
+
+int fm_haar_bank_detect(fm_haar_bank* b, const uint8_t* images, int n, int H, int W, int channels, int on_device,
+                        double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts) {
+    if (!b || b->mem.empty()) return FM_EINVAL;
+    if (bank_bad_out(b, rects, cap, counts)) return FM_EINVAL;
+    return bank_detect(b, images, n, H, W, channels, on_device, scale_factor, min_neighbors, rects, cap, counts);
+}
+
+int fm_haar_bank_set_roi_upscale(fm_haar_bank* b, int on) {
+    if (!b) return FM_EINVAL;
+    b->roi.allow_upscale(on != 0);
+    return FM_OK;
+}
+
+int fm_haar_bank_detect_frames(fm_haar_bank* b, const uint8_t* frames, int n, int H, int W, int on_device, int roi_w,
+                               double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts,
+                               int* roi_h_out) {
+    return bank_frames_impl(b, frames, nullptr, n, H, W, on_device, roi_w, scale_factor, min_neighbors, rects, cap,
+                            counts, roi_h_out, false);
+}
+
+int fm_haar_bank_detect_frame_list(fm_haar_bank* b, const uint8_t* const* frames, int n, int H, int W, int roi_w,
+                                   double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts,
+                                   int* roi_h_out) {
+    if (int rc = bank_check_list(b, frames, n)) return rc;
+    return bank_frames_impl(b, nullptr, frames, n, H, W, 1, roi_w, scale_factor, min_neighbors, rects, cap, counts,
+                            roi_h_out, false);
+}
+
+int fm_haar_bank_detect_frame_list_async(fm_haar_bank* b, const uint8_t* const* frames, int n, int H, int W, int roi_w,
+                                         double scale_factor, int min_neighbors, int* roi_h_out) {
+    if (int rc = bank_check_list(b, frames, n)) return rc;
+    return bank_frames_impl(b, nullptr, frames, n, H, W, 1, roi_w, scale_factor, min_neighbors, nullptr, 0, nullptr,
+                            roi_h_out, true);
+}
+
+int fm_haar_bank_collect(fm_haar_bank* b, int32_t* rects, int cap, int32_t* counts, int n) {
+    if (!b || b->mem.empty()) return FM_EINVAL;
+    if (bank_bad_out(b, rects, cap, counts)) return FM_EINVAL;
+    if (int rc = bank_finish(b)) return rc;
+    if (n != (int)b->mem[0].out.size())
+        return fm::failf(&b->err, FM_ESTATE, "%d images asked for, the last detection had %zu", n, b->mem[0].out.size());
+    bank_copy(b, n, rects, cap, counts);
+    return FM_OK;
+}
+
+int fm_haar_bank_candidates(const fm_haar_bank* b, int member, int32_t* rects, int cap) {
+    if (!b || member < 0 || member >= (int)b->mem.size() || cap < 0 || (cap > 0 && !rects)) return FM_EINVAL;
+    const auto& c = b->mem[member].cand;
+    const int nc = (int)c.size() / 4, k = std::min(nc, cap);
+    if (k > 0) std::memcpy(rects, c.data(), sizeof(int32_t) * 4 * k);
+    return nc;
+}
+
+double fm_haar_bank_last_ms(const fm_haar_bank* b) { return b ? b->last_ms : 0.; }
 
 }  // extern "C"

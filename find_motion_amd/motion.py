@@ -75,7 +75,7 @@ from collections import deque
 import numpy as np
 
 from . import videoio
-from ._native import (PLANE_BLUR, PLANE_DELTA, PLANE_GRAY, RESIZE_NAMES, CascadeClassifier, FMError, MJpegDecoder, MotionEngine,
+from ._native import (PLANE_BLUR, PLANE_DELTA, PLANE_GRAY, RESIZE_NAMES, FM_ENOTSUP, CascadeBank, CascadeClassifier, FMError, MJpegDecoder, MotionEngine,
                       YoloDetector, rasterize_masks)
 from .feeder import BatchFeeder
 
@@ -87,6 +87,10 @@ GREEN = (0, 255, 0)
 
 # fm.py:104-122
 _CASCADES: dict = {}  # (path, device) -> CascadeClassifier
+_CASCADE_BANKS: dict = {}  # (tuple of _CASCADES keys' paths, device) -> CascadeBank
+# find_objects with two or more cascades: one CascadeBank call instead of a call per cascade.  Decided by
+# tools/bench_haar_bank.py's rule on one 1080p host frame with 2 and with 9 cascades (profiles/haar_bank_bench.log).
+FIND_OBJECTS_USES_BANK = True
 _YOLOS: dict = {}  # (cfg path, weights path, names path, device, precision) -> YoloDetector
 
 CASCADE_LOOKUP = {
@@ -324,6 +328,8 @@ class VideoMotion:
         (find_motion_amd.CascadeClassifier).  Files are looked up in `cascade_dir`, $FM_HAARCASCADES,
         the installed reference package's haarcascades/ (FIND_MOTION_PATH), then cv2.data."""
         self.cascades = dict()
+        self.cascade_bank = None  # every loaded cascade in one CascadeBank, when there are two or more
+        paths = []
         if self.cascade_names is None:
             return
         names = copy.copy(CASCADE_LOOKUP) if "ALL" in self.cascade_names else {
@@ -345,6 +351,19 @@ class VideoMotion:
             if key not in _CASCADES:  # one device copy per file and device, shared by every stream
                 _CASCADES[key] = _roi_upscale(CascadeClassifier(path, device=self.device))
             self.cascades[title] = _CASCADES[key]
+            paths.append(key[0])
+        if FIND_OBJECTS_USES_BANK and len(paths) >= 2:
+            key = (tuple(paths), self.device)
+            if key not in _CASCADE_BANKS:
+                try:
+                    _CASCADE_BANKS[key] = CascadeBank([c.cascade for c in self.cascades.values()], device=self.device,
+                                                      roi_upscale=True)
+                except FMError as e:
+                    if e.code != FM_ENOTSUP:
+                        raise
+                    self.log.warning("no cascade bank (%s): find_objects runs the cascades one by one", e)
+                    _CASCADE_BANKS[key] = None
+            self.cascade_bank = _CASCADE_BANKS[key]
 
     def _calc_min_area(self) -> None:
         """fm.py:402-406"""
@@ -676,8 +695,13 @@ class VideoMotion:
                 src = (b.engine.frame_device_ptr(b.t, b.s), 1, H, W)
             elif src is None:
                 src = frame.raw[None]
-            for title, cascade in self.cascades.items():
-                found = cascade.detect_frames(src, width, scaleFactor, minNeighbours)[0]
+            if self.cascade_bank is not None:  # one pass over the frame for all cascades, members in self.cascades' order
+                per_member = self.cascade_bank.detect_frames(src, width, scaleFactor, minNeighbours)
+                found_by_title = {title: per_member[m][0] for m, title in enumerate(self.cascades)}
+            else:
+                found_by_title = {title: cascade.detect_frames(src, width, scaleFactor, minNeighbours)[0]
+                                  for title, cascade in self.cascades.items()}
+            for title, found in found_by_title.items():
                 for rect in found:
                     self.last_objects.setdefault(title, []).append(VideoMotion.make_area_from_rect(tuple(int(v) for v in rect)))
             if self.yolo is not None:

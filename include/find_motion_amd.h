@@ -356,6 +356,44 @@ double fm_haar_last_ms(const fm_haar* det);
  * patches do not fit in LDS take (large or large tilted windows). */
 int fm_haar_last_sweep(const fm_haar* det);
 
+/* ---- A bank of cascades: every cascade find_objects loaded, over one frame in one pass ----
+ * 1..32 cascades (members) on one device.  A call uploads and resizes the frames once, builds one
+ * pyramid and one set of integral images for the longest scale list any member needs, and sweeps
+ * every member's windows in one launch; each member's results are those of an fm_haar built from the
+ * same description.  Min and max object sizes are the defaults (none, the image).
+ * Create: every member is validated as fm_haar_create validates it, before any HIP call (FM_EINVAL,
+ * the message names the member; also for n_members outside 1..32); FM_ENOTSUP for a member whose
+ * window does not fit the tiled sweep's LDS patches (the ones fm_haar_last_sweep reports as 2): keep
+ * a separate fm_haar for it.  *out is set even on failure, for fm_haar_bank_last_error. */
+typedef struct fm_haar_bank fm_haar_bank;
+int fm_haar_bank_create(int device, const fm_haar_desc* descs, int n_members, fm_haar_bank** out);
+void fm_haar_bank_destroy(fm_haar_bank* bank);
+const char* fm_haar_bank_last_error(const fm_haar_bank* bank);
+int fm_haar_bank_size(const fm_haar_bank* bank); /* members; 0 for a bank that failed to build */
+/* fm_haar_detect for every member: rects[member][image][cap][4], counts[member][image] (may exceed
+ * cap; only cap are written). */
+int fm_haar_bank_detect(fm_haar_bank* bank, const uint8_t* images, int n, int H, int W, int channels, int on_device,
+                        double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts);
+/* fm_haar_detect_frames, _frame_list, _frame_list_async, fm_haar_collect and fm_haar_set_roi_upscale
+ * for a bank: one INTER_AREA resize to roi_w, results laid out as fm_haar_bank_detect's.  One
+ * detection in flight per bank (FM_ESTATE otherwise, and for a collect with another n); a queue that
+ * failed leaves nothing to collect. */
+int fm_haar_bank_set_roi_upscale(fm_haar_bank* bank, int on);
+int fm_haar_bank_detect_frames(fm_haar_bank* bank, const uint8_t* frames, int n, int H, int W, int on_device,
+                               int roi_w, double scale_factor, int min_neighbors, int32_t* rects, int cap,
+                               int32_t* counts, int* roi_h_out);
+int fm_haar_bank_detect_frame_list(fm_haar_bank* bank, const uint8_t* const* frames, int n, int H, int W, int roi_w,
+                                   double scale_factor, int min_neighbors, int32_t* rects, int cap, int32_t* counts,
+                                   int* roi_h_out);
+int fm_haar_bank_detect_frame_list_async(fm_haar_bank* bank, const uint8_t* const* frames, int n, int H, int W,
+                                         int roi_w, double scale_factor, int min_neighbors, int* roi_h_out);
+int fm_haar_bank_collect(fm_haar_bank* bank, int32_t* rects, int cap, int32_t* counts, int n);
+/* The ungrouped candidates of image 0 of the last detection, for one member (parity tests); returns
+ * their number. */
+int fm_haar_bank_candidates(const fm_haar_bank* bank, int member, int32_t* rects, int cap);
+/* Device time of the last detection's kernels, gray to sweep (HIP events), ms. */
+double fm_haar_bank_last_ms(const fm_haar_bank* bank);
+
 /* ---- Decode side: MJPEG frames decoded on the GPU ------
  * Stands in for cv2.VideoCapture.read (find_motion.py:413, :497-506) on MJPEG
  * video, where every frame is one baseline JPEG, when the caller opts in (or
