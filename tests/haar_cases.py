@@ -29,7 +29,10 @@ def _rand_rect(rng, W, H, tilted):
         return [x, y, w, h]
 
 
-def make_cascade(seed=0, win=(20, 20), stages=4, trees=5, depth=1, tilted=False, tight=0.35) -> Cascade:
+def make_cascade(seed=0, win=(20, 20), stages=4, trees=5, depth=1, tilted=False, tight=0.35,
+                 frac=False) -> Cascade:
+    """frac: rect weights uniform in +-[0.3, 3] as float32 (non-dyadic: every product w * sum rounds) instead
+    of weights from {-2, -1, 2, 3}; either way half of the features have three rects."""
     rng = np.random.default_rng(seed)
     W, H = win
     rects, wts, tl = [], [], []
@@ -58,7 +61,10 @@ def make_cascade(seed=0, win=(20, 20), stages=4, trees=5, depth=1, tilted=False,
                 t = int(tilted and rng.random() < 0.5)
                 k = int(rng.integers(2, 4))
                 rs = [_rand_rect(rng, W, H, bool(t)) for _ in range(k)]
-                ws = [float(np.float32(rng.choice([-1.0, 2.0, 3.0, -2.0]))) for _ in range(k)]
+                if frac:
+                    ws = [float(np.float32(rng.uniform(0.3, 3.0) * rng.choice([-1.0, 1.0]))) for _ in range(k)]
+                else:
+                    ws = [float(np.float32(rng.choice([-1.0, 2.0, 3.0, -2.0]))) for _ in range(k)]
                 fids.append(add_feature(rs, ws, t))
             if nn == 1:
                 left.append(0)
