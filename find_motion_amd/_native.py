@@ -51,6 +51,7 @@ EXPORTED = (
     "fm_haar_bank_detect", "fm_haar_bank_set_roi_upscale", "fm_haar_bank_detect_frames",
     "fm_haar_bank_detect_frame_list", "fm_haar_bank_detect_frame_list_async", "fm_haar_bank_collect",
     "fm_haar_bank_candidates", "fm_haar_bank_last_ms",
+    "fm_retain_reserve", "fm_retain_frames", "fm_release_frames", "fm_read_retained", "fm_retained_count",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -242,6 +243,11 @@ def load() -> C.CDLL:
     L.fm_yolo_route_in_place.argtypes = [vp, i32]
     L.fm_yolo_last_ms.argtypes = [vp, vp]
     L.fm_yolo_last_ms.restype = C.c_double
+    L.fm_retain_reserve.argtypes = [vp, i32]
+    L.fm_retain_frames.argtypes = [vp, vp, i32, vp]
+    L.fm_release_frames.argtypes = [vp, vp, i32]
+    L.fm_read_retained.argtypes = [vp, vp, vp]
+    L.fm_retained_count.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     for name in EXPORTED:
         if name not in ("fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_last_ms", "fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
                         "fm_haar_last_ms", "fm_haar_bank_destroy", "fm_haar_bank_last_error", "fm_haar_bank_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
@@ -718,6 +724,39 @@ class MotionEngine:
         p = C.c_void_p()
         self._check(self._L.fm_frame_device(self._h, frame, stream, C.byref(p)))
         return int(p.value)
+
+    # -- retained source frames (fm_retain_*): frames kept in HBM after their batch slot is reused ----------
+    def reserve_retained(self, n: int) -> None:
+        """Size the pool of retained frames to n entries of one source frame each (0 frees it)."""
+        self._check(self._L.fm_retain_reserve(self._h, int(n)))
+
+    def retain(self, pairs) -> list:
+        """Copy the (frame, stream) source frames of the last waited batch into free pool entries, all in one
+        kernel launch, complete on return; their device addresses, in the order of `pairs`."""
+        fs = np.ascontiguousarray([tuple(p) for p in pairs], dtype=np.int32).reshape(-1, 2)
+        n = fs.shape[0]
+        out = (C.c_void_p * max(n, 1))()
+        self._check(self._L.fm_retain_frames(self._h, _ptr(fs), n, C.cast(out, C.c_void_p)))
+        return [int(out[i]) for i in range(n)]
+
+    def release(self, ptrs) -> None:
+        """Free retained frames (all of them, or, if one is not a retained frame, none: FM_EINVAL)."""
+        ptrs = [int(p) for p in ptrs]
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        self._check(self._L.fm_release_frames(self._h, C.cast(arr, C.c_void_p), len(ptrs)))
+
+    def read_retained(self, ptr: int) -> np.ndarray:
+        """A retained frame (BGR [H, W, 3]) copied to the host."""
+        out = np.empty(self.src_shape, np.uint8)
+        self._check(self._L.fm_read_retained(self._h, C.c_void_p(int(ptr)), _ptr(out)))
+        return out
+
+    @property
+    def retained(self) -> tuple:
+        """(entries in use, the pool's size)."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self._L.fm_retained_count(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def plane(self, which: int, frame: int, stream: int) -> np.ndarray:
         """gray / blur / frame_delta (h, w), or PLANE_SMALL: the resized BGR frame (h, w, 3) (fm.py:490)."""

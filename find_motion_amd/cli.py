@@ -2,7 +2,7 @@
 
     python -m find_motion_amd [files] -i DIR -o DIR -c cfg.ini -B 100 -b 20 -t 12 -a 0.1 ...
                               [--gpus N] [--device D] [--batch T] [--group] [--gpu-decode]
-                              [--gpu-encode] [--contour-points]
+                              [--gpu-encode] [--resident-cache] [--contour-points]
 
 Everything the reference's `run` does around the hot path is kept in its
 shape (INI overriding the CLI, masks from literals and a JSON file, mtime
@@ -89,6 +89,9 @@ def get_args(parser: ArgumentParser) -> None:
     parser.add_argument("--gpu-encode", action="store_true", default=None,
                         help="Encode MJPG output on the GPU (libjpeg-turbo-exact baseline JPEG, quality 95, 4:2:0) "
                              "instead of cv2.VideoWriter / the host writer")
+    parser.add_argument("--resident-cache", action="store_true", default=False,
+                        help="With --gpu-encode: keep the pre-motion cache in GPU memory and encode what each batch "
+                             "writes in one call, so no written frame goes back through the host")
     parser.add_argument("--contour-points", action="store_true", default=False,
                         help="Trace every external contour on the GPU and keep its CHAIN_APPROX_SIMPLE points "
                              "(frame.contours[i] then converts to cv2.findContours' (n, 1, 2) array)")
@@ -106,7 +109,7 @@ def process_config(config_file: str, args: Namespace) -> Namespace:
         if setting in ("mintime", "cachetime", "avg"):
             use_value = float(value)
         if setting in ("mem", "progress", "debug", "show", "ignore_progress", "ignore_drive", "yolo_tiny", "group",
-                       "gpu_decode", "gpu_encode", "contour_points"):
+                       "gpu_decode", "gpu_encode", "contour_points", "resident_cache"):
             if value not in ("True", "False"):
                 raise ValueError("{} must be True or False".format(setting))
             use_value = value == "True"
@@ -223,6 +226,7 @@ def _job_kwargs(args) -> dict:
                 yolo_tiny=args.yolo_tiny, yolo_dir=getattr(args, "yolo_dir", None),
                 yolo_precision=getattr(args, "yolo_precision", None), gpu_decode=getattr(args, "gpu_decode", None),
                 gpu_encode=getattr(args, "gpu_encode", None),
+                resident_cache=bool(getattr(args, "resident_cache", False)),
                 contour_points=bool(getattr(args, "contour_points", False)))
 
 

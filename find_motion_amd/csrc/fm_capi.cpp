@@ -165,6 +165,14 @@ struct fm_ctx {
     std::vector<int32_t> ready_counts;                    // [ready * S]
     std::vector<std::vector<fm_contour>> contours;        // per (t*S+s), sorted
 
+    // retained source frames (fm_retain_reserve): ret_used.size() entries of ret_stride bytes each, outside the slots
+    uint8_t* d_ret = nullptr;
+    size_t ret_stride = 0;          // src_frame_bytes rounded up to 256
+    std::vector<uint8_t> ret_used;  // per entry: handed out by fm_retain_frames, not yet released
+    int ret_in_use = 0;
+    RetainPair* d_rtab = nullptr;   // the copies of one fm_retain_frames call, [entries] on the device
+    RetainPair* h_rtab = nullptr;   // and their page-locked staging
+
     std::vector<uint8_t> bg_init, has_keep;
     std::string err;
     uint64_t* d_ts = nullptr;     // FM_TS: contour-pass phase stamps (profiling)
@@ -1556,6 +1564,144 @@ int fm_frame_device(fm_ctx* c, int frame, int stream, const uint8_t** out) {
     const BatchSlot& B = c->slots[c->ready_slot];
     if (!B.src) return failf(c, FM_ESTATE, "no source frames for the last waited batch");
     *out = B.src + ((size_t)frame * c->p.n_streams + stream) * c->src_frame_bytes;
+    return FM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// a device / page-locked buffer of the context leaves it and its footprint (nullptr: nothing)
+void dfree(fm_ctx* c, const void* p) {
+    auto it = c->dev_sizes.find(p);
+    if (it == c->dev_sizes.end()) return;
+    (void)hipFree(const_cast<void*>(p));
+    c->dev_bytes -= it->second;
+    c->dev_sizes.erase(it);
+}
+
+void pfree(fm_ctx* c, const void* p) {
+    auto it = c->pin_sizes.find(p);
+    if (it == c->pin_sizes.end()) return;
+    (void)hipHostFree(const_cast<void*>(p));
+    c->pinned_bytes -= it->second;
+    c->pin_sizes.erase(it);
+}
+
+// the pool entry that starts at p and is handed out, or -1
+long retained_entry(const fm_ctx* c, const uint8_t* p) {
+    if (!c->d_ret || p < c->d_ret) return -1;
+    const size_t off = (size_t)(p - c->d_ret);
+    if (off % c->ret_stride || off / c->ret_stride >= c->ret_used.size()) return -1;
+    return c->ret_used[off / c->ret_stride] ? (long)(off / c->ret_stride) : -1;
+}
+}  // namespace
+
+extern "C" {
+
+int fm_retain_reserve(fm_ctx* c, int frames) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (frames < 0) return failf(c, FM_EINVAL, "a pool of %d retained frames", frames);
+    if (c->ret_in_use)
+        return failf(c, FM_ESTATE, "%d retained frames are in use: release them before resizing the pool", c->ret_in_use);
+    if ((size_t)frames == c->ret_used.size()) return FM_OK;
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    const size_t stride = (c->src_frame_bytes + 255) & ~(size_t)255;  // hipMalloc's base is 256-byte aligned too
+    uint8_t* pool = nullptr;
+    RetainPair *dtab = nullptr, *htab = nullptr;
+    if (frames > 0) {  // the new pool first: a failure leaves the old one as it was
+        int rc = dalloc(c, &pool, stride * (size_t)frames);
+        if (!rc) rc = dalloc(c, &dtab, (size_t)frames);
+        if (!rc && halloc(c, &htab, (size_t)frames * sizeof(RetainPair), hipHostMallocDefault) != hipSuccess)
+            rc = failf(c, FM_ENOMEM, "hipHostMalloc(%zu bytes) for the retain table", (size_t)frames * sizeof(RetainPair));
+        if (rc) {
+            dfree(c, pool);
+            dfree(c, dtab);
+            return rc;
+        }
+    }
+    dfree(c, c->d_ret);
+    dfree(c, c->d_rtab);
+    pfree(c, c->h_rtab);
+    c->d_ret = pool;
+    c->d_rtab = dtab;
+    c->h_rtab = htab;
+    c->ret_stride = stride;
+    c->ret_used.assign((size_t)frames, 0);
+    return FM_OK;
+}
+
+int fm_retain_frames(fm_ctx* c, const int32_t* frame_stream, int n, const uint8_t** dev_out) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (n < 0) return failf(c, FM_EINVAL, "%d frames to retain", n);
+    if (n == 0) return FM_OK;
+    if (!frame_stream || !dev_out) return failf(c, FM_EINVAL, "null argument");
+    if (c->ready_slot < 0 || c->ready < 1) return failf(c, FM_ESTATE, "no batch has been waited for");
+    const BatchSlot& B = c->slots[c->ready_slot];
+    if (B.gen != c->ready_gen) return failf(c, FM_ESTATE, "the batch's device results were overwritten by a later submit");
+    if (!B.src) return failf(c, FM_ESTATE, "no source frames for the last waited batch");
+    const int S = c->p.n_streams;
+    for (int i = 0; i < n; i++) {
+        const int t = frame_stream[2 * i], s = frame_stream[2 * i + 1];
+        if (t < 0 || t >= c->ready || s < 0 || s >= S)
+            return failf(c, FM_EINVAL, "pair %d: (frame %d, stream %d) not in the last batch (%d frames of %d streams)", i,
+                         t, s, c->ready, S);
+    }
+    const size_t cap = c->ret_used.size();
+    if ((size_t)n > cap - (size_t)c->ret_in_use)
+        return failf(c, FM_ENOMEM, "%d frames to retain, %zu of the pool's %zu entries free (fm_retain_reserve)", n,
+                     cap - (size_t)c->ret_in_use, cap);
+    size_t e = 0;
+    for (int i = 0; i < n; i++, e++) {  // (the table is idle: the last call synchronised)
+        while (c->ret_used[e]) e++;
+        c->h_rtab[i] = {B.src + ((size_t)frame_stream[2 * i] * S + frame_stream[2 * i + 1]) * c->src_frame_bytes,
+                        c->d_ret + e * c->ret_stride};
+    }
+    hipStream_t st = c->aux_stream;
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipMemcpyAsync(c->d_rtab, c->h_rtab, (size_t)n * sizeof(RetainPair), hipMemcpyHostToDevice, st));
+    FM_HIP_TRY(c, launch_retain_frames(st, c->d_rtab, n, c->src_frame_bytes));
+    FM_HIP_TRY(c, hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        c->ret_used[(size_t)(c->h_rtab[i].dst - c->d_ret) / c->ret_stride] = 1;
+        dev_out[i] = c->h_rtab[i].dst;
+    }
+    c->ret_in_use += n;
+    return FM_OK;
+}
+
+int fm_release_frames(fm_ctx* c, const uint8_t* const* dev, int n) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (n < 0) return failf(c, FM_EINVAL, "%d frames to release", n);
+    if (n == 0) return FM_OK;
+    if (!dev) return failf(c, FM_EINVAL, "null argument");
+    std::vector<long> idx((size_t)n);
+    std::vector<uint8_t> seen(c->ret_used.size(), 0);
+    for (int i = 0; i < n; i++) {
+        idx[i] = retained_entry(c, dev[i]);
+        if (idx[i] < 0 || seen[idx[i]])
+            return failf(c, FM_EINVAL, "address %d (%p) is not a retained frame of this context, or was released", i,
+                         (const void*)dev[i]);
+        seen[idx[i]] = 1;
+    }
+    for (long k : idx) c->ret_used[k] = 0;
+    c->ret_in_use -= n;
+    return FM_OK;
+}
+
+int fm_read_retained(fm_ctx* c, const uint8_t* dev, uint8_t* host_out) {
+    if (!c || !dev || !host_out) return failf(c, FM_EINVAL, "null argument");
+    if (retained_entry(c, dev) < 0)
+        return failf(c, FM_EINVAL, "%p is not a retained frame of this context, or was released", (const void*)dev);
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipMemcpyAsync(host_out, dev, c->src_frame_bytes, hipMemcpyDeviceToHost, c->aux_stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
+    return FM_OK;
+}
+
+int fm_retained_count(const fm_ctx* c, int* in_use, int* capacity) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (in_use) *in_use = c->ret_in_use;
+    if (capacity) *capacity = (int)c->ret_used.size();
     return FM_OK;
 }
 

@@ -228,6 +228,13 @@ struct YuvArgs {
     uint64_t* kstamp;
 };
 hipError_t launch_yuv2bgr(hipStream_t st, const YuvArgs& a);
+// n copies of `bytes` bytes each in one launch (fm_kernels.hip, k_retain_frames): copy i from pairs[i].src (any
+// alignment) to pairs[i].dst (16-byte aligned); pairs is a device table of n entries
+struct RetainPair {
+    const uint8_t* src;
+    uint8_t* dst;
+};
+hipError_t launch_retain_frames(hipStream_t st, const RetainPair* pairs, int n, size_t bytes);
 struct KernelTimer;
 hipError_t launch_ccl(hipStream_t st, const CclArgs& a, KernelTimer* timer);
 hipError_t launch_fused(hipStream_t st, const FusedArgs& a, KernelTimer* timer);

@@ -915,4 +915,91 @@ hipError_t launch_ccl(hipStream_t st, const CclArgs& a, KernelTimer* tm) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Retained source frames (fm_retain_frames): n copies of `bytes` bytes each in one launch, copy i from
+// pairs[i].src to pairs[i].dst.  A destination is a pool entry and 16-byte aligned (the launcher's contract);
+// a source is wherever its frame starts in a batch slot, (t * S + s) * bytes, so of any alignment.
+// A workgroup takes one chunk (64 bytes per lane) of one frame: blockIdx.x = frame * chunks + chunk.
+//   source 16-byte aligned: four 16-byte loads per lane, then the four stores (1 KiB per wave instruction);
+//   any other source: the destination's dwords, each from the two aligned source dwords around it
+//     (v_alignbit), four per lane in flight, 256 B per wave instruction.  Every dword read holds at
+//     least one byte of the frame, so no read leaves the pages the frame lies in;
+//   the last bytes % 16 of the frame: byte by byte.
+// No atomics, no data-dependent indices, no LDS.
+constexpr int kRetainLaneBytes = 64;
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+#define FM_GLOBAL __attribute__((address_space(1)))  // global (not flat) addressing of the table's addresses
+
+struct RetainLoad16 {  // a 16-byte piece of a 16-byte aligned source
+    typedef u32x4_t T;
+    const uint8_t* s;
+    __device__ __forceinline__ T operator()(size_t o) const { return *(const FM_GLOBAL T*)(s + o); }
+};
+struct RetainLoad4 {  // a dword of a source `sh` / 8 bytes past dword alignment, from the two aligned dwords around it
+    typedef uint32_t T;
+    const uint8_t* s;
+    uint32_t sh;
+    __device__ __forceinline__ T operator()(size_t o) const {
+        const FM_GLOBAL uint32_t* q = (const FM_GLOBAL uint32_t*)((uintptr_t)(s + o) & ~(uintptr_t)3);
+        const uint32_t lo = q[0];
+        return sh ? __builtin_amdgcn_alignbit(q[1], lo, sh) : lo;  // (sh != 0: the piece's last byte lies in q[1])
+    }
+};
+
+// a lane's four pieces, `step` bytes apart from byte o of the frame on, those that begin below vend: the loads, then
+// the stores
+template <class Load>
+__device__ __forceinline__ void retain_pieces(const Load& load, uint8_t* d, size_t o, size_t step, size_t vend) {
+    typedef typename Load::T T;
+    const size_t o1 = o + step, o2 = o1 + step, o3 = o2 + step;
+    if (o3 < vend) {  // all four (every chunk of a frame but its last): nothing between the loads
+        const T w0 = load(o), w1 = load(o1), w2 = load(o2), w3 = load(o3);
+        *(FM_GLOBAL T*)(d + o) = w0;
+        *(FM_GLOBAL T*)(d + o1) = w1;
+        *(FM_GLOBAL T*)(d + o2) = w2;
+        *(FM_GLOBAL T*)(d + o3) = w3;
+        return;
+    }
+    T v0 = {}, v1 = {}, v2 = {}, v3 = {};
+    if (o < vend) v0 = load(o);
+    if (o1 < vend) v1 = load(o1);
+    if (o2 < vend) v2 = load(o2);
+    if (o3 < vend) v3 = load(o3);
+    if (o < vend) *(FM_GLOBAL T*)(d + o) = v0;
+    if (o1 < vend) *(FM_GLOBAL T*)(d + o1) = v1;
+    if (o2 < vend) *(FM_GLOBAL T*)(d + o2) = v2;
+    if (o3 < vend) *(FM_GLOBAL T*)(d + o3) = v3;
+}
+
+__global__ __launch_bounds__(256) void k_retain_frames(const RetainPair* __restrict__ pairs, size_t bytes,
+                                                        unsigned chunks) {
+    const unsigned f = blockIdx.x / chunks, ch = blockIdx.x - f * chunks;
+    const uint8_t* s = pairs[f].src;
+    uint8_t* d = pairs[f].dst;
+    const size_t chunk = (size_t)blockDim.x * kRetainLaneBytes;
+    const size_t b0 = (size_t)ch * chunk;
+    const size_t b1 = min(b0 + chunk, bytes);
+    const size_t vend = b0 + ((b1 - b0) & ~(size_t)15);  // the end of the chunk's whole 16-byte pieces
+    if (((uintptr_t)s & 15) == 0) {
+        retain_pieces(RetainLoad16{s}, d, b0 + (size_t)threadIdx.x * 16, (size_t)blockDim.x * 16, vend);
+    } else {
+        const RetainLoad4 load{s, (uint32_t)((uintptr_t)s & 3) * 8u};
+        const size_t step = (size_t)blockDim.x * 4;
+        for (size_t o = b0 + (size_t)threadIdx.x * 4; o < vend; o += 4 * step) retain_pieces(load, d, o, step, vend);
+    }
+    for (size_t o = vend + threadIdx.x; o < b1; o += blockDim.x)
+        ((FM_GLOBAL uint8_t*)d)[o] = ((const FM_GLOBAL uint8_t*)s)[o];
+}
+
+hipError_t launch_retain_frames(hipStream_t st, const RetainPair* pairs, int n, size_t bytes) {
+    if (n < 1 || bytes == 0) return hipSuccess;
+    const unsigned threads = bytes >= 16384 ? 256 : 64;  // a small frame: one wave per 4 KiB of it
+    const size_t chunk = (size_t)threads * kRetainLaneBytes;
+    const size_t chunks = (bytes + chunk - 1) / chunk;
+    if (chunks * (size_t)n > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_retain_frames, dim3((unsigned)(chunks * (size_t)n)), dim3(threads), 0, st, pairs, bytes,
+                       (unsigned)chunks);
+    return hipGetLastError();
+}
+
 }  // namespace fm

@@ -45,13 +45,18 @@ encoded to baseline JPEG on the GPU (videoio.MjpegAviWriter with an
 MJpegEncoder): a frame whose batch is still the engine's current one is
 encoded where it lies in HBM, a frame flushed from the pre-motion cache from
 its host copy; the bytes are the ones Pillow's libjpeg-turbo writes, so the
-file equals the one the host writer produces.
+file equals the one the host writer produces.  With resident_cache=True as
+well, the frames waiting in the pre-motion cache are kept in HBM past their
+batch (MotionEngine.retain), every frame a batch decides to write is queued
+on the writer by its device address, and the queue is encoded at the end of
+the batch in as few encoder calls as it takes (_end_batch): no written frame
+goes back through the host, and the file is still the same.
 
 Extra keyword arguments (not in the reference): device (HIP ordinal),
 batch (frames decoded ahead and processed per kernel launch; the per-frame
 results and the decisions are identical for any batch -- only ref_frame is
 then observed at batch boundaries), capture (a ready capture object),
-gpu_decode, gpu_encode (see above), contour_points (every frame.contours[i]
+gpu_decode, gpu_encode, resident_cache (see above), contour_points (every frame.contours[i]
 then carries its CHAIN_APPROX_SIMPLE points, traced on the GPU: np.asarray(c)
 is the (n, 1, 2) int32 array cv2.findContours returns at fm.py:269-272),
 yolo_dir (the directory of cvlib's yolov3 files, default $FM_YOLO_DIR: find_objects
@@ -163,6 +168,11 @@ class VideoFrame:
         self._vals: dict = {}
         self.processed = False
         self.index = -1  # position in the source (set when the engine processes the frame)
+        # resident_cache: where the source frame lies in HBM -- its batch slot (engine generation, t, stream), and,
+        # once its batch is over, its retained copy's address with the VideoMotion that releases it
+        self._slot = None
+        self._dev = None
+        self._owner = None
 
     @property
     def raw(self):
@@ -226,6 +236,15 @@ class VideoFrame:
         if self.in_cache:
             return
         self._raw = self._load = self.jpeg = self.yuv = None
+        self._slot = None
+        self.release_retained()
+
+    def release_retained(self) -> None:
+        """Hand the frame's retained copy (resident_cache) back: its VideoMotion releases it once the writer has
+        encoded what is queued."""
+        if self._dev is not None:
+            self._owner._free.append(self._dev)
+            self._dev = None
 
 
 class VideoMotion:
@@ -246,7 +265,8 @@ class VideoMotion:
                  device: int = 0, batch: int = 1, capture=None, engine: MotionEngine = None,
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
                  pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None,
-                 contour_points: bool = False, yolo_dir: str = None, yolo_precision: str = None) -> None:
+                 contour_points: bool = False, yolo_dir: str = None, yolo_precision: str = None,
+                 resident_cache: bool = False) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -314,6 +334,10 @@ class VideoMotion:
         self.gpu_decode = gpu_decode
         self.gpu_encode = gpu_encode
         self.contour_points = bool(contour_points)
+        self.resident_cache = bool(resident_cache)
+        self._resident = False  # resident_cache in effect (_setup_resident)
+        self._kept: typing.List[VideoFrame] = []  # frames that hold a retained copy
+        self._free: typing.List[int] = []         # retained copies to release after the writer's next flush
         self._ahead: typing.Deque[VideoFrame] = deque()
         self.frames_read = 0
         self._jpeg_dec = None  # one-frame GPU decoder for raw frames of batches already overwritten
@@ -398,12 +422,28 @@ class VideoMotion:
                                         # a box wider than the frame enlarges it, as imutils.resize does
                                         **({"area_upscale": True} if self.box_size > self.frame_width else {}))
         self._log_pixel_path()
+        self._setup_resident()
         if self.mask_areas:
             h, w = self._engine.work_shape
             self._engine.set_mask(self._stream, rasterize_masks(h, w, self.scale, self.mask_areas))
         if self.yolo_dir:
             self._load_yolo()
         return True
+
+    def _setup_resident(self) -> None:
+        """resident_cache takes effect where a GPU-encoding MJPG writer is in use (gpu_encode, codec MJPG, not an
+        MJPEG source, whose bytes are copied) and the engine can retain frames: the engine's pool then holds the
+        pre-motion caches of all its streams."""
+        if not (self.resident_cache and self.gpu_encode and self.codec == "MJPG") or hasattr(self.cap, "read_jpeg"):
+            return
+        eng = self._engine
+        if not all(hasattr(eng, a) for a in ("retain", "release", "reserve_retained", "retained")):
+            self.log.warning("resident_cache: the engine cannot retain frames; writing as without it")
+            return
+        need = eng.n_streams * self.cache_frames
+        if eng.retained[1] < need:
+            eng.reserve_retained(need)
+        self._resident = True
 
     def _log_pixel_path(self) -> None:
         """One line per video naming the kernels that run its per-pixel chain (MotionEngine.pixel_path), and a
@@ -496,6 +536,7 @@ class VideoMotion:
                 raise RuntimeError("a shared multi-stream engine is driven by StreamGroup")
             if self._pipe is None:
                 self._pipe = iter(BatchFeeder(eng, [self.cap], self.batch, self.pipeline_depth))
+            _end_batch(eng, [self])  # (resident_cache) before the feeder hands the consumed batch's slot out again
             b = next(self._pipe, None)
             if b is None:
                 return False
@@ -513,10 +554,12 @@ class VideoMotion:
             return [VideoFrame(None, self.show, yuv=(y, b.yuv)) for y in b.frames[stream]]
         return [VideoFrame(r, self.show) for r in b.frames[stream]]
 
-    def _raw_loader(self, eng, gen: int, t: int, s: int, jpeg: bytes, yuv=None):
+    def _raw_loader(self, eng, gen: int, t: int, s: int, jpeg: bytes, yuv=None, vf=None):
         def load():
             if eng.generation == gen:  # the batch's decoded frame is still in the engine's input slot
                 return eng.read_frame(t, s)
+            if vf is not None and vf._dev is not None:  # (resident_cache) its retained copy
+                return eng.read_retained(vf._dev)
             if yuv is not None:  # a YUV frame of an older batch: the same conversion on the host
                 return videoio.yuv_to_bgr(yuv[0], self.frame_width, self.frame_height, yuv[1])
             if self._jpeg_dec is None:
@@ -527,8 +570,11 @@ class VideoMotion:
     def bind_results(self, vfs, eng, stream: int) -> None:
         for t, vf in enumerate(vfs):
             if (vf.jpeg is not None or vf.yuv is not None) and vf._raw is None:
-                vf._load = self._raw_loader(eng, eng.generation, t, stream, vf.jpeg, vf.yuv)
+                vf._load = self._raw_loader(eng, eng.generation, t, stream, vf.jpeg, vf.yuv,
+                                            *((vf,) if self._resident else ()))
             vf._bound = _Bound(eng, eng.generation, t, stream)
+            if self._resident:
+                vf._slot = (eng.generation, t, stream)
             vf.contours = eng.contours(t, stream)
             vf.processed = True
             vf.index = self.frames_read
@@ -547,7 +593,9 @@ class VideoMotion:
         self.outfile = videoio.open_writer(self.outfile_name, self.codec, self.fps,
                                            (self.frame_width, self.frame_height),
                                            jpeg=hasattr(self.cap, "read_jpeg"), gpu_encode=self.gpu_encode,
-                                           device=self.device)
+                                           device=self.device,
+                                           **({"encode_batch": min(self.batch + self.cache_frames, 64)}
+                                              if self._resident else {}))
 
     def output_frame(self, frame: VideoFrame = None) -> None:
         """fm.py:509-530"""
@@ -562,12 +610,27 @@ class VideoMotion:
 
     def _write_frame(self, frame: VideoFrame) -> None:
         self._write(lambda: frame.raw, getattr(frame, "index", -1), getattr(frame, "jpeg", None),
-                    getattr(frame, "_bound", None))
+                    getattr(frame, "_bound", None), *((frame,) if self._resident else ()))
 
-    def _put(self, raw, jpeg, bound=None) -> None:
+    def _device_address(self, frame) -> typing.Optional[int]:
+        """(resident_cache) Where the frame lies in HBM now: its retained copy, or its slot while its batch is the
+        engine's current one."""
+        if getattr(frame, "_dev", None) is not None:
+            return frame._dev
+        sl = getattr(frame, "_slot", None)
+        if sl is not None and sl[0] == self._engine.generation:
+            return self._engine.frame_device_ptr(sl[1], sl[2])
+        return None
+
+    def _put(self, raw, jpeg, bound=None, frame=None) -> None:
         out = self.outfile
+        ptr = self._device_address(frame) if self._resident and hasattr(out, "queue_device") else None
         if jpeg is not None and hasattr(out, "write_jpeg"):
             out.write_jpeg(jpeg)  # MJPEG in, MJPG out: the source's bytes, no re-encode
+        elif ptr is not None and getattr(out, "encoder", None) is not None:
+            # encoded with the rest of what this batch writes (_end_batch); the host copy, if there is one, only
+            # should the encoder refuse (the array itself: a cleanup may empty the frame before the flush)
+            out.queue_device(ptr, raw if getattr(frame, "_raw", None) is None else frame._raw)
         elif (bound is not None and getattr(out, "encoder", None) is not None
               and bound.engine.generation == bound.gen):
             # GPU writer, the frame's batch still current: encoded where it lies in HBM (fm_frame_device)
@@ -575,16 +638,16 @@ class VideoMotion:
         else:  # any other writer, or a frame of an older batch (the pre-motion cache): the host copy
             out.write(raw() if callable(raw) else raw)
 
-    def _write(self, raw, index, jpeg=None, bound=None):
+    def _write(self, raw, index, jpeg=None, bound=None, *frame):
         if not self.wrote_frames:
             self._make_outfile()
             self.wrote_frames = True
         try:
-            self._put(raw, jpeg, bound)
+            self._put(raw, jpeg, bound, *frame)
         except Exception as e:  # noqa: BLE001 (fm.py:527-530)
             self.log.warning("Having to create output file due to exception: {}".format(e))
             self._make_outfile()
-            self._put(raw, jpeg, bound)
+            self._put(raw, jpeg, bound, *frame)
         self.written_indices.append(index)
 
     # -- the hot path (fm.py:487-494, 619-636, 638-662) ------------------------
@@ -600,6 +663,7 @@ class VideoMotion:
         if self._pipe is not None:
             raise RuntimeError("cannot process an external frame while the decode-ahead pipeline is running")
         eng = self._engine
+        _end_batch(eng, [self])
         eng.submit(np.asarray(frame.raw, dtype=np.uint8)[None, None])
         eng.wait()
         self.bind_results([frame], eng, self._stream)
@@ -653,6 +717,10 @@ class VideoMotion:
         else:
             if self.cleanup_flag:
                 self.cleanup_cache()
+            if self._resident and 0 < self.cache_frames == len(self.frame_cache):
+                old = self.frame_cache.popleft()  # (deque(maxlen) would evict it silently)
+                if old is not None:
+                    old.release_retained()
             self.frame_cache.append(self.current_frame)
             self.current_frame.in_cache = True
 
@@ -774,12 +842,33 @@ class VideoMotion:
                     frame.in_cache = False
                     frame.cleanup()
             self.frame_cache.clear()
+        self._release_retained(everything=True)  # (after the writer's last flush)
         if self._own_engine and self._engine is not None:
             self._engine.close()
             self._engine = None
         if self._jpeg_dec is not None:
             self._jpeg_dec.close()
             self._jpeg_dec = None
+
+    def _release_retained(self, everything: bool = False) -> list:
+        """(resident_cache) The retained copies nothing needs any more -- handed back by a cleanup, or of frames no
+        longer in frame_cache, written or evicted (all of them with `everything`) -- released now (shared engine:
+        returned for the caller to release with the other streams')."""
+        if not self._kept and not self._free:
+            return []
+        alive = set() if everything else {id(f) for f in self.frame_cache}
+        kept = []
+        for vf in self._kept:
+            if vf._dev is not None and id(vf) in alive:
+                kept.append(vf)
+            else:
+                vf.release_retained()
+        self._kept = kept
+        free, self._free = self._free, []
+        if everything and free and self._engine is not None:
+            self._engine.release(free)
+            return []
+        return free
 
     # -- main loop (fm.py:852-904) ---------------------------------------------
     def step(self) -> None:
@@ -807,6 +896,27 @@ class VideoMotion:
                 break
         self.cleanup()
         return self.wrote_frames, self.err_msg, tuple(self.seen_objects)
+
+
+def _end_batch(eng, videos) -> None:
+    """resident_cache, between the last frame of a consumed batch and the next engine.wait(): every writer of the batch
+    encodes what the batch queued on it; the retained copies of frames that left a frame_cache, written or evicted,
+    are released; the batch's frames still waiting in a frame_cache are retained, in one call for the whole engine."""
+    vids = [v for v in videos if v._resident]
+    if not vids:
+        return
+    for v in vids:
+        if v.outfile is not None and hasattr(v.outfile, "flush"):
+            v.outfile.flush()
+    free = [p for v in vids for p in v._release_retained()]
+    if free:
+        eng.release(free)
+    want = [(v, vf) for v in vids for vf in v.frame_cache
+            if vf is not None and vf._dev is None and vf._slot is not None and vf._slot[0] == eng.generation]
+    if want:
+        for (v, vf), p in zip(want, eng.retain([vf._slot[1:] for _, vf in want])):
+            vf._dev, vf._owner = p, v
+            v._kept.append(vf)
 
 
 def run_vid(filename, **kwargs) -> tuple:
@@ -878,6 +988,7 @@ class StreamGroup:
                 for vf in vfs:
                     v.current_frame = vf
                     v.step()
+            _end_batch(self.engine, self.videos)
         out = []
         for f, v in zip(self.filenames, self.videos):
             v.cleanup()

@@ -623,14 +623,19 @@ class MjpegAviWriter(RawAviWriter):
     the GPU instead, and write_device() takes a frame already in HBM; the bytes are the ones Pillow would
     write for the encoder's settings (which replace quality / jpeg_kw), so the file is the same either way.
     A frame the encoder refuses (FMError) is encoded by Pillow and logged.  device_frames / host_frames /
-    fallback_frames count the frames that went each way."""
+    fallback_frames count the frames that went each way, encode_calls the calls made to the encoder.
+
+    queue_device() defers a device frame: flush() encodes the queued frames in order, at most
+    encoder.max_frames per encoder call, and every other method flushes first, so the file's order is
+    always the order of the calls.  A queued address must stay valid until the flush."""
 
     def __init__(self, path: str, fps: float, size, quality: int = 95, encoder=None, **jpeg_kw):
         self.quality = int(quality)
         self.jpeg_kw = jpeg_kw
         self.encoder = encoder
         self.own_encoder = False  # open_writer made the encoder: release() closes it
-        self.device_frames = self.host_frames = self.fallback_frames = 0
+        self.device_frames = self.host_frames = self.fallback_frames = self.encode_calls = 0
+        self._pending = []  # queue_device: (device address, raw) not yet encoded
         if encoder is not None:
             self.quality = int(getattr(encoder, "quality", quality))
             self.jpeg_kw = dict(jpeg_kw, subsampling=int(getattr(encoder, "subsampling", 2)))
@@ -658,6 +663,10 @@ class MjpegAviWriter(RawAviWriter):
         f.write(b"LIST" + struct.pack("<I", 0) + b"movi")
 
     def write_jpeg(self, data: bytes) -> None:
+        self.flush()
+        self._chunk(data)
+
+    def _chunk(self, data: bytes) -> None:
         off = self.f.tell() - (self._movi_at + 8)
         self.f.write(b"00dc" + struct.pack("<I", len(data)) + data + (b"\0" if len(data) & 1 else b""))
         self.index.append(off)
@@ -676,18 +685,20 @@ class MjpegAviWriter(RawAviWriter):
         frame = np.asarray(frame, dtype=np.uint8)
         if frame.shape != (self.h, self.w, 3):
             raise ValueError(f"frame shape {frame.shape} != ({self.h}, {self.w}, 3)")
+        self.flush()
         if self.encoder is None:
-            self.write_jpeg(self._host_encode(frame))
+            self._chunk(self._host_encode(frame))
             return
         from ._native import FMError
         try:
+            self.encode_calls += 1
             data = self.encoder.encode(frame[None])[0]
             self.host_frames += 1
         except FMError as e:
             log.info("frame refused by the GPU encoder (%s); encoding it on the host", e)
             data = self._host_encode(frame)
             self.fallback_frames += 1
-        self.write_jpeg(data)
+        self._chunk(data)
 
     def write_device(self, ptr: int, raw=None) -> None:
         """A BGR frame [h][w][3] already in device memory at address ptr, encoded where it lies.  raw: the same
@@ -695,7 +706,13 @@ class MjpegAviWriter(RawAviWriter):
         from ._native import FMError
         if self.encoder is None:
             raise ValueError("write_device needs a writer made with an encoder")
+        self.flush()
+        self._chunk(self._encode_device_one(ptr, raw))
+
+    def _encode_device_one(self, ptr: int, raw) -> bytes:
+        from ._native import FMError
         try:
+            self.encode_calls += 1
             data = self.encoder.encode_device([int(ptr)])[0]
             self.device_frames += 1
         except FMError as e:
@@ -704,9 +721,42 @@ class MjpegAviWriter(RawAviWriter):
             log.info("device frame refused by the GPU encoder (%s); encoding it on the host", e)
             data = self._host_encode(np.asarray(raw() if callable(raw) else raw, dtype=np.uint8))
             self.fallback_frames += 1
-        self.write_jpeg(data)
+        return data
+
+    def queue_device(self, ptr: int, raw=None) -> None:
+        """write_device, deferred: the frame is encoded and written at the next flush() (which every other
+        method starts with), together with the other queued frames.  ptr must stay valid until then."""
+        if self.encoder is None:
+            raise ValueError("queue_device needs a writer made with an encoder")
+        self._pending.append((int(ptr), raw))
+
+    def flush(self) -> None:
+        """Encode and write the queued device frames in order, one encoder call per chunk of at most
+        encoder.max_frames.  A chunk the encoder refuses goes frame by frame, by write_device's rule."""
+        from ._native import FMError
+        step = max(1, int(getattr(self.encoder, "max_frames", 1) or 1)) if self.encoder is not None else 1
+        while self._pending:
+            chunk, self._pending = self._pending[:step], self._pending[step:]
+            try:
+                self.encode_calls += 1
+                datas = self.encoder.encode_device([p for p, _ in chunk])
+                self.device_frames += len(chunk)
+            except FMError as e:
+                if len(chunk) > 1:
+                    log.info("%d device frames refused by the GPU encoder (%s); encoding them one by one", len(chunk), e)
+                datas = []
+                try:
+                    for p, raw in chunk:
+                        self._chunk(self._encode_device_one(p, raw))
+                except FMError:
+                    self._pending = []  # (what a failed flush had not written does not stay queued)
+                    raise
+            for data in datas:
+                self._chunk(data)
 
     def release(self) -> None:
+        if self.f is not None and self._pending:
+            self.flush()
         if self.own_encoder and self.encoder is not None:
             self.encoder.close()
             self.encoder = None
@@ -773,21 +823,23 @@ def open_capture(source, device: int = 0, gpu_decode: bool | None = None):
     return RawAviCapture(str(source))
 
 
-def open_writer(path: str, codec: str, fps: float, size, jpeg: bool = False, gpu_encode=None, device: int = 0):
+def open_writer(path: str, codec: str, fps: float, size, jpeg: bool = False, gpu_encode=None, device: int = 0,
+                encode_batch: int = 1):
     """cv2.VideoWriter(path, fourcc(codec), fps, size) (fm.py:468-470), else an uncompressed AVI.
     jpeg: the frames come from an MJPEG source -- an 'MJPG' output is then an MjpegAviWriter that
     stores the source's JPEG bytes as they are (write_jpeg), with or without cv2.
     gpu_encode: True (or an encoder object) with codec 'MJPG' -- an MjpegAviWriter whose frames are encoded
     on the GPU (MJpegEncoder on `device`: quality 95, 4:2:0, the bytes Pillow's libjpeg-turbo writes), with
     or without cv2 and for any source but an MJPEG one, whose bytes are still copied.  None / False: as
-    without it."""
+    without it.  encode_batch: the frames that encoder takes per call (its max_frames; what one flush() of
+    queued device frames encodes at once), 1 by default."""
     if jpeg and codec == "MJPG":
         return MjpegAviWriter(path, fps, size)
     if gpu_encode and codec == "MJPG":
         if gpu_encode is True:
             from ._native import MJpegEncoder
-            w = MjpegAviWriter(path, fps, size, encoder=MJpegEncoder(int(size[0]), int(size[1]), max_frames=1,
-                                                                    device=device))
+            w = MjpegAviWriter(path, fps, size, encoder=MJpegEncoder(int(size[0]), int(size[1]),
+                                                                    max_frames=max(1, int(encode_batch)), device=device))
             w.own_encoder = True
             return w
         return MjpegAviWriter(path, fps, size, encoder=gpu_encode)

@@ -457,6 +457,36 @@ int fm_read_frame(fm_ctx* ctx, int frame, int stream, uint8_t* out);
  * cascade without a round trip through host memory.  Valid until the next fm_wait. */
 int fm_frame_device(fm_ctx* ctx, int frame, int stream, const uint8_t** out);
 
+/* ---- Retained source frames: a frame kept in HBM after its batch slot is reused ----------------
+ * fm_frame_device's address dies with the next fm_wait.  The drop-in's pre-motion cache (fm.py:549-601)
+ * holds frames of older batches that may still be written, so the context keeps a pool of buffers of one
+ * source frame each (src_h * src_w * 3 bytes) outside the batch slots; a retained frame's address goes to
+ * fm_mjpeg_encode_frame_list, fm_haar_detect_frame_list, ... like any device frame.
+ *
+ * fm_retain_reserve: (re)sizes the pool to `frames` entries (>= 0; 0 frees it), each at a 256-byte
+ * aligned address.  FM_ESTATE while an entry is in use, FM_EINVAL for a negative count, FM_ENOMEM
+ * when the allocation fails (the previous pool stays as it was).  The pool counts in fm_footprint
+ * and goes with fm_destroy. */
+int fm_retain_reserve(fm_ctx* ctx, int frames);
+/* Copies n source frames of the last waited batch, named as (frame, stream) pairs in frame_stream
+ * [n][2], into free entries: the bytes fm_read_frame returns and fm_frame_device points at (after
+ * fm_submit(on_device = 1) they are read from the caller's buffer, which must still hold them).
+ * dev_out[i] receives the entry's device address.  One kernel launch does all n copies, and they
+ * are complete when the call returns (the call synchronises the stream they ran on), so nothing
+ * queued later -- the slot's next upload, a decode into it, an encoder -- needs ordering against them.
+ * Everything is checked before anything is enqueued: FM_EINVAL for null arguments or a pair outside
+ * the batch (the message names it); FM_ESTATE when no batch has been waited for, its slot was
+ * resubmitted, or it has no source frames; FM_ENOMEM when fewer than n entries are free (nothing is
+ * copied, the pool is unchanged).  n = 0 is FM_OK; a pair named twice gives two copies. */
+int fm_retain_frames(fm_ctx* ctx, const int32_t* frame_stream, int n, const uint8_t** dev_out);
+/* Frees n entries.  Every address is checked first: one the pool did not hand out, one already
+ * released, or one named twice gives FM_EINVAL and nothing is released. */
+int fm_release_frames(fm_ctx* ctx, const uint8_t* const* dev, int n);
+/* One retained frame (an address fm_retain_frames gave, not yet released) copied to host memory. */
+int fm_read_retained(fm_ctx* ctx, const uint8_t* dev, uint8_t* host_out);
+/* Entries in use and the pool's size (either pointer may be null). */
+int fm_retained_count(const fm_ctx* ctx, int* in_use, int* capacity);
+
 /* ---- YUV input: NV12 / I420 / YUY2 / UYVY frames converted to BGR on the GPU ------------------
  * What produces video hands out YUV, not BGR: a hardware decoder leaves NV12 surfaces (pitch, chroma
  * offset) in device memory, a V4L2 camera gives YUY2 or UYVY, raw captures are I420 / NV12 / YUY2.
