@@ -21,6 +21,7 @@ FM_OK, FM_EINVAL, FM_EHIP, FM_ENOMEM, FM_ESTATE, FM_ENOTSUP = 0, -1, -2, -3, -4,
 FM_FLAG_KEEP_PLANES, FM_FLAG_PROFILE, FM_FLAG_PROFILE_PIX, FM_FLAG_CONTOUR_AREA = 0x1, 0x2, 0x4, 0x8
 FM_FLAG_CONTOUR_POINTS = 0x10
 FM_FLAG_AREA_UPSCALE = 0x20
+FM_FLAG_COLOUR_MOTION = 0x40
 RESIZE_IDENTITY, RESIZE_FAST, RESIZE_GENERAL, RESIZE_UP = 0, 1, 2, 3
 RESIZE_NAMES = ("identity", "area_fast", "area", "area_up")
 PLANE_GRAY, PLANE_BLUR, PLANE_DELTA, PLANE_SMALL = 0, 1, 2, 3
@@ -52,6 +53,7 @@ EXPORTED = (
     "fm_haar_bank_detect_frame_list", "fm_haar_bank_detect_frame_list_async", "fm_haar_bank_collect",
     "fm_haar_bank_candidates", "fm_haar_bank_last_ms",
     "fm_retain_reserve", "fm_retain_frames", "fm_release_frames", "fm_read_retained", "fm_retained_count",
+    "fm_background_channels",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -248,6 +250,7 @@ def load() -> C.CDLL:
     L.fm_release_frames.argtypes = [vp, vp, i32]
     L.fm_read_retained.argtypes = [vp, vp, vp]
     L.fm_retained_count.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.fm_background_channels.argtypes = [vp, C.POINTER(i32)]
     for name in EXPORTED:
         if name not in ("fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_last_ms", "fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
                         "fm_haar_last_ms", "fm_haar_bank_destroy", "fm_haar_bank_last_error", "fm_haar_bank_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
@@ -303,9 +306,10 @@ def yuv_frame_bytes(width: int, height: int, fmt, pitch: int = 0, chroma_offset:
 
 
 def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_points=False,
-                 area_upscale=False) -> int:
+                 area_upscale=False, colour_motion=False) -> int:
     """fm_params.flags of MotionEngine's keyword arguments."""
     return ((FM_FLAG_KEEP_PLANES if keep_planes else 0) | (FM_FLAG_CONTOUR_AREA if contour_area else 0) |
+            (FM_FLAG_COLOUR_MOTION if colour_motion else 0) |
             (FM_FLAG_CONTOUR_POINTS if contour_points else 0) | (FM_FLAG_AREA_UPSCALE if area_upscale else 0) |
             (FM_FLAG_PROFILE_PIX if profile == "pix" else FM_FLAG_PROFILE if profile else 0))
 
@@ -313,14 +317,15 @@ def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_p
 def plan(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: int, threshold: int = 12,
          avg: float = 0.1, max_batch: int = 1, max_contours: int = 4096, keep_planes: bool = False,
          profile: bool | str = False, device: int = 0, contour_area: bool = False,
-         contour_points: bool = False, area_upscale: bool = False) -> dict:
+         contour_points: bool = False, area_upscale: bool = False, colour_motion: bool = False) -> dict:
     """What MotionEngine(**params) would set up, asked of the library without touching a device (fm_plan: the
     same validation and selection as fm_create): work_shape (h, w), tiles, max_inflight and pixel_path, one of
-    "small", "pix", "fused", "wide" and "pixel" (the per-frame path: one batch in flight).  FMError as
+    "small", "pix", "fused", "wide", "rgb" (colour_motion) and "pixel" (the per-frame path: one batch in flight).  FMError as
     MotionEngine raises it for parameters the engine refuses."""
     L = load()
     p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg), max_batch,
-                 max_contours, engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale))
+                 max_contours,
+                 engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion))
     out = FMPlan()
     rc = L.fm_plan(C.byref(p), C.byref(out))
     if rc != FM_OK:
@@ -332,13 +337,14 @@ def plan(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: in
 def resize_kind(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: int, threshold: int = 12,
                 avg: float = 0.1, max_batch: int = 1, max_contours: int = 4096, keep_planes: bool = False,
                 profile: bool | str = False, device: int = 0, contour_area: bool = False,
-                contour_points: bool = False, area_upscale: bool = False) -> int:
+                contour_points: bool = False, area_upscale: bool = False, colour_motion: bool = False) -> int:
     """The resize MotionEngine(**params) would put in front of the pixel chain (fm_resize_kind: no device is
     touched): RESIZE_IDENTITY, RESIZE_FAST, RESIZE_GENERAL, or RESIZE_UP for a box wider than the frame, which
     needs area_upscale=True.  FMError as plan() raises it."""
     L = load()
     p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg), max_batch,
-                 max_contours, engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale))
+                 max_contours,
+                 engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion))
     kind = C.c_int32(-1)
     rc = L.fm_resize_kind(C.byref(p), C.byref(kind))
     if rc != FM_OK:
@@ -404,13 +410,16 @@ class MotionEngine:
     def __init__(self, *, n_streams: int, src_w: int, src_h: int, box_size: int, ksize: int,
                  threshold: int, avg: float, max_batch: int = 1, max_contours: int = 4096,
                  keep_planes: bool = False, profile: bool | str = False, device: int = 0,
-                 contour_area: bool = False, contour_points: bool = False, area_upscale: bool = False):
+                 contour_area: bool = False, contour_points: bool = False, area_upscale: bool = False,
+                 colour_motion: bool = False):
         # area_upscale: a box wider than the frame enlarges it, as imutils.resize does (else FM_ENOTSUP)
+        # colour_motion: the chain per colour channel (FM_FLAG_COLOUR_MOTION): the background is (h, w, 3), a pixel
+        # is set where any channel's delta exceeds the threshold; no planes (keep_planes with it: FM_ENOTSUP)
         # profile: True = every kernel timed with HIP events, "pix" = pixel-stream kernels only
         self._L = load()
         p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg),
                      max_batch, max_contours,
-                     engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale))
+                     engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion))
         h = C.c_void_p()
         rc = self._L.fm_create(C.byref(h), C.byref(p))
         if rc != FM_OK:
@@ -420,6 +429,10 @@ class MotionEngine:
         hh, ww = C.c_int(), C.c_int()
         self._check(self._L.fm_work_size(h, C.byref(hh), C.byref(ww)))
         self.work_shape = (hh.value, ww.value)
+        ch = C.c_int()
+        self._check(self._L.fm_background_channels(h, C.byref(ch)))
+        self.colour_motion = ch.value == 3
+        self.background_shape = self.work_shape + ((3,) if self.colour_motion else ())
         self.max_inflight = self._L.fm_max_inflight(h)
         pl = FMPlan()   # the selection fm_create just made (the same function): which kernels run the pixel chain
         self._check(self._L.fm_plan(C.byref(p), C.byref(pl)))
@@ -514,14 +527,14 @@ class MotionEngine:
         return self._init[stream]
 
     def background(self, stream: int) -> np.ndarray:
-        out = np.empty(self.work_shape, np.float64)
+        out = np.empty(self.background_shape, np.float64)
         self._check(self._L.fm_read_background(self._h, stream, _ptr(out)))
         return out
 
     def set_background(self, stream: int, bg: np.ndarray) -> None:
         bg = np.ascontiguousarray(bg, dtype=np.float64)
-        if bg.shape != self.work_shape:
-            raise ValueError(f"background shape {bg.shape} != work shape {self.work_shape}")
+        if bg.shape != self.background_shape:
+            raise ValueError(f"background shape {bg.shape} != {self.background_shape}")
         self._check(self._L.fm_write_background(self._h, stream, _ptr(bg)))
         self._init[stream] = True
 

@@ -2,7 +2,7 @@
 
     python -m find_motion_amd [files] -i DIR -o DIR -c cfg.ini -B 100 -b 20 -t 12 -a 0.1 ...
                               [--gpus N] [--device D] [--batch T] [--group] [--gpu-decode]
-                              [--gpu-encode] [--resident-cache] [--contour-points]
+                              [--gpu-encode] [--resident-cache] [--contour-points] [--colour-motion]
 
 Everything the reference's `run` does around the hot path is kept in its
 shape (INI overriding the CLI, masks from literals and a JSON file, mtime
@@ -95,6 +95,10 @@ def get_args(parser: ArgumentParser) -> None:
     parser.add_argument("--contour-points", action="store_true", default=False,
                         help="Trace every external contour on the GPU and keep its CHAIN_APPROX_SIMPLE points "
                              "(frame.contours[i] then converts to cv2.findContours' (n, 1, 2) array)")
+    parser.add_argument("--colour-motion", action="store_true", default=False,
+                        help="Detect motion per colour channel instead of on the gray image: a pixel moves where "
+                             "any of B, G, R changes by more than the threshold, so a mover as bright as its "
+                             "background is still seen (Gaussian sizes up to 49; no gray / blur / delta planes)")
 
 
 def process_config(config_file: str, args: Namespace) -> Namespace:
@@ -109,7 +113,7 @@ def process_config(config_file: str, args: Namespace) -> Namespace:
         if setting in ("mintime", "cachetime", "avg"):
             use_value = float(value)
         if setting in ("mem", "progress", "debug", "show", "ignore_progress", "ignore_drive", "yolo_tiny", "group",
-                       "gpu_decode", "gpu_encode", "contour_points", "resident_cache"):
+                       "gpu_decode", "gpu_encode", "contour_points", "resident_cache", "colour_motion"):
             if value not in ("True", "False"):
                 raise ValueError("{} must be True or False".format(setting))
             use_value = value == "True"
@@ -227,7 +231,8 @@ def _job_kwargs(args) -> dict:
                 yolo_precision=getattr(args, "yolo_precision", None), gpu_decode=getattr(args, "gpu_decode", None),
                 gpu_encode=getattr(args, "gpu_encode", None),
                 resident_cache=bool(getattr(args, "resident_cache", False)),
-                contour_points=bool(getattr(args, "contour_points", False)))
+                contour_points=bool(getattr(args, "contour_points", False)),
+                colour_motion=bool(getattr(args, "colour_motion", False)))
 
 
 def run_shard(files: list, kwargs: dict, device: int, batch: int, group: bool) -> list:

@@ -49,6 +49,7 @@ constexpr fm_ctx* kNoCtx = nullptr;  // a failure before a context exists: fm_la
 #endif
 constexpr int kSlots = FM_SLOTS;
 constexpr int kWideSlots = 4;  // batch slots of the wide-Gaussian path (its slots carry the blur scratch)
+constexpr size_t kRgbSlotBytes = size_t(256) << 20;  // colour motion: blur scratch of a slot above which kWideSlots
 struct BatchSlot {
     uint8_t* d_in = nullptr;        // host-fed staging [T][S][H][W][3]
     uint8_t* d_yuv = nullptr;       // host-fed YUV staging of fm_submit_yuv (first use; grown on demand)
@@ -60,6 +61,7 @@ struct BatchSlot {
     uint64_t* d_bits = nullptr;     // threshold bit rows (k_pix output)
     uint8_t* d_sblur = nullptr;     // small work images: blur bytes [T*S][w][nty * 64] (k_small_blur -> k_small_scan)
     uint8_t* d_wblur = nullptr;     // wide Gaussians: blur bytes, same layout (k_wide_blur -> k_small_scan)
+    uint8_t* d_cblur = nullptr;     // colour motion: blur bytes [T*S][3][w][nty * 64] (k_rgb_blur -> k_rgb_scan)
     uint64_t* d_dbits = nullptr;    // dilated bit rows = VideoFrame.thresh
     TileRec* d_tiles = nullptr;
     NodeRec* d_nodes = nullptr;
@@ -145,6 +147,8 @@ struct fm_ctx {
     bool use_pix = false;          // k_pix + dilating tile CCL (else k_fused dilates itself)
     bool use_small = false;        // the pixel stage as k_small_blur + k_small_scan (small work images)
     bool use_wide = false;         // the pixel stage as k_wide_blur + k_small_scan (ksize above k_fused's)
+    bool use_rgb = false;          // the pixel stage as k_rgb_blur + k_rgb_scan (FM_FLAG_COLOUR_MOTION)
+    int bg_ch = 1;                 // doubles per work pixel of the background: 3 on a colour context, [h][w][3]
     bool frame_ccl = false;        // the contour pass as one workgroup per frame (ntiles <= kFrameCclTiles)
     int ntx = 0, nty = 0, ntiles = 0, nnodes = 0;  // nnodes: per batch slot
     int nquota = 0;                                             // nodes of each frame's quota
@@ -508,12 +512,28 @@ static int plan_context(fm_ctx* c, const fm_params& p) {
     // a slot of the wide path also holds 1 B per pixel-frame of blur bytes (0.53 GB at 1080p x 256 frames, 2.1 GB
     // at 2160p): kWideSlots of them
     c->nslots = c->use_wide ? std::min(kSlots, kWideSlots) : c->use_fused ? kSlots : 1;
+    // FM_FLAG_COLOUR_MOTION: the chain on the three channels (fm_rgb.hip) at any work size of at most 8,192 tiles
+    // and any ksize up to 49, with the tile machinery of the fused paths behind it.  The gray, blur and delta
+    // planes have no 3-channel form.  A slot also holds 3 B per pixel-frame of blur bytes: where that is more than
+    // kRgbSlotBytes a slot (1080p from 43 frames a batch on), kWideSlots of them, as on the wide path.
+    if (p.flags & FM_FLAG_COLOUR_MOTION) {
+        if (p.flags & FM_FLAG_KEEP_PLANES)
+            return failf(kNoCtx, FM_ENOTSUP, "colour motion keeps no gray / blur / delta planes (FM_FLAG_KEEP_PLANES)");
+        if (!rgb_supported(c->h, c->w, p.ksize))
+            return failf(kNoCtx, FM_ENOTSUP, "colour motion takes ksize up to 49 and at most 8192 tiles (ksize %d, %d tiles)",
+                         p.ksize, tiles);
+        c->use_rgb = c->use_fused = c->use_pix = true;
+        c->use_small = c->use_wide = false;
+        c->bg_ch = 3;
+        const size_t scratch = rgb_scratch_bytes(c->w, (c->h + 63) / 64, (size_t)p.n_streams * p.max_batch);
+        c->nslots = scratch > kRgbSlotBytes ? std::min(kSlots, kWideSlots) : kSlots;
+    }
     return FM_OK;
 }
 
 // the plan's pixel path by name (fm_plan, MotionEngine.pixel_path)
 static const char* pixel_path_name(const fm_ctx* c) {
-    return c->use_wide ? "wide" : c->use_small ? "small" : c->use_pix ? "pix" : c->use_fused ? "fused" : "pixel";
+    return c->use_rgb ? "rgb" : c->use_wide ? "wide" : c->use_small ? "small" : c->use_pix ? "pix" : c->use_fused ? "fused" : "pixel";
 }
 
 int fm_plan(const fm_params* prm, struct fm_plan* out) {
@@ -611,7 +631,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     // runtime multiplexes streams onto GPU_MAX_HW_QUEUES (4) hardware queues in order,
     // and a contour kernel queued ahead of a pixel kernel on a shared queue stalls it
     for (int i = 0; i < 2; i++)
-        if ((rc = dalloc(cp, &c->d_bg[i], S * c->work_plane))) return rc;
+        if ((rc = dalloc(cp, &c->d_bg[i], S * c->work_plane * c->bg_ch))) return rc;
     if ((rc = dalloc(cp, &c->d_keep, S * c->work_plane)) || (rc = dalloc(cp, &c->d_has_keep, S)) ||
         (rc = dalloc(cp, &c->d_init, S)) || (rc = dalloc(cp, &c->d_mask, c->use_fused ? c->work_plane : px)))
         return rc;
@@ -658,6 +678,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
                 (c->use_pix && (rc = dalloc(cp, &b.d_bits, frames * c->ntiles * 64))) ||
                 (c->use_small && (rc = dalloc(cp, &b.d_sblur, small_scratch_bytes(c->h, c->w, c->nty, frames)))) ||
                 (c->use_wide && (rc = dalloc(cp, &b.d_wblur, wide_scratch_bytes(c->w, c->nty, frames)))) ||
+                (c->use_rgb && (rc = dalloc(cp, &b.d_cblur, rgb_scratch_bytes(c->w, c->nty, frames)))) ||
                 (rc = dalloc(cp, &b.d_nodes, (size_t)c->nnodes)))
                 return rc;
         }
@@ -699,8 +720,8 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&c->dh_err, c->h_err, 0));
     *c->h_err = 0;
     FM_HIP_TRY(cp, hipMemset(c->d_has_keep, 0, S));
-    FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * sizeof(double)));
-    FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * sizeof(double)));
+    FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
+    FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
     auto up = [&](auto** d, const auto& v) -> int {
         int r = dalloc(cp, d, v.size());
         if (r) return r;
@@ -972,7 +993,7 @@ FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool a
     fa.dbits = B.d_dbits;
     fa.tiles = B.d_tiles;
     fa.tflag = B.d_tflag;
-    fa.tflag_waves = (c->use_small || c->use_wide) ? 8 : 1;
+    fa.tflag_waves = (c->use_small || c->use_wide || c->use_rgb) ? 8 : 1;
     fa.candf = B.d_candf;
     fa.clist = B.d_clist;
     fa.rlist = B.d_rlist;
@@ -1041,6 +1062,10 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
             FM_HIP_TRY(c, c->timer.timed(ps, init ? "wide_blur_init" : "wide_blur", [&](uint64_t* k1, uint64_t* k2) {
                 return launch_wide(ps, fp, B.d_wblur, k1, k2);
             }, true, init ? "wide_scan_init" : "wide_scan", init ? "wide_init" : "wide"));
+        else if (c->use_rgb)
+            FM_HIP_TRY(c, c->timer.timed(ps, init ? "rgb_blur_init" : "rgb_blur", [&](uint64_t* k1, uint64_t* k2) {
+                return launch_rgb(ps, fp, B.d_cblur, k1, k2);
+            }, true, init ? "rgb_scan_init" : "rgb_scan", init ? "rgb_init" : "rgb"));
         else
             FM_HIP_TRY(c, c->timer.timed(ps, name, [&](uint64_t* ks, uint64_t*) {
                 fp.kstamp = ks;
@@ -1070,9 +1095,9 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
     FM_HIP_TRY(c, hipStreamWaitEvent(cs, B.ev_pix, 0));
     // The 64 x 64 tile pixel kernels (launch_pix) store threshold bits only: every frame's tile flags, the init
     // frame's launch included, come from those bits here, at the head of the chain and ahead of the labelling gate.
-    // (The small-image and wide-Gaussian scans and k_fused write their own.)  Timed by events, like k_regions
+    // (The small-image, wide-Gaussian and colour scans and k_fused write their own.)  Timed by events, like k_regions
     // (FM_FLAG_PROFILE; never in the pixel-only mode on a contour stream).
-    if (c->use_pix && !c->use_small && !c->use_wide)
+    if (c->use_pix && !c->use_small && !c->use_wide && !c->use_rgb)
         FM_HIP_TRY(c, c->timer.timed(cs, "tile_flags", [&](uint64_t*, uint64_t*) { return launch_tile_flags(cs, fa); }, false));
     if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
         FusedArgs fc = fa;
@@ -1712,8 +1737,9 @@ int fm_read_background(fm_ctx* c, int stream, double* out) {
     if (!c->bg_init[stream]) return failf(c, FM_ESTATE, "stream %d has no background yet", stream);
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
     FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, c->work_plane * sizeof(double),
-                              hipMemcpyDeviceToHost, c->stream));
+    const size_t n = c->work_plane * c->bg_ch;  // a colour context: [h][w][3]
+    FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_bg[c->bg_cur] + (size_t)stream * n, n * sizeof(double), hipMemcpyDeviceToHost,
+                              c->stream));
     FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FM_OK;
 }
@@ -1723,10 +1749,17 @@ int fm_write_background(fm_ctx* c, int stream, const double* in) {
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
-    FM_HIP_TRY(c, hipMemcpyAsync(c->d_bg[c->bg_cur] + (size_t)stream * c->work_plane, in, c->work_plane * sizeof(double),
-                              hipMemcpyHostToDevice, c->stream));
+    const size_t n = c->work_plane * c->bg_ch;
+    FM_HIP_TRY(c, hipMemcpyAsync(c->d_bg[c->bg_cur] + (size_t)stream * n, in, n * sizeof(double), hipMemcpyHostToDevice,
+                              c->stream));
     FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bg_init[stream] = 1;
+    return FM_OK;
+}
+
+int fm_background_channels(const fm_ctx* c, int* channels) {
+    if (!c || !channels) return failf(kNoCtx, FM_EINVAL, "null argument");
+    *channels = c->bg_ch;
     return FM_OK;
 }
 

@@ -258,6 +258,15 @@ bool wide_supported(int ksize, const int32_t* coef);
 int wide_lds_bytes(int ksize, const int32_t* coef);
 size_t wide_scratch_bytes(int w, int nty, size_t frames);
 hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks_blur, uint64_t* ks_scan);
+// the chain on the three colour channels (fm_rgb.hip, FM_FLAG_COLOUR_MOTION): k_rgb_blur (every frame and 64 x 64
+// tile of the launch in parallel) + k_rgb_scan (k_small_scan with three backgrounds; the channels' threshold bits
+// ORed).  The kernels take their own argument struct, filled from a: a.bg_in / a.bg_out are [S][h][w][3] doubles
+// here, and the element counts of OpenCV's SIMD rules (a.cvt_simd, a.acc_vec_end) are taken over 3hw, not from a.
+// cblur: rgb_scratch_bytes of the batch's frames, [F][3][x][nty * 64]
+bool rgb_supported(int h, int w, int ksize);
+int rgb_lds_bytes(int ksize);
+size_t rgb_scratch_bytes(int w, int nty, size_t frames);
+hipError_t launch_rgb(hipStream_t st, const FusedArgs& a, uint8_t* cblur, uint64_t* ks_blur, uint64_t* ks_scan);
 // a.tflag (one word per tile-frame) of all a.T * a.S frames from a.bits: after the 64 x 64 tile pixel kernels
 // (launch_pix), ahead of either contour pass below
 hipError_t launch_tile_flags(hipStream_t st, const FusedArgs& a);

@@ -62,7 +62,10 @@ is the (n, 1, 2) int32 array cv2.findContours returns at fm.py:269-272),
 yolo_dir (the directory of cvlib's yolov3 files, default $FM_YOLO_DIR: find_objects
 then tags frames with YOLOv3 on the GPU as fm.py:733-741 does with cvlib; without
 it that stage is off), yolo_precision ("f32", the default, or "f16": the network in
-half precision on the f16 matrix instructions; default $FM_YOLO_PRECISION).
+half precision on the f16 matrix instructions; default $FM_YOLO_PRECISION),
+colour_motion (the chain per colour channel, the TODO at the top of find_motion.py:
+a pixel moves where any of B, G, R changes by more than the threshold, ref_frame is
+(h, w, 3), and frame.gray / blur / frame_delta are None).
 
 There is no CPU fallback: without the HIP library this module raises
 NativeLibraryMissing at VideoMotion construction.
@@ -266,7 +269,7 @@ class VideoMotion:
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
                  pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None,
                  contour_points: bool = False, yolo_dir: str = None, yolo_precision: str = None,
-                 resident_cache: bool = False) -> None:
+                 resident_cache: bool = False, colour_motion: bool = False) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -322,7 +325,11 @@ class VideoMotion:
         # MI355X engine
         self.device = int(device)
         self.batch = max(1, int(batch))
-        self.keep_planes = (show or self.debug) if keep_planes is None else bool(keep_planes)
+        # colour_motion: motion per colour channel (the TODO at the top of find_motion.py): ref_frame is (h, w, 3);
+        # the gray / blur / delta planes have no 3-channel form, so show and debug logging do not request them and
+        # frame.gray / frame.blur / frame.frame_delta are None (thresh and contours as usual)
+        self.colour_motion = bool(colour_motion)
+        self.keep_planes = ((show or self.debug) and not self.colour_motion) if keep_planes is None else bool(keep_planes)
         self._engine = engine
         self._own_engine = engine is None
         self._pipe = None  # BatchFeeder iterator of read() (single-stream engine)
@@ -419,6 +426,7 @@ class VideoMotion:
                                         avg=self.avg, max_batch=self.batch, keep_planes=self.keep_planes,
                                         device=self.device, contour_area=self.area_filter,
                                         **({"contour_points": True} if self.contour_points else {}),
+                                        **({"colour_motion": True} if self.colour_motion else {}),
                                         # a box wider than the frame enlarges it, as imutils.resize does
                                         **({"area_upscale": True} if self.box_size > self.frame_width else {}))
         self._log_pixel_path()
@@ -963,14 +971,16 @@ class StreamGroup:
         blur_scale = kwargs.get("blur_scale", 20)
         show = kwargs.get("show", False)
         dbg = kwargs.get("log_level", logging.INFO) == logging.DEBUG
+        colour = bool(kwargs.get("colour_motion"))  # no planes with it (VideoMotion.__init__)
         self.batch = max(1, int(batch))
         make = engine if engine is not None else MotionEngine  # engine: a factory with MotionEngine's signature
         mbs = kwargs.get("min_box_scale", VideoMotion.DEFAULT_MIN_BOX_SCALE)
         area_filter = int(W * H / 2 * (box / W)) < int(math.pow(box / mbs, 2))  # as _load_video decides
         self.engine = make(n_streams=S, src_w=W, src_h=H, box_size=box, ksize=make_gaussian_size(box, blur_scale),
                            threshold=kwargs.get("threshold", 7), avg=kwargs.get("avg", 0.1), max_batch=self.batch,
-                           keep_planes=show or dbg, device=device, contour_area=area_filter,
+                           keep_planes=(show or dbg) and not colour, device=device, contour_area=area_filter,
                            **({"contour_points": True} if kwargs.get("contour_points") else {}),
+                           **({"colour_motion": True} if colour else {}),
                            **({"area_upscale": True} if box > W else {}))
         self.videos = [VideoMotion(filename=f, capture=c, engine=self.engine, stream=s, batch=self.batch, **kwargs)
                        for s, (f, c) in enumerate(zip(self.filenames, caps))]

@@ -55,6 +55,17 @@ extern "C" {
                                       (fm.py:490), and cv2.resize(INTER_AREA) then runs its 8-bit bilinear resizer
                                       with area-mode taps (the kernel `resize_area_up`).  Off: FM_ENOTSUP for such
                                       a box, as before; no kernel, buffer, result or status differs */
+#define FM_FLAG_COLOUR_MOTION 0x40u /* detect motion per colour channel: the chain the reference would run without
+                                       its cvtColor line (fm.py:493; the TODO at the top of find_motion.py).
+                                       GaussianBlur per channel, the keep-mask zeroes all three, absdiff /
+                                       convertScaleAbs / accumulateWeighted run element-wise over [h][w][3] (their
+                                       SIMD rules count 3hw elements), and a pixel is set where any channel's
+                                       delta exceeds the threshold; dilation, contours, boxes and points as
+                                       always.  A mover whose gray level equals the background's is seen.  The
+                                       kernels `rgb_blur` + `rgb_scan`; the background has 3 doubles per pixel
+                                       (fm_background_channels).  FM_ENOTSUP with ksize above 49, more than 8,192
+                                       tiles, or FM_FLAG_KEEP_PLANES (FM_PLANE_SMALL still works).  Off: no
+                                       kernel, buffer, result or status differs */
 
 /* planes for fm_read_plane */
 #define FM_PLANE_GRAY 0  /* VideoFrame.gray        (fm.py:493) */
@@ -106,6 +117,7 @@ void fm_destroy(fm_ctx* ctx);
  *   "fused"  k_fused (other ksize up to 49)
  *   "wide"   k_wide_blur + k_small_scan (ksize above 49, more than 16 and at most 8,192 tiles of 64 x 64,
  *            no FM_FLAG_KEEP_PLANES)
+ *   "rgb"    k_rgb_blur + k_rgb_scan (FM_FLAG_COLOUR_MOTION: ksize up to 49, at most 8,192 tiles)
  *   "pixel"  one k_pixel launch per frame and the pixel-level CCL: one batch in flight
  * (The struct has no typedef: C keeps struct tags apart from function names, not typedef names.) */
 struct fm_plan {
@@ -226,9 +238,12 @@ int fm_read_threshold_bits(fm_ctx* ctx, int frame, int stream, uint64_t* out);
  * resized BGR frame, h*w*3 bytes (FM_ESTATE when box_size = frame width). */
 int fm_read_plane(fm_ctx* ctx, int plane, int frame, int stream, uint8_t* out);
 
-/* Background model (VideoMotion.ref_frame, float64, fm.py:652, 659), h*w doubles. */
+/* Background model (VideoMotion.ref_frame, float64, fm.py:652, 659), h*w doubles; on a context with
+ * FM_FLAG_COLOUR_MOTION 3*h*w doubles in [h][w][3] order (B, G, R), the numpy array it would be. */
 int fm_read_background(fm_ctx* ctx, int stream, double* out);
 int fm_write_background(fm_ctx* ctx, int stream, const double* in);
+/* Doubles per work pixel of the background: 1, or 3 with FM_FLAG_COLOUR_MOTION. */
+int fm_background_channels(const fm_ctx* ctx, int* channels);
 
 /* Launch on the caller's HIP stream (hipStream_t) instead of the context's own
  * stream; NULL restores the context stream.  FM_ESTATE while a batch is in flight.
