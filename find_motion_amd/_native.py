@@ -22,6 +22,7 @@ FM_FLAG_KEEP_PLANES, FM_FLAG_PROFILE, FM_FLAG_PROFILE_PIX, FM_FLAG_CONTOUR_AREA 
 FM_FLAG_CONTOUR_POINTS = 0x10
 FM_FLAG_AREA_UPSCALE = 0x20
 FM_FLAG_COLOUR_MOTION = 0x40
+FM_FLAG_MOG2 = 0x80
 RESIZE_IDENTITY, RESIZE_FAST, RESIZE_GENERAL, RESIZE_UP = 0, 1, 2, 3
 RESIZE_NAMES = ("identity", "area_fast", "area", "area_up")
 PLANE_GRAY, PLANE_BLUR, PLANE_DELTA, PLANE_SMALL = 0, 1, 2, 3
@@ -54,6 +55,7 @@ EXPORTED = (
     "fm_haar_bank_candidates", "fm_haar_bank_last_ms",
     "fm_retain_reserve", "fm_retain_frames", "fm_release_frames", "fm_read_retained", "fm_retained_count",
     "fm_background_channels",
+    "fm_mog2_defaults", "fm_create_mog2", "fm_mog2_read_model", "fm_mog2_write_model", "fm_mog2_background",
 )
 YOLO_CONV, YOLO_MAXPOOL, YOLO_UPSAMPLE, YOLO_ROUTE, YOLO_SHORTCUT, YOLO_HEAD = range(6)
 YOLO_CAND = 9  # floats per decoded row: head, row, bx, by, bw, bh, obj, class, p
@@ -78,6 +80,43 @@ class FMParams(C.Structure):
     _fields_ = [("device", C.c_int), ("n_streams", C.c_int), ("src_w", C.c_int), ("src_h", C.c_int),
                 ("box_size", C.c_int), ("ksize", C.c_int), ("threshold", C.c_int), ("avg", C.c_double),
                 ("max_batch", C.c_int), ("max_contours", C.c_int), ("flags", C.c_uint)]
+
+
+class Mog2Params(C.Structure):
+    """fm_mog2_params: BackgroundSubtractorMOG2's parameters (five mixtures).  Mog2Params() holds OpenCV's defaults;
+    keyword arguments override them."""
+    _fields_ = [("history", C.c_int), ("var_threshold", C.c_float), ("var_threshold_gen", C.c_float),
+                ("background_ratio", C.c_float), ("var_init", C.c_float), ("var_min", C.c_float),
+                ("var_max", C.c_float), ("complexity_reduction", C.c_float), ("shadow_tau", C.c_float),
+                ("detect_shadows", C.c_int), ("learning_rate", C.c_double)]
+    DEFAULTS = dict(history=500, var_threshold=16.0, var_threshold_gen=9.0, background_ratio=0.9, var_init=15.0,
+                    var_min=4.0, var_max=75.0, complexity_reduction=0.05, shadow_tau=0.5, detect_shadows=1,
+                    learning_rate=-1.0)
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown MOG2 parameter(s): {sorted(unknown)}")
+        vals = dict(self.DEFAULTS, **kw)
+        vals["detect_shadows"] = int(bool(vals["detect_shadows"]))
+        super().__init__(**vals)
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+def mog2_params(mog2) -> "Mog2Params | None":
+    """MotionEngine's mog2 argument as parameters: None / False = off, True = the defaults, a dict of overrides,
+    or a Mog2Params."""
+    if mog2 is None or mog2 is False:
+        return None
+    if mog2 is True:
+        return Mog2Params()
+    if isinstance(mog2, Mog2Params):
+        return mog2
+    if isinstance(mog2, dict):
+        return Mog2Params(**mog2)
+    raise TypeError("mog2 must be None, True, a dict or a Mog2Params")
 
 
 class FMPlan(C.Structure):
@@ -251,6 +290,11 @@ def load() -> C.CDLL:
     L.fm_read_retained.argtypes = [vp, vp, vp]
     L.fm_retained_count.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.fm_background_channels.argtypes = [vp, C.POINTER(i32)]
+    L.fm_mog2_defaults.argtypes = [C.POINTER(Mog2Params)]
+    L.fm_create_mog2.argtypes = [C.POINTER(vp), C.POINTER(FMParams), C.POINTER(Mog2Params)]
+    L.fm_mog2_read_model.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.fm_mog2_write_model.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.fm_mog2_background.argtypes = [vp, i32, vp]
     for name in EXPORTED:
         if name not in ("fm_yolo_destroy", "fm_yolo_last_error", "fm_yolo_last_ms", "fm_destroy", "fm_last_error", "fm_abi_version", "fm_haar_destroy", "fm_haar_last_error",
                         "fm_haar_last_ms", "fm_haar_bank_destroy", "fm_haar_bank_last_error", "fm_haar_bank_last_ms", "fm_mjpeg_destroy", "fm_mjpeg_last_error", "fm_mjpeg_last_ms",
@@ -306,10 +350,10 @@ def yuv_frame_bytes(width: int, height: int, fmt, pitch: int = 0, chroma_offset:
 
 
 def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_points=False,
-                 area_upscale=False, colour_motion=False) -> int:
+                 area_upscale=False, colour_motion=False, mog2=None) -> int:
     """fm_params.flags of MotionEngine's keyword arguments."""
     return ((FM_FLAG_KEEP_PLANES if keep_planes else 0) | (FM_FLAG_CONTOUR_AREA if contour_area else 0) |
-            (FM_FLAG_COLOUR_MOTION if colour_motion else 0) |
+            (FM_FLAG_COLOUR_MOTION if colour_motion else 0) | (FM_FLAG_MOG2 if mog2_params(mog2) is not None else 0) |
             (FM_FLAG_CONTOUR_POINTS if contour_points else 0) | (FM_FLAG_AREA_UPSCALE if area_upscale else 0) |
             (FM_FLAG_PROFILE_PIX if profile == "pix" else FM_FLAG_PROFILE if profile else 0))
 
@@ -317,15 +361,17 @@ def engine_flags(keep_planes=False, profile=False, contour_area=False, contour_p
 def plan(*, n_streams: int = 1, src_w: int, src_h: int, box_size: int, ksize: int, threshold: int = 12,
          avg: float = 0.1, max_batch: int = 1, max_contours: int = 4096, keep_planes: bool = False,
          profile: bool | str = False, device: int = 0, contour_area: bool = False,
-         contour_points: bool = False, area_upscale: bool = False, colour_motion: bool = False) -> dict:
+         contour_points: bool = False, area_upscale: bool = False, colour_motion: bool = False,
+         mog2=None) -> dict:
     """What MotionEngine(**params) would set up, asked of the library without touching a device (fm_plan: the
     same validation and selection as fm_create): work_shape (h, w), tiles, max_inflight and pixel_path, one of
-    "small", "pix", "fused", "wide", "rgb" (colour_motion) and "pixel" (the per-frame path: one batch in flight).  FMError as
+    "small", "pix", "fused", "wide", "rgb" (colour_motion), "mog2" (mog2: the flag alone decides the plan, the
+    parameters are checked by MotionEngine) and "pixel" (the per-frame path: one batch in flight).  FMError as
     MotionEngine raises it for parameters the engine refuses."""
     L = load()
     p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg), max_batch,
                  max_contours,
-                 engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion))
+                 engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion, mog2))
     out = FMPlan()
     rc = L.fm_plan(C.byref(p), C.byref(out))
     if rc != FM_OK:
@@ -411,7 +457,10 @@ class MotionEngine:
                  threshold: int, avg: float, max_batch: int = 1, max_contours: int = 4096,
                  keep_planes: bool = False, profile: bool | str = False, device: int = 0,
                  contour_area: bool = False, contour_points: bool = False, area_upscale: bool = False,
-                 colour_motion: bool = False):
+                 colour_motion: bool = False, mog2=None):
+        # mog2: None, True (OpenCV's defaults), a dict of overrides or a Mog2Params: the Gaussian-mixture background
+        # model in place of the running average (FM_FLAG_MOG2); threshold and avg are then unused, there is no
+        # background() but mog2_background() / mog2_model(), and no planes
         # area_upscale: a box wider than the frame enlarges it, as imutils.resize does (else FM_ENOTSUP)
         # colour_motion: the chain per colour channel (FM_FLAG_COLOUR_MOTION): the background is (h, w, 3), a pixel
         # is set where any channel's delta exceeds the threshold; no planes (keep_planes with it: FM_ENOTSUP)
@@ -419,9 +468,13 @@ class MotionEngine:
         self._L = load()
         p = FMParams(device, n_streams, src_w, src_h, box_size, ksize, int(threshold), float(avg),
                      max_batch, max_contours,
-                     engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion))
+                     engine_flags(keep_planes, profile, contour_area, contour_points, area_upscale, colour_motion, mog2))
         h = C.c_void_p()
-        rc = self._L.fm_create(C.byref(h), C.byref(p))
+        self.mog2 = mog2_params(mog2)  # the parameters in force, or None
+        if self.mog2 is not None:
+            rc = self._L.fm_create_mog2(C.byref(h), C.byref(p), C.byref(self.mog2))
+        else:
+            rc = self._L.fm_create(C.byref(h), C.byref(p))
         if rc != FM_OK:
             raise FMError(rc, self._L.fm_last_error(None).decode())
         self._h = h
@@ -429,8 +482,9 @@ class MotionEngine:
         hh, ww = C.c_int(), C.c_int()
         self._check(self._L.fm_work_size(h, C.byref(hh), C.byref(ww)))
         self.work_shape = (hh.value, ww.value)
-        ch = C.c_int()
-        self._check(self._L.fm_background_channels(h, C.byref(ch)))
+        ch = C.c_int(1)
+        if self.mog2 is None:
+            self._check(self._L.fm_background_channels(h, C.byref(ch)))
         self.colour_motion = ch.value == 3
         self.background_shape = self.work_shape + ((3,) if self.colour_motion else ())
         self.max_inflight = self._L.fm_max_inflight(h)
@@ -526,7 +580,35 @@ class MotionEngine:
         """True once the stream's background exists (after its first frame, fm.py:651-652)."""
         return self._init[stream]
 
+    def mog2_model(self, stream: int) -> dict:
+        """The stream's Gaussian-mixture model: weight, mean, var float32 (5, h, w), nmodes uint8 (h, w), nframes.
+        Entries at mode >= nmodes are 0."""
+        h, w = self.work_shape
+        wt, mean, var = (np.zeros((5, h, w), np.float32) for _ in range(3))
+        nm = np.zeros((h, w), np.uint8)
+        nf = C.c_int64()
+        self._check(self._L.fm_mog2_read_model(self._h, stream, _ptr(wt), _ptr(mean), _ptr(var), _ptr(nm), C.byref(nf)))
+        return {"weight": wt, "mean": mean, "var": var, "nmodes": nm, "nframes": int(nf.value)}
+
+    def set_mog2_model(self, stream: int, weight, mean, var, nmodes, nframes: int) -> None:
+        h, w = self.work_shape
+        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (weight, mean, var)]
+        nm = np.ascontiguousarray(nmodes, dtype=np.uint8)
+        if any(a.shape != (5, h, w) for a in arrs) or nm.shape != (h, w):
+            raise ValueError(f"model arrays must be (5, {h}, {w}) and nmodes ({h}, {w})")
+        nf = C.c_int64(int(nframes))
+        self._check(self._L.fm_mog2_write_model(self._h, stream, *[_ptr(a) for a in arrs], _ptr(nm), C.byref(nf)))
+        self._init[stream] = True
+
+    def mog2_background(self, stream: int) -> np.ndarray:
+        """cv2's getBackgroundImage of the stream's model: uint8 (h, w), 0 where a pixel has no mode yet."""
+        out = np.zeros(self.work_shape, np.uint8)
+        self._check(self._L.fm_mog2_background(self._h, stream, _ptr(out)))
+        return out
+
     def background(self, stream: int) -> np.ndarray:
+        if self.mog2 is not None:
+            raise FMError(FM_ESTATE, "a mog2 engine has no running average: use mog2_background() or mog2_model()")
         out = np.empty(self.background_shape, np.float64)
         self._check(self._L.fm_read_background(self._h, stream, _ptr(out)))
         return out

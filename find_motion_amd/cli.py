@@ -3,6 +3,8 @@
     python -m find_motion_amd [files] -i DIR -o DIR -c cfg.ini -B 100 -b 20 -t 12 -a 0.1 ...
                               [--gpus N] [--device D] [--batch T] [--group] [--gpu-decode]
                               [--gpu-encode] [--resident-cache] [--contour-points] [--colour-motion]
+                              [--background-model average|mog2] [--mog2-history N] [--mog2-var-threshold V]
+                              [--mog2-no-shadows] [--mog2-learning-rate R]
 
 Everything the reference's `run` does around the hot path is kept in its
 shape (INI overriding the CLI, masks from literals and a JSON file, mtime
@@ -99,6 +101,18 @@ def get_args(parser: ArgumentParser) -> None:
                         help="Detect motion per colour channel instead of on the gray image: a pixel moves where "
                              "any of B, G, R changes by more than the threshold, so a mover as bright as its "
                              "background is still seen (Gaussian sizes up to 49; no gray / blur / delta planes)")
+    parser.add_argument("--background-model", choices=("average", "mog2"), default="average",
+                        help="average: the running average and threshold (-a, -t).  mog2: OpenCV's Gaussian-mixture "
+                             "background subtractor applied to the blurred frame, which learns a flickering or "
+                             "swaying background instead of firing on it (-a and -t unused; no gray / blur / delta "
+                             "planes)")
+    parser.add_argument("--mog2-history", type=int, default=500, help="mog2: frames of history")
+    parser.add_argument("--mog2-var-threshold", type=float, default=16.0,
+                        help="mog2: squared distance, in variances, below which the background explains a pixel")
+    parser.add_argument("--mog2-no-shadows", action="store_true", default=False,
+                        help="mog2: do not detect shadows (a shadow is otherwise no motion)")
+    parser.add_argument("--mog2-learning-rate", type=float, default=-1.0,
+                        help="mog2: learning rate in [0, 1]; negative: automatic")
 
 
 def process_config(config_file: str, args: Namespace) -> Namespace:
@@ -108,15 +122,19 @@ def process_config(config_file: str, args: Namespace) -> Namespace:
     for setting, value in config["settings"].items():
         setting = setting.replace("-", "_")
         use_value: typing.Any = value
-        if setting in ("processes", "blur_scale", "min_box_scale", "threshold", "fps", "box_size", "gpus", "batch"):
+        if setting in ("processes", "blur_scale", "min_box_scale", "threshold", "fps", "box_size", "gpus", "batch",
+                       "mog2_history"):
             use_value = int(value)
-        if setting in ("mintime", "cachetime", "avg"):
+        if setting in ("mintime", "cachetime", "avg", "mog2_var_threshold", "mog2_learning_rate"):
             use_value = float(value)
         if setting in ("mem", "progress", "debug", "show", "ignore_progress", "ignore_drive", "yolo_tiny", "group",
-                       "gpu_decode", "gpu_encode", "contour_points", "resident_cache", "colour_motion"):
+                       "gpu_decode", "gpu_encode", "contour_points", "resident_cache", "colour_motion",
+                       "mog2_no_shadows"):
             if value not in ("True", "False"):
                 raise ValueError("{} must be True or False".format(setting))
             use_value = value == "True"
+        if setting == "background_model" and value not in ("average", "mog2"):
+            raise ValueError("background_model must be average or mog2")
         if setting == "yolo_precision" and value not in ("f32", "f16"):
             raise ValueError("yolo_precision must be f32 or f16")
         if setting in ("masks", "cameras", "time_order"):
@@ -232,7 +250,13 @@ def _job_kwargs(args) -> dict:
                 gpu_encode=getattr(args, "gpu_encode", None),
                 resident_cache=bool(getattr(args, "resident_cache", False)),
                 contour_points=bool(getattr(args, "contour_points", False)),
-                colour_motion=bool(getattr(args, "colour_motion", False)))
+                colour_motion=bool(getattr(args, "colour_motion", False)),
+                # (the mixture model's keys only when it is chosen: the call as it was otherwise)
+                **({"background_model": "mog2", "mog2_history": int(getattr(args, "mog2_history", 500)),
+                    "mog2_var_threshold": float(getattr(args, "mog2_var_threshold", 16.0)),
+                    "mog2_detect_shadows": not getattr(args, "mog2_no_shadows", False),
+                    "mog2_learning_rate": float(getattr(args, "mog2_learning_rate", -1.0))}
+                   if getattr(args, "background_model", "average") == "mog2" else {}))
 
 
 def run_shard(files: list, kwargs: dict, device: int, batch: int, group: bool) -> list:

@@ -62,6 +62,9 @@ struct BatchSlot {
     uint8_t* d_sblur = nullptr;     // small work images: blur bytes [T*S][w][nty * 64] (k_small_blur -> k_small_scan)
     uint8_t* d_wblur = nullptr;     // wide Gaussians: blur bytes, same layout (k_wide_blur -> k_small_scan)
     uint8_t* d_cblur = nullptr;     // colour motion: blur bytes [T*S][3][w][nty * 64] (k_rgb_blur -> k_rgb_scan)
+    uint8_t* d_mblur = nullptr;     // Gaussian mixture: blur bytes [T*S][w][nty * 64] (k_small_blur / k_wide_blur -> k_mog2_scan)
+    float* d_alpha = nullptr;       // Gaussian mixture: the learning rate of each frame [T][S]
+    float* h_alpha = nullptr;       // and its page-locked staging
     uint64_t* d_dbits = nullptr;    // dilated bit rows = VideoFrame.thresh
     TileRec* d_tiles = nullptr;
     NodeRec* d_nodes = nullptr;
@@ -148,7 +151,15 @@ struct fm_ctx {
     bool use_small = false;        // the pixel stage as k_small_blur + k_small_scan (small work images)
     bool use_wide = false;         // the pixel stage as k_wide_blur + k_small_scan (ksize above k_fused's)
     bool use_rgb = false;          // the pixel stage as k_rgb_blur + k_rgb_scan (FM_FLAG_COLOUR_MOTION)
-    int bg_ch = 1;                 // doubles per work pixel of the background: 3 on a colour context, [h][w][3]
+    int bg_ch = 1;                 // doubles per work pixel of the background: 3 on a colour context, [h][w][3];
+                                   // 0 on a Gaussian-mixture context
+    bool use_mog2 = false;         // the pixel stage as k_small_blur / k_wide_blur + k_mog2_scan (FM_FLAG_MOG2)
+    bool mog2_small = false;       // ... with k_small_blur in front (small_supported), else k_wide_blur
+    fm_mog2_params mog2{};         // its parameters
+    float* d_mog_state = nullptr;  // [S][15][w][nty * 64] weight, mean, var of the five modes (fm_mog2.hip)
+    uint8_t* d_mog_nm = nullptr;   // [S][w][nty * 64] modes in use
+    uint8_t* d_mog_bg = nullptr;   // [h*w] fm_mog2_background's image
+    std::vector<int64_t> mog_nframes;  // [S] frames each stream's model has seen (advanced at submit)
     bool frame_ccl = false;        // the contour pass as one workgroup per frame (ntiles <= kFrameCclTiles)
     int ntx = 0, nty = 0, ntiles = 0, nnodes = 0;  // nnodes: per batch slot
     int nquota = 0;                                             // nodes of each frame's quota
@@ -528,12 +539,30 @@ static int plan_context(fm_ctx* c, const fm_params& p) {
         const size_t scratch = rgb_scratch_bytes(c->w, (c->h + 63) / 64, (size_t)p.n_streams * p.max_batch);
         c->nslots = scratch > kRgbSlotBytes ? std::min(kSlots, kWideSlots) : kSlots;
     }
+    // FM_FLAG_MOG2: the Gaussian-mixture model (fm_mog2.hip) behind k_small_blur where it takes the image, else
+    // behind k_wide_blur (any odd ksize from 3: its taps are bytes, and ksize 1's single tap is 256), with the tile
+    // machinery of the fused paths behind it.  A slot holds a blur byte per pixel-frame: the wide path's slot count.
+    if (p.flags & FM_FLAG_MOG2) {
+        if (p.flags & FM_FLAG_COLOUR_MOTION)
+            return failf(kNoCtx, FM_ENOTSUP, "the Gaussian-mixture model runs on the gray image (FM_FLAG_COLOUR_MOTION)");
+        if (p.flags & FM_FLAG_KEEP_PLANES)
+            return failf(kNoCtx, FM_ENOTSUP, "the Gaussian-mixture path keeps no gray / blur / delta planes (FM_FLAG_KEEP_PLANES)");
+        if (tiles > 8192) return failf(kNoCtx, FM_ENOTSUP, "the Gaussian-mixture path takes at most 8192 tiles (%d)", tiles);
+        c->mog2_small = small_supported(c->h, c->w, p.ksize);
+        if (!c->mog2_small && !(p.ksize >= 3 && wide_supported(p.ksize, c->coef.data())))
+            return failf(kNoCtx, FM_ENOTSUP, "ksize %d on %d x %d: neither k_small_blur nor k_wide_blur takes it", p.ksize,
+                         c->w, c->h);
+        c->use_mog2 = c->use_fused = c->use_pix = true;
+        c->use_small = c->use_wide = c->use_rgb = false;
+        c->bg_ch = 0;  // no average: the ping-pong planes stay empty
+        c->nslots = std::min(kSlots, kWideSlots);
+    }
     return FM_OK;
 }
 
 // the plan's pixel path by name (fm_plan, MotionEngine.pixel_path)
 static const char* pixel_path_name(const fm_ctx* c) {
-    return c->use_rgb ? "rgb" : c->use_wide ? "wide" : c->use_small ? "small" : c->use_pix ? "pix" : c->use_fused ? "fused" : "pixel";
+    return c->use_mog2 ? "mog2" : c->use_rgb ? "rgb" : c->use_wide ? "wide" : c->use_small ? "small" : c->use_pix ? "pix" : c->use_fused ? "fused" : "pixel";
 }
 
 int fm_plan(const fm_params* prm, struct fm_plan* out) {
@@ -578,12 +607,49 @@ int fm_gaussian_taps(int ksize, int32_t* out) {
     return FM_OK;
 }
 
-int fm_create(fm_ctx** out, const fm_params* prm) {
+int fm_mog2_defaults(fm_mog2_params* out) {
+    if (!out) return failf(kNoCtx, FM_EINVAL, "null argument");
+    *out = fm_mog2_params{500, 16.f, 9.f, 0.9f, 15.f, 4.f, 75.f, 0.05f, 0.5f, 1, -1.0};
+    return FM_OK;
+}
+
+// fm_create_mog2's parameter rules (no device is touched)
+static int check_mog2(const fm_mog2_params& m) {
+    if (m.history < 1) return failf(kNoCtx, FM_EINVAL, "mog2 history %d must be at least 1", m.history);
+    for (float f : {m.var_threshold, m.var_threshold_gen, m.background_ratio, m.var_init, m.var_min, m.var_max,
+                    m.complexity_reduction, m.shadow_tau})
+        if (!std::isfinite(f) || f < 0.f) return failf(kNoCtx, FM_EINVAL, "mog2 parameter %g must be finite and not negative", (double)f);
+    if (m.var_min > m.var_max) return failf(kNoCtx, FM_EINVAL, "mog2 var_min %g above var_max %g", (double)m.var_min, (double)m.var_max);
+    if (!(m.background_ratio > 0.f && m.background_ratio <= 1.f))
+        return failf(kNoCtx, FM_EINVAL, "mog2 background_ratio %g outside (0, 1]", (double)m.background_ratio);
+    if (!(m.learning_rate <= 1.0)) return failf(kNoCtx, FM_EINVAL, "mog2 learning_rate %g above 1", m.learning_rate);
+    return FM_OK;
+}
+
+static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_params* mog2);
+
+int fm_create(fm_ctx** out, const fm_params* prm) { return create_context(out, prm, nullptr); }
+
+int fm_create_mog2(fm_ctx** out, const fm_params* prm, const fm_mog2_params* mog2) {
+    if (!out || !prm) return failf(kNoCtx, FM_EINVAL, "null argument");
+    *out = nullptr;
+    if (mog2)
+        if (int rc = check_mog2(*mog2)) return rc;
+    fm_params p = *prm;
+    p.flags |= FM_FLAG_MOG2;
+    return create_context(out, &p, mog2);
+}
+
+static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_params* mog2) {
     if (!out || !prm) return failf(kNoCtx, FM_EINVAL, "null argument");
     *out = nullptr;
     const fm_params& p = *prm;
     std::unique_ptr<fm_ctx> c(new fm_ctx());
     if (int rc = plan_context(c.get(), p)) return rc;
+    if (c->use_mog2) {
+        if (mog2) c->mog2 = *mog2;
+        else (void)fm_mog2_defaults(&c->mog2);
+    }
 
     fm_ctx* cp = c.get();
     FM_HIP_TRY(cp, hipSetDevice(p.device));
@@ -679,6 +745,8 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
                 (c->use_small && (rc = dalloc(cp, &b.d_sblur, small_scratch_bytes(c->h, c->w, c->nty, frames)))) ||
                 (c->use_wide && (rc = dalloc(cp, &b.d_wblur, wide_scratch_bytes(c->w, c->nty, frames)))) ||
                 (c->use_rgb && (rc = dalloc(cp, &b.d_cblur, rgb_scratch_bytes(c->w, c->nty, frames)))) ||
+                (c->use_mog2 && ((rc = dalloc(cp, &b.d_mblur, wide_scratch_bytes(c->w, c->nty, frames))) ||
+                                 (rc = dalloc(cp, &b.d_alpha, frames)))) ||
                 (rc = dalloc(cp, &b.d_nodes, (size_t)c->nnodes)))
                 return rc;
         }
@@ -694,6 +762,7 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
         FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_overflow, b.h_overflow, 0));
         if (b.d_tflag) FM_HIP_TRY(cp, hipMemset(b.d_tflag, 0, frames * c->ntiles * 8 * sizeof(uint32_t)));
         FM_HIP_TRY(cp, halloc(cp, &b.h_init, S, 0));
+        if (c->use_mog2) FM_HIP_TRY(cp, halloc(cp, &b.h_alpha, frames * sizeof(float), 0));
         if (i < c->nccl && ccl_qmode != 2) {
             if (ccl_qmode == 1) {
                 int lo = 0, hi = 0;
@@ -720,8 +789,10 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&c->dh_err, c->h_err, 0));
     *c->h_err = 0;
     FM_HIP_TRY(cp, hipMemset(c->d_has_keep, 0, S));
-    FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
-    FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
+    if (c->bg_ch) {
+        FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
+        FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
+    }
     auto up = [&](auto** d, const auto& v) -> int {
         int r = dalloc(cp, d, v.size());
         if (r) return r;
@@ -736,6 +807,14 @@ int fm_create(fm_ctx** out, const fm_params* prm) {
     }
     c->bg_init.assign(S, 0);
     c->has_keep.assign(S, 0);
+    if (c->use_mog2) {  // no pixel has a mode yet; modes at or above nmodes are never read
+        if ((rc = dalloc(cp, &c->d_mog_state, mog2_state_floats((int)S, c->w, c->nty))) ||
+            (rc = dalloc(cp, &c->d_mog_nm, mog2_nmodes_bytes((int)S, c->w, c->nty))) ||
+            (rc = dalloc(cp, &c->d_mog_bg, c->work_plane)))
+            return rc;
+        FM_HIP_TRY(cp, hipMemset(c->d_mog_nm, 0, mog2_nmodes_bytes((int)S, c->w, c->nty)));
+        c->mog_nframes.assign(S, 0);
+    }
     if (const char* e = dev_env("FM_DEBUG_SKIP")) c->dbg_skip = std::atoi(e);
     c->serial = dev_env("FM_SERIAL") != nullptr;
     if (dev_env("FM_PTS") && c->use_pix) {
@@ -829,6 +908,13 @@ int fm_reset_stream(fm_ctx* c, int stream) {
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     c->bg_init[stream] = 0;
+    if (c->use_mog2) {
+        const size_t n = mog2_nmodes_bytes(1, c->w, c->nty);
+        FM_HIP_TRY(c, hipSetDevice(c->p.device));
+        FM_HIP_TRY(c, hipMemsetAsync(c->d_mog_nm + (size_t)stream * n, 0, n, c->stream));
+        FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->mog_nframes[stream] = 0;
+    }
     return FM_OK;
 }
 
@@ -993,7 +1079,7 @@ FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool a
     fa.dbits = B.d_dbits;
     fa.tiles = B.d_tiles;
     fa.tflag = B.d_tflag;
-    fa.tflag_waves = (c->use_small || c->use_wide || c->use_rgb) ? 8 : 1;
+    fa.tflag_waves = (c->use_small || c->use_wide || c->use_rgb || c->use_mog2) ? 8 : 1;
     fa.candf = B.d_candf;
     fa.clist = B.d_clist;
     fa.rlist = B.d_rlist;
@@ -1043,6 +1129,33 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
     if (!c->use_pix) {
         FM_HIP_TRY(c, launch_fused(ps, fa, &c->timer));
         c->bg_cur ^= 1;
+        return FM_OK;
+    }
+    if (c->use_mog2) {
+        // The whole batch in one launch pair (a stream's first frame is a frame like any other: no mode fits).
+        // Each frame's learning rate from the stream's frame count, in double as OpenCV computes it; the counts
+        // advance here, so batches in flight chain as the model itself does on the pixel stream.
+        const int S = fa.S;
+        for (int t = 0; t < n; t++)
+            for (int s = 0; s < S; s++) {
+                const int64_t nf = c->mog_nframes[s] + t + 1;
+                const double lr = (c->mog2.learning_rate >= 0 && nf > 1)
+                                      ? c->mog2.learning_rate
+                                      : 1.0 / (double)std::min<int64_t>(2 * nf, (int64_t)c->mog2.history);
+                B.h_alpha[(size_t)t * S + s] = (float)lr;
+            }
+        for (int s = 0; s < S; s++) c->mog_nframes[s] += n;
+        FM_HIP_TRY(c, hipMemcpyAsync(B.d_alpha, B.h_alpha, (size_t)n * S * sizeof(float), hipMemcpyHostToDevice, ps));
+        const Mog2Dev md{c->d_mog_state, c->d_mog_nm, B.d_alpha, c->mog2};
+        FusedArgs fp = fa;
+        fp.init = nullptr;
+        // (each kernel timed on its own, so that the scan appears as mog2_scan under either profile flag)
+        FM_HIP_TRY(c, c->timer.timed(ps, c->mog2_small ? "small_blur" : "wide_blur", [&](uint64_t* ks, uint64_t*) {
+            return c->mog2_small ? launch_small_blur(ps, fp, B.d_mblur, ks) : launch_wide_blur(ps, fp, B.d_mblur, ks);
+        }));
+        FM_HIP_TRY(c, c->timer.timed(ps, "mog2_scan", [&](uint64_t* ks, uint64_t*) {
+            return launch_mog2_scan(ps, fp, md, B.d_mblur, ks);
+        }));
         return FM_OK;
     }
     const bool planes = B.d_planes != nullptr;
@@ -1097,7 +1210,7 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
     // frame's launch included, come from those bits here, at the head of the chain and ahead of the labelling gate.
     // (The small-image, wide-Gaussian and colour scans and k_fused write their own.)  Timed by events, like k_regions
     // (FM_FLAG_PROFILE; never in the pixel-only mode on a contour stream).
-    if (c->use_pix && !c->use_small && !c->use_wide && !c->use_rgb)
+    if (c->use_pix && !c->use_small && !c->use_wide && !c->use_rgb && !c->use_mog2)
         FM_HIP_TRY(c, c->timer.timed(cs, "tile_flags", [&](uint64_t*, uint64_t*) { return launch_tile_flags(cs, fa); }, false));
     if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
         FusedArgs fc = fa;
@@ -1732,6 +1845,7 @@ int fm_retained_count(const fm_ctx* c, int* in_use, int* capacity) {
 
 int fm_read_background(fm_ctx* c, int stream, double* out) {
     if (!c || !out) return failf(c, FM_EINVAL, "null argument");
+    if (c->use_mog2) return failf(c, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_background / fm_mog2_read_model");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     if (!c->bg_init[stream]) return failf(c, FM_ESTATE, "stream %d has no background yet", stream);
@@ -1746,6 +1860,7 @@ int fm_read_background(fm_ctx* c, int stream, double* out) {
 
 int fm_write_background(fm_ctx* c, int stream, const double* in) {
     if (!c || !in) return failf(c, FM_EINVAL, "null argument");
+    if (c->use_mog2) return failf(c, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_write_model");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
@@ -1759,7 +1874,85 @@ int fm_write_background(fm_ctx* c, int stream, const double* in) {
 
 int fm_background_channels(const fm_ctx* c, int* channels) {
     if (!c || !channels) return failf(kNoCtx, FM_EINVAL, "null argument");
+    if (c->use_mog2) return failf(kNoCtx, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_background");
     *channels = c->bg_ch;
+    return FM_OK;
+}
+
+// The Gaussian-mixture model of one stream between the device's column-major planes ([15][x][CS] floats and
+// [x][CS] bytes) and the ABI's row-major [5][h][w] arrays: whole planes are copied and transposed on the host.
+namespace {
+int check_mog2_ctx(fm_ctx* c, int stream) {
+    if (!c->use_mog2) return failf(c, FM_ESTATE, "not a Gaussian-mixture context (FM_FLAG_MOG2)");
+    if (int rc = check_idle(c)) return rc;
+    return check_stream(c, stream);
+}
+}  // namespace
+
+int fm_mog2_read_model(fm_ctx* c, int stream, float* weight, float* mean, float* var, uint8_t* nmodes, int64_t* nframes) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (int rc = check_mog2_ctx(c, stream)) return rc;
+    const int h = c->h, w = c->w, CS = c->nty * 64;
+    const size_t PS = (size_t)w * CS;
+    std::vector<uint8_t> nm(PS);
+    std::vector<float> st(weight || mean || var ? 15 * PS : 0);
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    FM_HIP_TRY(c, hipMemcpy(nm.data(), c->d_mog_nm + (size_t)stream * PS, PS, hipMemcpyDeviceToHost));
+    if (!st.empty())
+        FM_HIP_TRY(c, hipMemcpy(st.data(), c->d_mog_state + (size_t)stream * 15 * PS, 15 * PS * sizeof(float), hipMemcpyDeviceToHost));
+    float* const dst[3] = {weight, mean, var};
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t pix = (size_t)x * CS + y, o = (size_t)y * w + x;
+            const int n = nm[pix];
+            if (nmodes) nmodes[o] = (uint8_t)n;
+            for (int k = 0; k < 3; k++)
+                if (dst[k])
+                    for (int m = 0; m < 5; m++) dst[k][(size_t)m * h * w + o] = m < n ? st[(size_t)(k * 5 + m) * PS + pix] : 0.f;
+        }
+    if (nframes) *nframes = c->mog_nframes[stream];
+    return FM_OK;
+}
+
+int fm_mog2_write_model(fm_ctx* c, int stream, const float* weight, const float* mean, const float* var,
+                        const uint8_t* nmodes, const int64_t* nframes) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (!weight || !mean || !var || !nmodes || !nframes) return failf(c, FM_EINVAL, "null argument");
+    if (int rc = check_mog2_ctx(c, stream)) return rc;
+    if (*nframes < 0) return failf(c, FM_EINVAL, "nframes %lld is negative", (long long)*nframes);
+    const int h = c->h, w = c->w, CS = c->nty * 64;
+    const size_t PS = (size_t)w * CS;
+    for (size_t i = 0; i < (size_t)h * w; i++)
+        if (nmodes[i] > 5) return failf(c, FM_EINVAL, "nmodes %d above 5 at pixel %zu", (int)nmodes[i], i);
+    std::vector<uint8_t> nm(PS, 0);
+    std::vector<float> st(15 * PS, 0.f);
+    const float* const src[3] = {weight, mean, var};
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t pix = (size_t)x * CS + y, o = (size_t)y * w + x;
+            nm[pix] = nmodes[o];
+            for (int k = 0; k < 3; k++)
+                for (int m = 0; m < nmodes[o]; m++) st[(size_t)(k * 5 + m) * PS + pix] = src[k][(size_t)m * h * w + o];
+        }
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    FM_HIP_TRY(c, hipMemcpy(c->d_mog_nm + (size_t)stream * PS, nm.data(), PS, hipMemcpyHostToDevice));
+    FM_HIP_TRY(c, hipMemcpy(c->d_mog_state + (size_t)stream * 15 * PS, st.data(), 15 * PS * sizeof(float), hipMemcpyHostToDevice));
+    c->mog_nframes[stream] = *nframes;
+    c->bg_init[stream] = 1;
+    return FM_OK;
+}
+
+int fm_mog2_background(fm_ctx* c, int stream, uint8_t* out) {
+    if (!c) return failf(kNoCtx, FM_EINVAL, "null context");
+    if (!out) return failf(c, FM_EINVAL, "null argument");
+    if (int rc = check_mog2_ctx(c, stream)) return rc;
+    FM_HIP_TRY(c, hipSetDevice(c->p.device));
+    const Mog2Dev md{c->d_mog_state, c->d_mog_nm, nullptr, c->mog2};
+    FM_HIP_TRY(c, launch_mog2_background(c->stream, md, stream, c->h, c->w, c->nty, c->d_mog_bg));
+    FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_mog_bg, c->work_plane, hipMemcpyDeviceToHost, c->stream));
+    FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FM_OK;
 }
 

@@ -267,6 +267,24 @@ bool rgb_supported(int h, int w, int ksize);
 int rgb_lds_bytes(int ksize);
 size_t rgb_scratch_bytes(int w, int nty, size_t frames);
 hipError_t launch_rgb(hipStream_t st, const FusedArgs& a, uint8_t* cblur, uint64_t* ks_blur, uint64_t* ks_scan);
+// the Gaussian-mixture background model (fm_mog2.hip, FM_FLAG_MOG2): the blur of launch_small or launch_wide_blur,
+// then k_mog2_scan (k_small_scan's job shape with the pixel's five modes in registers) in place of the average's
+// scan.  The state is updated in place: float planes [S][15][x][nty * 64] (field = 5 * {weight, mean, var} +
+// mode; mog2_state_floats) and uint8 nmodes [S][x][nty * 64] (mog2_nmodes_bytes); alphaT: the learning rate of
+// each of the batch's a.T * a.S frames, [T][S]
+struct Mog2Dev {
+    float* state;
+    uint8_t* nmodes;
+    const float* alphaT;
+    fm_mog2_params prm;
+};
+size_t mog2_state_floats(int S, int w, int nty);
+size_t mog2_nmodes_bytes(int S, int w, int nty);
+hipError_t launch_small_blur(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint64_t* ks_blur);
+hipError_t launch_wide_blur(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks_blur);
+hipError_t launch_mog2_scan(hipStream_t st, const FusedArgs& a, const Mog2Dev& m, const uint8_t* blur, uint64_t* ks_scan);
+// getBackgroundImage of stream s into out [h][w] (device memory)
+hipError_t launch_mog2_background(hipStream_t st, const Mog2Dev& m, int s, int h, int w, int nty, uint8_t* out);
 // a.tflag (one word per tile-frame) of all a.T * a.S frames from a.bits: after the 64 x 64 tile pixel kernels
 // (launch_pix), ahead of either contour pass below
 hipError_t launch_tile_flags(hipStream_t st, const FusedArgs& a);

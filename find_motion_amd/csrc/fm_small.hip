@@ -223,13 +223,19 @@ size_t small_scratch_bytes(int h, int w, int nty, size_t frames) { return frames
 // frames [a.t_begin, a.t_end) of the batch: blur of every frame in parallel, then the scan; a.init may mark
 // first frames (bg := blur at t_begin).  ks1 / ks2: launch stamps of the two kernels (or nullptr)
 hipError_t launch_small(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint64_t* ks1, uint64_t* ks2) {
+    (void)launch_small_blur(st, a, sblur, ks1);
+    return launch_small_scan(st, a, sblur, ks2);
+}
+
+// the blur alone (the Gaussian-mixture scan of fm_mog2.hip follows it too)
+hipError_t launch_small_blur(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint64_t* ks) {
     const int CS = a.nty * 64;
     const int nf = (a.t_end - a.t_begin) * a.S;
     const size_t lds = sm::blur_lds_bytes(a.h, a.w, a.ksize >> 1);
     FusedArgs b = a;
-    b.kstamp = ks1;
+    b.kstamp = ks;
     hipLaunchKernelGGL(sm::k_small_blur, dim3(nf), dim3(sm::BT), lds, st, b, sblur, CS);
-    return launch_small_scan(st, a, sblur, ks2);
+    return hipGetLastError();
 }
 
 // the scan alone, over blur bytes [F][x][a.nty * 64] of frames [a.t_begin, a.t_end) that are already written and

@@ -294,6 +294,12 @@ size_t wide_scratch_bytes(int w, int nty, size_t frames) { return frames * (size
 // frames [a.t_begin, a.t_end) of the batch: blur of every frame in parallel, then the scan; a.init may mark
 // first frames (bg := blur at t_begin).  ks1 / ks2: launch stamps of the two kernels (or nullptr)
 hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks1, uint64_t* ks2) {
+    if (hipError_t e = launch_wide_blur(st, a, wblur, ks1); e != hipSuccess) return e;
+    return launch_small_scan(st, a, wblur, ks2);
+}
+
+// the blur alone (the Gaussian-mixture scan of fm_mog2.hip follows it too)
+hipError_t launch_wide_blur(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks1) {
     const wd::Geo g = wd::make_geo(a.ksize, a.coef);
     if (g.nt == 0) return hipErrorInvalidValue;
     const int nf = (a.t_end - a.t_begin) * a.S;
@@ -316,8 +322,7 @@ hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint6
         (void)hipFuncSetAttribute((const void*)wd::k_wide_blur<128>, hipFuncAttributeMaxDynamicSharedMemorySize, g.lds);
         hipLaunchKernelGGL(wd::k_wide_blur<128>, grid, dim3(128), g.lds, st, b, wblur, L);
     }
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    return launch_small_scan(st, a, wblur, ks2);
+    return hipGetLastError();
 }
 
 }  // namespace fm

@@ -65,7 +65,13 @@ it that stage is off), yolo_precision ("f32", the default, or "f16": the network
 half precision on the f16 matrix instructions; default $FM_YOLO_PRECISION),
 colour_motion (the chain per colour channel, the TODO at the top of find_motion.py:
 a pixel moves where any of B, G, R changes by more than the threshold, ref_frame is
-(h, w, 3), and frame.gray / blur / frame_delta are None).
+(h, w, 3), and frame.gray / blur / frame_delta are None), background_model
+("average", the reference's, or "mog2": cv2.createBackgroundSubtractorMOG2's
+Gaussian mixture applied to frame.blur in place of the running average, which
+learns a flickering or swaying background instead of firing on it; tuned with
+mog2_history, mog2_var_threshold, mog2_detect_shadows, mog2_learning_rate;
+threshold and avg are then unused, ref_frame is the background image as float
+(h, w), and frame.gray / blur / frame_delta are None).
 
 There is no CPU fallback: without the HIP library this module raises
 NativeLibraryMissing at VideoMotion construction.
@@ -250,6 +256,16 @@ class VideoFrame:
             self._dev = None
 
 
+def mog2_engine_params(background_model, history=500, var_threshold=16.0, detect_shadows=True, learning_rate=-1.0):
+    """MotionEngine's mog2 argument of VideoMotion's background_model and mog2_* arguments: None for "average"."""
+    if background_model == "average":
+        return None
+    if background_model != "mog2":
+        raise ValueError(f"background_model {background_model!r}: average or mog2")
+    return {"history": int(history), "var_threshold": float(var_threshold), "detect_shadows": bool(detect_shadows),
+            "learning_rate": float(learning_rate)}
+
+
 class VideoMotion:
     """fm.py:294-926 with the per-frame chain on the GPU (see the module docstring)."""
 
@@ -269,7 +285,9 @@ class VideoMotion:
                  stream: int = 0, keep_planes: bool = None, cascade_dir: str = None,
                  pipeline_depth: int = None, gpu_decode: bool = None, gpu_encode: bool = None,
                  contour_points: bool = False, yolo_dir: str = None, yolo_precision: str = None,
-                 resident_cache: bool = False, colour_motion: bool = False) -> None:
+                 resident_cache: bool = False, colour_motion: bool = False,
+                 background_model: str = "average", mog2_history: int = 500, mog2_var_threshold: float = 16.0,
+                 mog2_detect_shadows: bool = True, mog2_learning_rate: float = -1.0) -> None:
         self.filename = filename
         if self.filename is None and capture is None:
             raise Exception("Filename required")
@@ -329,7 +347,13 @@ class VideoMotion:
         # the gray / blur / delta planes have no 3-channel form, so show and debug logging do not request them and
         # frame.gray / frame.blur / frame.frame_delta are None (thresh and contours as usual)
         self.colour_motion = bool(colour_motion)
-        self.keep_planes = ((show or self.debug) and not self.colour_motion) if keep_planes is None else bool(keep_planes)
+        # background_model "mog2": the Gaussian mixture in place of the running average (MotionEngine's mog2); no
+        # planes on that path either
+        self.background_model = background_model
+        self.mog2 = mog2_engine_params(background_model, mog2_history, mog2_var_threshold, mog2_detect_shadows,
+                                       mog2_learning_rate)
+        no_planes = self.colour_motion or self.mog2 is not None
+        self.keep_planes = ((show or self.debug) and not no_planes) if keep_planes is None else bool(keep_planes)
         self._engine = engine
         self._own_engine = engine is None
         self._pipe = None  # BatchFeeder iterator of read() (single-stream engine)
@@ -427,6 +451,7 @@ class VideoMotion:
                                         device=self.device, contour_area=self.area_filter,
                                         **({"contour_points": True} if self.contour_points else {}),
                                         **({"colour_motion": True} if self.colour_motion else {}),
+                                        **({"mog2": self.mog2} if self.mog2 is not None else {}),
                                         # a box wider than the frame enlarges it, as imutils.resize does
                                         **({"area_upscale": True} if self.box_size > self.frame_width else {}))
         self._log_pixel_path()
@@ -521,6 +546,8 @@ class VideoMotion:
         eng = self._engine
         if eng is None or not eng.initialized(self._stream):
             return None
+        if getattr(eng, "mog2", None) is not None:  # the mixture's background image (getBackgroundImage)
+            return eng.mog2_background(self._stream).astype(np.float64)
         return eng.background(self._stream)
 
     @ref_frame.setter
@@ -972,15 +999,20 @@ class StreamGroup:
         show = kwargs.get("show", False)
         dbg = kwargs.get("log_level", logging.INFO) == logging.DEBUG
         colour = bool(kwargs.get("colour_motion"))  # no planes with it (VideoMotion.__init__)
+        mog2 = mog2_engine_params(kwargs.get("background_model", "average"), kwargs.get("mog2_history", 500),
+                                  kwargs.get("mog2_var_threshold", 16.0), kwargs.get("mog2_detect_shadows", True),
+                                  kwargs.get("mog2_learning_rate", -1.0))  # nor with the mixture model
         self.batch = max(1, int(batch))
         make = engine if engine is not None else MotionEngine  # engine: a factory with MotionEngine's signature
         mbs = kwargs.get("min_box_scale", VideoMotion.DEFAULT_MIN_BOX_SCALE)
         area_filter = int(W * H / 2 * (box / W)) < int(math.pow(box / mbs, 2))  # as _load_video decides
         self.engine = make(n_streams=S, src_w=W, src_h=H, box_size=box, ksize=make_gaussian_size(box, blur_scale),
                            threshold=kwargs.get("threshold", 7), avg=kwargs.get("avg", 0.1), max_batch=self.batch,
-                           keep_planes=(show or dbg) and not colour, device=device, contour_area=area_filter,
+                           keep_planes=(show or dbg) and not colour and mog2 is None, device=device,
+                           contour_area=area_filter,
                            **({"contour_points": True} if kwargs.get("contour_points") else {}),
                            **({"colour_motion": True} if colour else {}),
+                           **({"mog2": mog2} if mog2 is not None else {}),
                            **({"area_upscale": True} if box > W else {}))
         self.videos = [VideoMotion(filename=f, capture=c, engine=self.engine, stream=s, batch=self.batch, **kwargs)
                        for s, (f, c) in enumerate(zip(self.filenames, caps))]

@@ -66,6 +66,17 @@ extern "C" {
                                        (fm_background_channels).  FM_ENOTSUP with ksize above 49, more than 8,192
                                        tiles, or FM_FLAG_KEEP_PLANES (FM_PLANE_SMALL still works).  Off: no
                                        kernel, buffer, result or status differs */
+#define FM_FLAG_MOG2 0x80u /* a Gaussian-mixture background model in place of the running average: what
+                              `fgmask = cv2.createBackgroundSubtractorMOG2(...).apply(frame.blur)` gives in
+                              find_diff (fm.py:638-662), one channel, five mixtures.  Resize, gray, GaussianBlur and
+                              the keep-mask as always; then a pixel is set where the mask value is 255 (a shadow, 127,
+                              is not foreground); dilation, contours, boxes and points as always.  threshold and avg
+                              are not used.  A pixel that alternates between two values is learnt and stays silent.
+                              The kernels `small_blur` or `wide_blur` + `mog2_scan`; fm_plan says "mog2".
+                              Parameters: fm_create_mog2 (fm_create takes the defaults).  FM_ENOTSUP with
+                              FM_FLAG_COLOUR_MOTION, FM_FLAG_KEEP_PLANES, more than 8,192 tiles, or a ksize neither
+                              blur takes (ksize 1 on more than 16,384 work pixels).  Off: no kernel, buffer, result
+                              or status differs */
 
 /* planes for fm_read_plane */
 #define FM_PLANE_GRAY 0  /* VideoFrame.gray        (fm.py:493) */
@@ -110,6 +121,27 @@ int fm_abi_version(void);
 int fm_create(fm_ctx** out, const fm_params* params);
 void fm_destroy(fm_ctx* ctx);
 
+/* Parameters of the Gaussian-mixture background model (FM_FLAG_MOG2): BackgroundSubtractorMOG2's, with OpenCV's
+ * defaults from fm_mog2_defaults.  nmixtures is fixed at 5. */
+typedef struct fm_mog2_params {
+    int history;                /* 500: frames until the learning rate settles at 1 / history */
+    float var_threshold;        /* 16 (Tb): squared distance in variances below which a mode explains the pixel */
+    float var_threshold_gen;    /* 9 (Tg): ... below which the pixel updates the mode */
+    float background_ratio;     /* 0.9 (TB): summed weight of the modes that count as background */
+    float var_init;             /* 15 */
+    float var_min;              /* 4 */
+    float var_max;              /* 75 */
+    float complexity_reduction; /* 0.05 (CT): prior that prunes weak modes */
+    float shadow_tau;           /* 0.5: darkest shadow as a fraction of the background */
+    int detect_shadows;         /* 1: mark shadows 127 (not foreground) */
+    double learning_rate;       /* -1: automatic, 1 / min(2 nframes, history); else the rate from the 2nd frame on */
+} fm_mog2_params;
+int fm_mog2_defaults(fm_mog2_params* out);
+/* fm_create with FM_FLAG_MOG2 set and these parameters (NULL: the defaults, which is what fm_create gives when the
+ * flag is set).  FM_EINVAL, before any device call, for history < 1, a non-finite or negative float, var_min >
+ * var_max, background_ratio outside (0, 1] or learning_rate > 1; FM_ENOTSUP as the flag describes. */
+int fm_create_mog2(fm_ctx** out, const fm_params* params, const fm_mog2_params* mog2);
+
 /* What fm_create would set up for params, without touching a device: the same validation (and error codes)
  * and the same selection, by the same code.  pixel_path names the kernels of the per-pixel chain:
  *   "small"  k_small_blur + k_small_scan (work images of at most 16,384 pixels, ksize up to 49)
@@ -118,6 +150,7 @@ void fm_destroy(fm_ctx* ctx);
  *   "wide"   k_wide_blur + k_small_scan (ksize above 49, more than 16 and at most 8,192 tiles of 64 x 64,
  *            no FM_FLAG_KEEP_PLANES)
  *   "rgb"    k_rgb_blur + k_rgb_scan (FM_FLAG_COLOUR_MOTION: ksize up to 49, at most 8,192 tiles)
+ *   "mog2"   k_small_blur or k_wide_blur + k_mog2_scan (FM_FLAG_MOG2: at most 8,192 tiles)
  *   "pixel"  one k_pixel launch per frame and the pixel-level CCL: one batch in flight
  * (The struct has no typedef: C keeps struct tags apart from function names, not typedef names.) */
 struct fm_plan {
@@ -154,7 +187,7 @@ int fm_work_size(const fm_ctx* ctx, int* h, int* w);
 int fm_set_mask(fm_ctx* ctx, int stream, const uint8_t* keep_hw);
 
 /* Forget the background model: the next frame re-initialises it
- * (VideoMotion.ref_frame = None, fm.py:414, 651-652). */
+ * (VideoMotion.ref_frame = None, fm.py:414, 651-652).  With FM_FLAG_MOG2: nmodes = 0 everywhere and nframes = 0. */
 int fm_reset_stream(fm_ctx* ctx, int stream);
 
 /* Batches that may be in flight at once (fm_submit before fm_wait): the contour
@@ -244,6 +277,17 @@ int fm_read_background(fm_ctx* ctx, int stream, double* out);
 int fm_write_background(fm_ctx* ctx, int stream, const double* in);
 /* Doubles per work pixel of the background: 1, or 3 with FM_FLAG_COLOUR_MOTION. */
 int fm_background_channels(const fm_ctx* ctx, int* channels);
+/* On a context with FM_FLAG_MOG2 the three calls above give FM_ESTATE (there is no average); the calls below give
+ * FM_ESTATE on any other context, and while a batch is in flight.
+ * The model of one stream: weight, mean, var [5][h][w] floats row-major, nmodes [h][w] (0..5), nframes the frames
+ * the stream has seen.  Entries at mode >= nmodes read as 0 and are ignored when written; a written nmodes above 5
+ * is FM_EINVAL.  For tests, and for carrying a model from one file of a camera to the next. */
+int fm_mog2_read_model(fm_ctx* ctx, int stream, float* weight, float* mean, float* var, uint8_t* nmodes, int64_t* nframes);
+int fm_mog2_write_model(fm_ctx* ctx, int stream, const float* weight, const float* mean, const float* var,
+                        const uint8_t* nmodes, const int64_t* nframes);
+/* getBackgroundImage of one stream, h*w bytes: the weighted mean of the strongest modes up to background_ratio,
+ * 0 where a pixel has no mode yet. */
+int fm_mog2_background(fm_ctx* ctx, int stream, uint8_t* out_hw);
 
 /* Launch on the caller's HIP stream (hipStream_t) instead of the context's own
  * stream; NULL restores the context stream.  FM_ESTATE while a batch is in flight.
