@@ -16,7 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "fm_internal.h"
+#include "fm_scan.h"
 #include "fm_roi.h"
 
 namespace fm {
@@ -34,6 +34,33 @@ using ResizeMode = AreaMode::Kind;
 constexpr fm_ctx* kNoCtx = nullptr;  // a failure before a context exists: fm_last_error(nullptr) has it
 
 }  // namespace
+
+// The pixel stage of a context, and what follows from it.
+enum class PixelPath { PerFrame, Fused, Pix, Small, Wide, Rgb, Mog2 };
+using ScanLaunch = hipError_t (*)(hipStream_t, const FusedArgs&, uint8_t*, uint64_t*, uint64_t*);
+struct PathTraits {
+    const char* name;  // fm_plan's pixel_path
+    bool tiles;        // the tile machinery sits behind it: batch slots, tile CCL (else one launch per frame, pixel CCL)
+    bool bits;         // it writes threshold bits for the dilating contour pass (else k_fused dilates itself)
+    bool scan;         // a blur + scan path (fm_scan.h): it writes its own tile flags, 8 words per tile-frame, and
+                       // k_tile_flags is not run for it
+    int bg_ch;         // doubles per work pixel of the background: [h][w][3] on a colour context, none for a mixture
+    int blur_ch;       // channels of a slot's blur scratch
+    ScanLaunch launch;           // a scan path's blur + scan pair (Mog2 launches its two kernels itself)
+    const char* timer[2][3];     // and its timer names, steady / init launch: blur, scan, the pair under events
+};
+constexpr PathTraits kPathTraits[] = {
+    {"pixel", false, false, false, 1, 0, nullptr, {}},
+    {"fused", true, false, false, 1, 0, nullptr, {}},
+    {"pix", true, true, false, 1, 0, nullptr, {}},
+    {"small", true, true, true, 1, 1, launch_small,
+     {{"small_blur", "small_scan", "small"}, {"small_blur_init", "small_scan_init", "small_init"}}},
+    {"wide", true, true, true, 1, 1, launch_wide,
+     {{"wide_blur", "wide_scan", "wide"}, {"wide_blur_init", "wide_scan_init", "wide_init"}}},
+    {"rgb", true, true, true, 3, 3, launch_rgb,
+     {{"rgb_blur", "rgb_scan", "rgb"}, {"rgb_blur_init", "rgb_scan_init", "rgb_init"}}},
+    {"mog2", true, true, true, 0, 1, nullptr, {}},
+};
 
 // One batch's device results.  The fused paths keep kSlots slots: the pixel
 // kernels run in submission order on the pixel stream (the background
@@ -59,10 +86,7 @@ struct BatchSlot {
     uint8_t* d_work = nullptr;      // resized BGR [T][S][h][w][3] (mode D)
     uint8_t* d_planes = nullptr;    // [3][T][S][h*w] gray, blur, frame_delta (FM_FLAG_KEEP_PLANES)
     uint64_t* d_bits = nullptr;     // threshold bit rows (k_pix output)
-    uint8_t* d_sblur = nullptr;     // small work images: blur bytes [T*S][w][nty * 64] (k_small_blur -> k_small_scan)
-    uint8_t* d_wblur = nullptr;     // wide Gaussians: blur bytes, same layout (k_wide_blur -> k_small_scan)
-    uint8_t* d_cblur = nullptr;     // colour motion: blur bytes [T*S][3][w][nty * 64] (k_rgb_blur -> k_rgb_scan)
-    uint8_t* d_mblur = nullptr;     // Gaussian mixture: blur bytes [T*S][w][nty * 64] (k_small_blur / k_wide_blur -> k_mog2_scan)
+    uint8_t* d_blur = nullptr;      // blur + scan paths: blur bytes [T*S][channels][w][nty * 64] between the two kernels
     float* d_alpha = nullptr;       // Gaussian mixture: the learning rate of each frame [T][S]
     float* h_alpha = nullptr;       // and its page-locked staging
     uint64_t* d_dbits = nullptr;    // dilated bit rows = VideoFrame.thresh
@@ -146,15 +170,9 @@ struct fm_ctx {
     size_t dev_bytes = 0;     // device bytes the context holds now (fm_footprint)
     size_t pinned_bytes = 0;  // and its page-locked host allocations
     std::unordered_map<const void*, size_t> dev_sizes, pin_sizes;  // every buffer of either kind it owns -> its bytes
-    bool use_fused = false;
-    bool use_pix = false;          // k_pix + dilating tile CCL (else k_fused dilates itself)
-    bool use_small = false;        // the pixel stage as k_small_blur + k_small_scan (small work images)
-    bool use_wide = false;         // the pixel stage as k_wide_blur + k_small_scan (ksize above k_fused's)
-    bool use_rgb = false;          // the pixel stage as k_rgb_blur + k_rgb_scan (FM_FLAG_COLOUR_MOTION)
-    int bg_ch = 1;                 // doubles per work pixel of the background: 3 on a colour context, [h][w][3];
-                                   // 0 on a Gaussian-mixture context
-    bool use_mog2 = false;         // the pixel stage as k_small_blur / k_wide_blur + k_mog2_scan (FM_FLAG_MOG2)
-    bool mog2_small = false;       // ... with k_small_blur in front (small_supported), else k_wide_blur
+    PixelPath path = PixelPath::PerFrame;  // decided once by plan_context; everything else reads its traits
+    const PathTraits& traits() const { return kPathTraits[(int)path]; }
+    bool small_blur = false;       // Mog2: k_small_blur in front of the scan (small_supported), else k_wide_blur
     fm_mog2_params mog2{};         // its parameters
     float* d_mog_state = nullptr;  // [S][15][w][nty * 64] weight, mean, var of the five modes (fm_mog2.hip)
     uint8_t* d_mog_nm = nullptr;   // [S][w][nty * 64] modes in use
@@ -326,7 +344,7 @@ int relabel_frame(fm_ctx* c, BatchSlot& B, size_t f, std::vector<int32_t>& out, 
     hipStream_t st = c->aux_stream;
     int32_t* dcnt = B.d_count + f;  // this frame's contour counter (the batch is finished)
     const uint8_t* mask = c->d_mask + f * c->work_plane;  // per-frame path: the batch's dilated masks
-    if (c->use_fused) {
+    if (c->traits().tiles) {
         FM_HIP_TRY(c, launch_expand_bits(st, B.d_dbits + f * c->ntiles * 64, B.d_candf + f * c->ntiles, c->d_mask, c->h,
                                       c->w, c->ntx));
         mask = c->d_mask;
@@ -369,8 +387,8 @@ int contour_areas(fm_ctx* c, BatchSlot& B, size_t F) {
     hipStream_t st = c->aux_stream;
     std::vector<int32_t> a2(n);
     FM_HIP_TRY(c, hipMemcpyAsync(c->d_area, jobs.data(), n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    FM_HIP_TRY(c, launch_contour_area(st, c->use_fused ? B.d_dbits : nullptr, c->use_fused ? B.d_candf : nullptr,
-                                   c->use_fused ? nullptr : c->d_mask, c->ntiles, c->ntx, c->h, c->w, c->d_area, (int)n,
+    FM_HIP_TRY(c, launch_contour_area(st, c->traits().tiles ? B.d_dbits : nullptr, c->traits().tiles ? B.d_candf : nullptr,
+                                   c->traits().tiles ? nullptr : c->d_mask, c->ntiles, c->ntx, c->h, c->w, c->d_area, (int)n,
                                    c->d_area + n * 3));
     FM_HIP_TRY(c, hipMemcpyAsync(a2.data(), c->d_area + n * 3, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FM_HIP_TRY(c, hipStreamSynchronize(st));
@@ -412,7 +430,7 @@ int contour_points(fm_ctx* c, BatchSlot& B, size_t F) {
     int32_t* d_res = c->d_trace + n * 9;
     int32_t* d_err = c->d_trace + n * 12;
     hipStream_t st = c->aux_stream;
-    TraceArgs ta{c->use_fused ? B.d_dbits : nullptr, c->use_fused ? B.d_candf : nullptr, c->use_fused ? nullptr : c->d_mask,
+    TraceArgs ta{c->traits().tiles ? B.d_dbits : nullptr, c->traits().tiles ? B.d_candf : nullptr, c->traits().tiles ? nullptr : c->d_mask,
                  c->ntiles, c->ntx, c->h, c->w, d_jobs, d_jobs + n * 8,
                  {(int)path[0].size(), (int)path[1].size(), (int)path[2].size(), (int)path[3].size()}, d_res, nullptr, d_err};
     std::vector<int32_t> res(n * 3);
@@ -502,67 +520,57 @@ static int plan_context(fm_ctx* c, const fm_params& p) {
     if (pixel_lds_bytes(p.ksize) > 160 * 1024) return failf(kNoCtx, FM_ENOTSUP, "ksize %d too large for the LDS tile", p.ksize);
 
     const int tiles = ((c->w + 63) / 64) * ((c->h + 63) / 64);
-    c->use_fused = p.ksize <= fused_max_ksize() && fused_lds_bytes(p.ksize) <= 160 * 1024 &&
-                   tiles <= 8192;  // region labelling holds the tile grid in LDS
-    // small work images (mode D: 1080p -> 100 x 56), k <= 49 (use_fused; k > 49 goes to the per-frame k_pixel, or
-    // to the wide path, which no image this small reaches): frame-parallel blur + per-pixel scan
-    // (fm_small.hip; mode D 634 -> 746 k frames/s, round 5), unless the caller keeps the gray / blur /
-    // delta planes (k_pix writes them).  Both it and k_pix write threshold bits for the dilating contour pass.
-    c->use_small = c->use_fused && (size_t)c->h * c->w >= 16 && !(p.flags & FM_FLAG_KEEP_PLANES) &&
-                   small_supported(c->h, c->w, p.ksize) && dev_env("FM_NO_PIX") == nullptr;
-    if (const char* e = dev_env("FM_SMALL")) c->use_small = c->use_small && std::atoi(e) != 0;
-    c->use_pix = c->use_small || (c->use_fused && pix_supported(p.ksize) && (size_t)c->h * c->w >= 16 &&
-                                  pix_lds_bytes(p.ksize) <= 160 * 1024 && dev_env("FM_NO_PIX") == nullptr);
+    const bool planes = (p.flags & FM_FLAG_KEEP_PLANES) != 0, px16 = (size_t)c->h * c->w >= 16;
+    const bool fused = p.ksize <= fused_max_ksize() && fused_lds_bytes(p.ksize) <= 160 * 1024 &&
+                       tiles <= 8192;  // region labelling holds the tile grid in LDS
+    // small work images (mode D: 1080p -> 100 x 56), k <= 49 (k > 49 goes to the per-frame k_pixel, or to the wide
+    // path, which no image this small reaches): frame-parallel blur + per-pixel scan (fm_small.hip; mode D
+    // 634 -> 746 k frames/s, round 5), unless the caller keeps the gray / blur / delta planes (k_pix writes them).
+    bool small = fused && px16 && !planes && small_supported(c->h, c->w, p.ksize) && dev_env("FM_NO_PIX") == nullptr;
+    if (const char* e = dev_env("FM_SMALL")) small = small && std::atoi(e) != 0;
+    const bool pix = fused && pix_supported(p.ksize) && px16 && pix_lds_bytes(p.ksize) <= 160 * 1024 &&
+                     dev_env("FM_NO_PIX") == nullptr;
     // Gaussian sizes above k_fused's on more than kFrameCclTiles tiles (the reference's default blur scale with
     // a raised box: -B 1920 gives k = 97): frame-parallel strip blur + the same scan (fm_wide.hip), with the
     // tile machinery of the fused paths behind it.  Kept planes stay with the per-frame kernel, as above.
-    c->use_wide = p.ksize > fused_max_ksize() && !(p.flags & FM_FLAG_KEEP_PLANES) && tiles > kFrameCclTiles &&
-                  tiles <= 8192 && wide_supported(p.ksize, c->coef.data());
-    if (const char* e = dev_env("FM_WIDE")) c->use_wide = c->use_wide && std::atoi(e) != 0;
-    if (c->use_wide) c->use_fused = c->use_pix = true;
-    // a slot of the wide path also holds 1 B per pixel-frame of blur bytes (0.53 GB at 1080p x 256 frames, 2.1 GB
-    // at 2160p): kWideSlots of them
-    c->nslots = c->use_wide ? std::min(kSlots, kWideSlots) : c->use_fused ? kSlots : 1;
+    bool wide = p.ksize > fused_max_ksize() && !planes && tiles > kFrameCclTiles && tiles <= 8192 &&
+                wide_supported(p.ksize, c->coef.data());
+    if (const char* e = dev_env("FM_WIDE")) wide = wide && std::atoi(e) != 0;
     // FM_FLAG_COLOUR_MOTION: the chain on the three channels (fm_rgb.hip) at any work size of at most 8,192 tiles
     // and any ksize up to 49, with the tile machinery of the fused paths behind it.  The gray, blur and delta
-    // planes have no 3-channel form.  A slot also holds 3 B per pixel-frame of blur bytes: where that is more than
-    // kRgbSlotBytes a slot (1080p from 43 frames a batch on), kWideSlots of them, as on the wide path.
-    if (p.flags & FM_FLAG_COLOUR_MOTION) {
-        if (p.flags & FM_FLAG_KEEP_PLANES)
+    // planes have no 3-channel form.
+    const bool colour = (p.flags & FM_FLAG_COLOUR_MOTION) != 0, mog2 = (p.flags & FM_FLAG_MOG2) != 0;
+    if (colour) {
+        if (planes)
             return failf(kNoCtx, FM_ENOTSUP, "colour motion keeps no gray / blur / delta planes (FM_FLAG_KEEP_PLANES)");
         if (!rgb_supported(c->h, c->w, p.ksize))
             return failf(kNoCtx, FM_ENOTSUP, "colour motion takes ksize up to 49 and at most 8192 tiles (ksize %d, %d tiles)",
                          p.ksize, tiles);
-        c->use_rgb = c->use_fused = c->use_pix = true;
-        c->use_small = c->use_wide = false;
-        c->bg_ch = 3;
-        const size_t scratch = rgb_scratch_bytes(c->w, (c->h + 63) / 64, (size_t)p.n_streams * p.max_batch);
-        c->nslots = scratch > kRgbSlotBytes ? std::min(kSlots, kWideSlots) : kSlots;
     }
     // FM_FLAG_MOG2: the Gaussian-mixture model (fm_mog2.hip) behind k_small_blur where it takes the image, else
     // behind k_wide_blur (any odd ksize from 3: its taps are bytes, and ksize 1's single tap is 256), with the tile
-    // machinery of the fused paths behind it.  A slot holds a blur byte per pixel-frame: the wide path's slot count.
-    if (p.flags & FM_FLAG_MOG2) {
-        if (p.flags & FM_FLAG_COLOUR_MOTION)
+    // machinery of the fused paths behind it.
+    if (mog2) {
+        if (colour)
             return failf(kNoCtx, FM_ENOTSUP, "the Gaussian-mixture model runs on the gray image (FM_FLAG_COLOUR_MOTION)");
-        if (p.flags & FM_FLAG_KEEP_PLANES)
+        if (planes)
             return failf(kNoCtx, FM_ENOTSUP, "the Gaussian-mixture path keeps no gray / blur / delta planes (FM_FLAG_KEEP_PLANES)");
         if (tiles > 8192) return failf(kNoCtx, FM_ENOTSUP, "the Gaussian-mixture path takes at most 8192 tiles (%d)", tiles);
-        c->mog2_small = small_supported(c->h, c->w, p.ksize);
-        if (!c->mog2_small && !(p.ksize >= 3 && wide_supported(p.ksize, c->coef.data())))
+        c->small_blur = small_supported(c->h, c->w, p.ksize);
+        if (!c->small_blur && !(p.ksize >= 3 && wide_supported(p.ksize, c->coef.data())))
             return failf(kNoCtx, FM_ENOTSUP, "ksize %d on %d x %d: neither k_small_blur nor k_wide_blur takes it", p.ksize,
                          c->w, c->h);
-        c->use_mog2 = c->use_fused = c->use_pix = true;
-        c->use_small = c->use_wide = c->use_rgb = false;
-        c->bg_ch = 0;  // no average: the ping-pong planes stay empty
-        c->nslots = std::min(kSlots, kWideSlots);
     }
+    c->path = mog2 ? PixelPath::Mog2 : colour ? PixelPath::Rgb : wide ? PixelPath::Wide : small ? PixelPath::Small
+              : pix ? PixelPath::Pix : fused ? PixelPath::Fused : PixelPath::PerFrame;
+    // A slot of a scan path also holds its blur bytes, 1 B per pixel-frame (0.53 GB at 1080p x 256 frames, 2.1 GB at
+    // 2160p) on the wide and mixture paths: kWideSlots of them.  A colour slot holds 3 B per pixel-frame: kWideSlots
+    // where that is more than kRgbSlotBytes (1080p from 43 frames a batch on).  The small path's are small.
+    const bool few = c->path == PixelPath::Wide || c->path == PixelPath::Mog2 ||
+                     (c->path == PixelPath::Rgb &&
+                      scan_scratch_bytes(c->w, (c->h + 63) / 64, (size_t)p.n_streams * p.max_batch, 3) > kRgbSlotBytes);
+    c->nslots = !c->traits().tiles ? 1 : few ? std::min(kSlots, kWideSlots) : kSlots;
     return FM_OK;
-}
-
-// the plan's pixel path by name (fm_plan, MotionEngine.pixel_path)
-static const char* pixel_path_name(const fm_ctx* c) {
-    return c->use_mog2 ? "mog2" : c->use_rgb ? "rgb" : c->use_wide ? "wide" : c->use_small ? "small" : c->use_pix ? "pix" : c->use_fused ? "fused" : "pixel";
 }
 
 int fm_plan(const fm_params* prm, struct fm_plan* out) {
@@ -574,7 +582,7 @@ int fm_plan(const fm_params* prm, struct fm_plan* out) {
     out->work_w = c.w;
     out->tiles = ((c.w + 63) / 64) * ((c.h + 63) / 64);
     out->max_inflight = c.nslots;
-    std::snprintf(out->pixel_path, sizeof out->pixel_path, "%s", pixel_path_name(&c));
+    std::snprintf(out->pixel_path, sizeof out->pixel_path, "%s", c.traits().name);
     return FM_OK;
 }
 
@@ -646,7 +654,7 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
     const fm_params& p = *prm;
     std::unique_ptr<fm_ctx> c(new fm_ctx());
     if (int rc = plan_context(c.get(), p)) return rc;
-    if (c->use_mog2) {
+    if (c->path == PixelPath::Mog2) {
         if (mog2) c->mog2 = *mog2;
         else (void)fm_mog2_defaults(&c->mog2);
     }
@@ -697,11 +705,11 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
     // runtime multiplexes streams onto GPU_MAX_HW_QUEUES (4) hardware queues in order,
     // and a contour kernel queued ahead of a pixel kernel on a shared queue stalls it
     for (int i = 0; i < 2; i++)
-        if ((rc = dalloc(cp, &c->d_bg[i], S * c->work_plane * c->bg_ch))) return rc;
+        if ((rc = dalloc(cp, &c->d_bg[i], S * c->work_plane * c->traits().bg_ch))) return rc;
     if ((rc = dalloc(cp, &c->d_keep, S * c->work_plane)) || (rc = dalloc(cp, &c->d_has_keep, S)) ||
-        (rc = dalloc(cp, &c->d_init, S)) || (rc = dalloc(cp, &c->d_mask, c->use_fused ? c->work_plane : px)))
+        (rc = dalloc(cp, &c->d_init, S)) || (rc = dalloc(cp, &c->d_mask, c->traits().tiles ? c->work_plane : px)))
         return rc;
-    if (c->use_fused) {
+    if (c->traits().tiles) {
         c->ntx = (c->w + 63) / 64;
         c->nty = (c->h + 63) / 64;
         c->ntiles = c->ntx * c->nty;
@@ -723,7 +731,7 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
     // per slot at 8 streams x 256 frames and max_contours 1 << 14 (4 GB pinned per rank).  The per-frame
     // path copies [frames][max_contours] records from the device and keeps that size.
     c->rec_cap = p.max_contours;
-    if (c->use_fused)
+    if (c->traits().tiles)
         c->rec_cap = (int)std::min<size_t>((size_t)p.max_contours,
                                            std::max<size_t>(64, (size_t(32) << 20) / (frames * 5 * sizeof(int32_t))));
     for (int i = 0; i < c->nslots; i++) {
@@ -734,19 +742,17 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
         if (hipMemset(b.d_count, 0, (3 * frames + 3) * sizeof(int32_t)) != hipSuccess)
             return failf(cp, FM_EHIP, "hipMemset of the batch counters failed");
         if ((p.flags & FM_FLAG_KEEP_PLANES) && (rc = dalloc(cp, &b.d_planes, px * 3))) return rc;
-        if (c->use_fused) {
+        if (c->traits().tiles) {
             if ((rc = dalloc(cp, &b.d_heavy, frames * c->ntiles)) ||
                 (rc = dalloc(cp, &b.d_tiles, frames * c->ntiles)) ||
                 (rc = dalloc(cp, &b.d_tflag, frames * c->ntiles * 8)) || (rc = dalloc(cp, &b.d_candf, frames * c->ntiles)) ||
                 (rc = dalloc(cp, &b.d_clist, frames * c->ntiles)) || (rc = dalloc(cp, &b.d_rlist, frames * c->ntiles)) ||
                 (rc = dalloc(cp, &b.d_regrep, frames * c->ntiles)) || (rc = dalloc(cp, &b.d_ncr, frames * 2)) ||
                 (rc = dalloc(cp, &b.d_dbits, frames * c->ntiles * 64)) ||
-                (c->use_pix && (rc = dalloc(cp, &b.d_bits, frames * c->ntiles * 64))) ||
-                (c->use_small && (rc = dalloc(cp, &b.d_sblur, small_scratch_bytes(c->h, c->w, c->nty, frames)))) ||
-                (c->use_wide && (rc = dalloc(cp, &b.d_wblur, wide_scratch_bytes(c->w, c->nty, frames)))) ||
-                (c->use_rgb && (rc = dalloc(cp, &b.d_cblur, rgb_scratch_bytes(c->w, c->nty, frames)))) ||
-                (c->use_mog2 && ((rc = dalloc(cp, &b.d_mblur, wide_scratch_bytes(c->w, c->nty, frames))) ||
-                                 (rc = dalloc(cp, &b.d_alpha, frames)))) ||
+                (c->traits().bits && (rc = dalloc(cp, &b.d_bits, frames * c->ntiles * 64))) ||
+                (c->traits().blur_ch &&
+                 (rc = dalloc(cp, &b.d_blur, scan_scratch_bytes(c->w, c->nty, frames, c->traits().blur_ch)))) ||
+                (c->path == PixelPath::Mog2 && (rc = dalloc(cp, &b.d_alpha, frames))) ||
                 (rc = dalloc(cp, &b.d_nodes, (size_t)c->nnodes)))
                 return rc;
         }
@@ -762,7 +768,7 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
         FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&b.dh_overflow, b.h_overflow, 0));
         if (b.d_tflag) FM_HIP_TRY(cp, hipMemset(b.d_tflag, 0, frames * c->ntiles * 8 * sizeof(uint32_t)));
         FM_HIP_TRY(cp, halloc(cp, &b.h_init, S, 0));
-        if (c->use_mog2) FM_HIP_TRY(cp, halloc(cp, &b.h_alpha, frames * sizeof(float), 0));
+        if (c->path == PixelPath::Mog2) FM_HIP_TRY(cp, halloc(cp, &b.h_alpha, frames * sizeof(float), 0));
         if (i < c->nccl && ccl_qmode != 2) {
             if (ccl_qmode == 1) {
                 int lo = 0, hi = 0;
@@ -778,10 +784,10 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
             FM_HIP_TRY(cp, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     }
     // pixel-level CCL: the whole batch on the v1 path, one frame for the fused path's overflow fallback
-    const size_t ccl_px = c->use_fused ? c->work_plane : px;
+    const size_t ccl_px = c->traits().tiles ? c->work_plane : px;
     if ((rc = dalloc(cp, &c->d_label, ccl_px)) || (rc = dalloc(cp, &c->d_cid, ccl_px)) ||
         (rc = dalloc(cp, &c->d_outer, ccl_px)) ||
-        (!c->use_fused && (rc = dalloc(cp, &c->d_rec_dev, frames * (size_t)p.max_contours * 5))) ||
+        (!c->traits().tiles && (rc = dalloc(cp, &c->d_rec_dev, frames * (size_t)p.max_contours * 5))) ||
         (rc = dalloc(cp, &c->d_rec_one, (size_t)p.max_contours * 5)))
         return rc;
     c->rec_one_cap = (size_t)p.max_contours;
@@ -789,9 +795,9 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
     FM_HIP_TRY(cp, hipHostGetDevicePointer((void**)&c->dh_err, c->h_err, 0));
     *c->h_err = 0;
     FM_HIP_TRY(cp, hipMemset(c->d_has_keep, 0, S));
-    if (c->bg_ch) {
-        FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
-        FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * c->bg_ch * sizeof(double)));
+    if (c->traits().bg_ch) {
+        FM_HIP_TRY(cp, hipMemset(c->d_bg[0], 0, S * c->work_plane * c->traits().bg_ch * sizeof(double)));
+        FM_HIP_TRY(cp, hipMemset(c->d_bg[1], 0, S * c->work_plane * c->traits().bg_ch * sizeof(double)));
     }
     auto up = [&](auto** d, const auto& v) -> int {
         int r = dalloc(cp, d, v.size());
@@ -807,7 +813,7 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
     }
     c->bg_init.assign(S, 0);
     c->has_keep.assign(S, 0);
-    if (c->use_mog2) {  // no pixel has a mode yet; modes at or above nmodes are never read
+    if (c->path == PixelPath::Mog2) {  // no pixel has a mode yet; modes at or above nmodes are never read
         if ((rc = dalloc(cp, &c->d_mog_state, mog2_state_floats((int)S, c->w, c->nty))) ||
             (rc = dalloc(cp, &c->d_mog_nm, mog2_nmodes_bytes((int)S, c->w, c->nty))) ||
             (rc = dalloc(cp, &c->d_mog_bg, c->work_plane)))
@@ -817,14 +823,14 @@ static int create_context(fm_ctx** out, const fm_params* prm, const fm_mog2_para
     }
     if (const char* e = dev_env("FM_DEBUG_SKIP")) c->dbg_skip = std::atoi(e);
     c->serial = dev_env("FM_SERIAL") != nullptr;
-    if (dev_env("FM_PTS") && c->use_pix) {
+    if (dev_env("FM_PTS") && c->traits().bits) {
         // per launch: [S][ntiles][4] workgroup stamps, then [S][ntiles][8 waves][4] k_pix5 phase cycles
         if (const char* e = dev_env("FM_PTS_RING")) c->pts_ring = std::max(1, std::min(256, std::atoi(e)));
         const size_t n = (size_t)S * c->ntiles * 36 * c->pts_ring;
         if ((rc = dalloc(cp, &c->d_pts, n))) return rc;
         FM_HIP_TRY(cp, hipMemset(c->d_pts, 0, n * sizeof(uint64_t)));
     }
-    if (dev_env("FM_TS") && c->use_fused) {
+    if (dev_env("FM_TS") && c->traits().tiles) {
         if ((rc = dalloc(cp, &c->d_ts, frames * c->ntiles * 16))) return rc;
         c->ts_sum.assign(16, 0.0);
         c->ts_n.assign(16, 0);
@@ -908,7 +914,7 @@ int fm_reset_stream(fm_ctx* c, int stream) {
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     c->bg_init[stream] = 0;
-    if (c->use_mog2) {
+    if (c->path == PixelPath::Mog2) {
         const size_t n = mog2_nmodes_bytes(1, c->w, c->nty);
         FM_HIP_TRY(c, hipSetDevice(c->p.device));
         FM_HIP_TRY(c, hipMemsetAsync(c->d_mog_nm + (size_t)stream * n, 0, n, c->stream));
@@ -1079,7 +1085,7 @@ FusedArgs fused_args(fm_ctx* c, BatchSlot& B, const uint8_t* work, int n, bool a
     fa.dbits = B.d_dbits;
     fa.tiles = B.d_tiles;
     fa.tflag = B.d_tflag;
-    fa.tflag_waves = (c->use_small || c->use_wide || c->use_rgb || c->use_mog2) ? 8 : 1;
+    fa.tflag_waves = c->traits().scan ? 8 : 1;
     fa.candf = B.d_candf;
     fa.clist = B.d_clist;
     fa.rlist = B.d_rlist;
@@ -1126,12 +1132,12 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
     hipStream_t ps = c->stream;
     const int n = fa.T;
     if (c->d_ts) FM_HIP_TRY(c, hipMemsetAsync(c->d_ts, 0, (size_t)n * fa.S * c->ntiles * 16 * sizeof(uint64_t), ps));
-    if (!c->use_pix) {
+    if (!c->traits().bits) {
         FM_HIP_TRY(c, launch_fused(ps, fa, &c->timer));
         c->bg_cur ^= 1;
         return FM_OK;
     }
-    if (c->use_mog2) {
+    if (c->path == PixelPath::Mog2) {
         // The whole batch in one launch pair (a stream's first frame is a frame like any other: no mode fits).
         // Each frame's learning rate from the stream's frame count, in double as OpenCV computes it; the counts
         // advance here, so batches in flight chain as the model itself does on the pixel stream.
@@ -1150,11 +1156,11 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
         FusedArgs fp = fa;
         fp.init = nullptr;
         // (each kernel timed on its own, so that the scan appears as mog2_scan under either profile flag)
-        FM_HIP_TRY(c, c->timer.timed(ps, c->mog2_small ? "small_blur" : "wide_blur", [&](uint64_t* ks, uint64_t*) {
-            return c->mog2_small ? launch_small_blur(ps, fp, B.d_mblur, ks) : launch_wide_blur(ps, fp, B.d_mblur, ks);
+        FM_HIP_TRY(c, c->timer.timed(ps, c->small_blur ? "small_blur" : "wide_blur", [&](uint64_t* ks, uint64_t*) {
+            return c->small_blur ? launch_small_blur(ps, fp, B.d_blur, ks) : launch_wide_blur(ps, fp, B.d_blur, ks);
         }));
         FM_HIP_TRY(c, c->timer.timed(ps, "mog2_scan", [&](uint64_t* ks, uint64_t*) {
-            return launch_mog2_scan(ps, fp, md, B.d_mblur, ks);
+            return launch_mog2_scan(ps, fp, md, B.d_blur, ks);
         }));
         return FM_OK;
     }
@@ -1167,19 +1173,13 @@ int run_pixel(fm_ctx* c, BatchSlot& B, const FusedArgs& fa, bool any_init) {
         fp.bg_in = c->d_bg[c->bg_cur];
         fp.bg_out = c->d_bg[c->bg_cur ^ 1];
         if (!init) fp.init = nullptr;
-        if (c->use_small)  // not stamping (FM_FLAG_PROFILE, or the stamp ring full): the pair timed by events
-            FM_HIP_TRY(c, c->timer.timed(ps, init ? "small_blur_init" : "small_blur", [&](uint64_t* k1, uint64_t* k2) {
-                return launch_small(ps, fp, B.d_sblur, k1, k2);
-            }, true, init ? "small_scan_init" : "small_scan", init ? "small_init" : "small"));
-        else if (c->use_wide)
-            FM_HIP_TRY(c, c->timer.timed(ps, init ? "wide_blur_init" : "wide_blur", [&](uint64_t* k1, uint64_t* k2) {
-                return launch_wide(ps, fp, B.d_wblur, k1, k2);
-            }, true, init ? "wide_scan_init" : "wide_scan", init ? "wide_init" : "wide"));
-        else if (c->use_rgb)
-            FM_HIP_TRY(c, c->timer.timed(ps, init ? "rgb_blur_init" : "rgb_blur", [&](uint64_t* k1, uint64_t* k2) {
-                return launch_rgb(ps, fp, B.d_cblur, k1, k2);
-            }, true, init ? "rgb_scan_init" : "rgb_scan", init ? "rgb_init" : "rgb"));
-        else
+        const PathTraits& tr = c->traits();
+        if (tr.launch) {  // not stamping (FM_FLAG_PROFILE, or the stamp ring full): the pair timed by events
+            const char* const* nm = tr.timer[init];
+            FM_HIP_TRY(c, c->timer.timed(ps, nm[0], [&](uint64_t* k1, uint64_t* k2) {
+                return tr.launch(ps, fp, B.d_blur, k1, k2);
+            }, true, nm[1], nm[2]));
+        } else
             FM_HIP_TRY(c, c->timer.timed(ps, name, [&](uint64_t* ks, uint64_t*) {
                 fp.kstamp = ks;
                 return launch_pix(ps, fp, planes, init);
@@ -1210,7 +1210,7 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
     // frame's launch included, come from those bits here, at the head of the chain and ahead of the labelling gate.
     // (The small-image, wide-Gaussian and colour scans and k_fused write their own.)  Timed by events, like k_regions
     // (FM_FLAG_PROFILE; never in the pixel-only mode on a contour stream).
-    if (c->use_pix && !c->use_small && !c->use_wide && !c->use_rgb && !c->use_mog2)
+    if (c->traits().bits && !c->traits().scan)
         FM_HIP_TRY(c, c->timer.timed(cs, "tile_flags", [&](uint64_t*, uint64_t*) { return launch_tile_flags(cs, fa); }, false));
     if (c->frame_ccl) {  // small work images: the whole pass of a frame in one workgroup (no gate needed)
         FusedArgs fc = fa;
@@ -1226,7 +1226,7 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
                 if (e != hipSuccess) return e;
                 B.ccl_F = F;
             }
-            return launch_frame_contours(cs, fc, c->use_pix);
+            return launch_frame_contours(cs, fc, c->traits().bits);
         }, kDevSwitches));
     } else {
         // the labelling gate: one batch's labelling kernel at a time (the previous batch's, on another contour
@@ -1234,7 +1234,7 @@ int run_contours(fm_ctx* c, BatchSlot& B, int si, const FusedArgs& fa) {
         // (+1.5 %, 388.1 vs 382.3 k, 4 alternating rounds, round 3)
         hipEvent_t gate_wait = nullptr;
         if (!c->serial && c->lab_prev >= 0 && c->lab_prev != si) gate_wait = c->slots[c->lab_prev].ev_lab;
-        FM_HIP_TRY(c, launch_tile_ccl(cs, fa, c->use_pix, &c->timer, gate_wait, B.ev_lab));
+        FM_HIP_TRY(c, launch_tile_ccl(cs, fa, c->traits().bits, &c->timer, gate_wait, B.ev_lab));
         c->lab_prev = si;
     }
     B.fa = fa;
@@ -1336,7 +1336,7 @@ int submit(fm_ctx* c, BatchInput in) {
         any_init |= B.h_init[s] != 0;
     }
     if (any_init) FM_HIP_TRY(c, hipMemcpyAsync(c->d_init, B.h_init, S, hipMemcpyHostToDevice, ps));
-    if (c->use_fused) {
+    if (c->traits().tiles) {
         const FusedArgs fa = fused_args(c, B, work, n, any_init);
         if ((rc = run_pixel(c, B, fa, any_init)) || (rc = run_contours(c, B, si, fa))) return rc;
     } else if ((rc = run_per_frame(c, B, work, n, any_init))) {
@@ -1444,10 +1444,10 @@ using WholeFrames = std::vector<std::pair<size_t, std::vector<int32_t>>>;  // (f
 int fetch_whole_frames(fm_ctx* c, BatchSlot& B, size_t F, WholeFrames& whole) {
     c->fallbacks = 0;
     for (size_t f = 0; f < F; f++) {
-        const bool ovf = c->use_fused && B.h_overflow[f];
+        const bool ovf = c->traits().tiles && B.h_overflow[f];
         if (!ovf && B.h_count[f] <= c->rec_cap) continue;
         std::vector<int32_t> v;
-        if (c->use_fused && !ovf) {
+        if (c->traits().tiles && !ovf) {
             if (int rc = emit_all(c, B, f, B.h_count[f], v)) return rc;
         } else {
             // the contour pass ran out of nodes for this frame (fused path), or the per-frame
@@ -1538,7 +1538,7 @@ int fm_wait(fm_ctx* c) {
 #ifdef FM_BOUNDS_CHECK
     if (*c->h_err) return failf(c, FM_EHIP, "contour-pass bounds check failed: codes 0x%x", *c->h_err);
 #endif
-    if (c->use_fused) {
+    if (c->traits().tiles) {
         c->stats[0] = B.h_stats[0];
         c->stats[1] = B.h_stats[1];
     }
@@ -1635,7 +1635,7 @@ int fm_read_mask(fm_ctx* c, int frame, int stream, uint8_t* out) {
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const size_t f = (size_t)frame * c->p.n_streams + stream;
     hipStream_t st = c->aux_stream;
-    if (c->use_fused) {
+    if (c->traits().tiles) {
         const BatchSlot& B = c->slots[c->ready_slot];
         FM_HIP_TRY(c, launch_expand_bits(st, B.d_dbits + f * c->ntiles * 64, B.d_candf + f * c->ntiles, c->d_mask, c->h, c->w,
                                       c->ntx));
@@ -1649,7 +1649,7 @@ int fm_read_mask(fm_ctx* c, int frame, int stream, uint8_t* out) {
 
 int fm_read_threshold_bits(fm_ctx* c, int frame, int stream, uint64_t* out) {
     if (!c || !out) return failf(c, FM_EINVAL, "null argument");
-    if (!c->use_pix) return failf(c, FM_ESTATE, "this pixel path keeps no threshold bits");
+    if (!c->traits().bits) return failf(c, FM_ESTATE, "this pixel path keeps no threshold bits");
     if (int rc = check_frame(c, frame, stream, true)) return rc;
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
     const BatchSlot& B = c->slots[c->ready_slot];
@@ -1845,13 +1845,13 @@ int fm_retained_count(const fm_ctx* c, int* in_use, int* capacity) {
 
 int fm_read_background(fm_ctx* c, int stream, double* out) {
     if (!c || !out) return failf(c, FM_EINVAL, "null argument");
-    if (c->use_mog2) return failf(c, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_background / fm_mog2_read_model");
+    if (c->path == PixelPath::Mog2) return failf(c, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_background / fm_mog2_read_model");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     if (!c->bg_init[stream]) return failf(c, FM_ESTATE, "stream %d has no background yet", stream);
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
     FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t n = c->work_plane * c->bg_ch;  // a colour context: [h][w][3]
+    const size_t n = c->work_plane * c->traits().bg_ch;  // a colour context: [h][w][3]
     FM_HIP_TRY(c, hipMemcpyAsync(out, c->d_bg[c->bg_cur] + (size_t)stream * n, n * sizeof(double), hipMemcpyDeviceToHost,
                               c->stream));
     FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1860,11 +1860,11 @@ int fm_read_background(fm_ctx* c, int stream, double* out) {
 
 int fm_write_background(fm_ctx* c, int stream, const double* in) {
     if (!c || !in) return failf(c, FM_EINVAL, "null argument");
-    if (c->use_mog2) return failf(c, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_write_model");
+    if (c->path == PixelPath::Mog2) return failf(c, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_write_model");
     if (int rc = check_idle(c)) return rc;
     if (int rc = check_stream(c, stream)) return rc;
     FM_HIP_TRY(c, hipSetDevice(c->p.device));
-    const size_t n = c->work_plane * c->bg_ch;
+    const size_t n = c->work_plane * c->traits().bg_ch;
     FM_HIP_TRY(c, hipMemcpyAsync(c->d_bg[c->bg_cur] + (size_t)stream * n, in, n * sizeof(double), hipMemcpyHostToDevice,
                               c->stream));
     FM_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1874,8 +1874,8 @@ int fm_write_background(fm_ctx* c, int stream, const double* in) {
 
 int fm_background_channels(const fm_ctx* c, int* channels) {
     if (!c || !channels) return failf(kNoCtx, FM_EINVAL, "null argument");
-    if (c->use_mog2) return failf(kNoCtx, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_background");
-    *channels = c->bg_ch;
+    if (c->path == PixelPath::Mog2) return failf(kNoCtx, FM_ESTATE, "a Gaussian-mixture context has no average: fm_mog2_background");
+    *channels = c->traits().bg_ch;
     return FM_OK;
 }
 
@@ -1883,7 +1883,7 @@ int fm_background_channels(const fm_ctx* c, int* channels) {
 // [x][CS] bytes) and the ABI's row-major [5][h][w] arrays: whole planes are copied and transposed on the host.
 namespace {
 int check_mog2_ctx(fm_ctx* c, int stream) {
-    if (!c->use_mog2) return failf(c, FM_ESTATE, "not a Gaussian-mixture context (FM_FLAG_MOG2)");
+    if (c->path != PixelPath::Mog2) return failf(c, FM_ESTATE, "not a Gaussian-mixture context (FM_FLAG_MOG2)");
     if (int rc = check_idle(c)) return rc;
     return check_stream(c, stream);
 }

@@ -245,32 +245,29 @@ int fused_max_ksize();
 hipError_t launch_pix(hipStream_t st, const FusedArgs& a, bool planes, bool init);
 int pix_lds_bytes(int ksize);
 bool pix_supported(int ksize);
-// small work images (fm_small.hip): k_small_blur (every frame of the launch in parallel) + k_small_scan
-// (one wave per column and tile row, lane = row); sblur: small_scratch_bytes of the batch's frames
+// The blur + scan paths: a frame-parallel blur into a scratch of blur bytes (scan_scratch_bytes, fm_scan.h), then
+// fm_scan.h's scan of the frames in order around a per-pixel model.
+// small work images (fm_small.hip): k_small_blur (one workgroup per frame) + k_small_scan (the running average)
 bool small_supported(int h, int w, int ksize);
-size_t small_scratch_bytes(int h, int w, int nty, size_t frames);
-hipError_t launch_small(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint64_t* ks_blur, uint64_t* ks_scan);
-hipError_t launch_small_scan(hipStream_t st, const FusedArgs& a, const uint8_t* sblur, uint64_t* ks_scan);
-// Gaussian sizes above k_fused's on larger work images (fm_wide.hip): k_wide_blur (every frame of the launch in
-// parallel, a workgroup per column strip sliding down an LDS ring of horizontal sums) + k_small_scan; coef: the
-// context's taps; wblur: wide_scratch_bytes of the batch's frames
+hipError_t launch_small(hipStream_t st, const FusedArgs& a, uint8_t* blur, uint64_t* ks_blur, uint64_t* ks_scan);
+hipError_t launch_small_scan(hipStream_t st, const FusedArgs& a, const uint8_t* blur, uint64_t* ks_scan);
+// Gaussian sizes above k_fused's on larger work images (fm_wide.hip): k_wide_blur (a workgroup per column strip
+// sliding down an LDS ring of horizontal sums) + k_small_scan; coef: the context's taps
 bool wide_supported(int ksize, const int32_t* coef);
 int wide_lds_bytes(int ksize, const int32_t* coef);
-size_t wide_scratch_bytes(int w, int nty, size_t frames);
-hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* wblur, uint64_t* ks_blur, uint64_t* ks_scan);
-// the chain on the three colour channels (fm_rgb.hip, FM_FLAG_COLOUR_MOTION): k_rgb_blur (every frame and 64 x 64
-// tile of the launch in parallel) + k_rgb_scan (k_small_scan with three backgrounds; the channels' threshold bits
-// ORed).  The kernels take their own argument struct, filled from a: a.bg_in / a.bg_out are [S][h][w][3] doubles
-// here, and the element counts of OpenCV's SIMD rules (a.cvt_simd, a.acc_vec_end) are taken over 3hw, not from a.
-// cblur: rgb_scratch_bytes of the batch's frames, [F][3][x][nty * 64]
+hipError_t launch_wide(hipStream_t st, const FusedArgs& a, uint8_t* blur, uint64_t* ks_blur, uint64_t* ks_scan);
+// the chain on the three colour channels (fm_rgb.hip, FM_FLAG_COLOUR_MOTION): k_rgb_blur (a workgroup per frame and
+// 64 x 64 tile) + k_rgb_scan (three running averages; the channels' threshold bits ORed).  The kernels take their
+// own argument struct, filled from a: a.bg_in / a.bg_out are [S][h][w][3] doubles here, and the element counts of
+// OpenCV's SIMD rules (a.cvt_simd, a.acc_vec_end) are taken over 3hw, not from a.  blur: three channels,
+// [F][3][x][nty * 64]
 bool rgb_supported(int h, int w, int ksize);
 int rgb_lds_bytes(int ksize);
-size_t rgb_scratch_bytes(int w, int nty, size_t frames);
-hipError_t launch_rgb(hipStream_t st, const FusedArgs& a, uint8_t* cblur, uint64_t* ks_blur, uint64_t* ks_scan);
+hipError_t launch_rgb(hipStream_t st, const FusedArgs& a, uint8_t* blur, uint64_t* ks_blur, uint64_t* ks_scan);
 // the Gaussian-mixture background model (fm_mog2.hip, FM_FLAG_MOG2): the blur of launch_small or launch_wide_blur,
-// then k_mog2_scan (k_small_scan's job shape with the pixel's five modes in registers) in place of the average's
-// scan.  The state is updated in place: float planes [S][15][x][nty * 64] (field = 5 * {weight, mean, var} +
-// mode; mog2_state_floats) and uint8 nmodes [S][x][nty * 64] (mog2_nmodes_bytes); alphaT: the learning rate of
+// then k_mog2_scan (the scan around the pixel's five modes in registers) in place of the average's scan.  The
+// state is updated in place: float planes [S][15][x][nty * 64] (field = 5 * {weight, mean, var} + mode;
+// mog2_state_floats) and uint8 nmodes [S][x][nty * 64] (mog2_nmodes_bytes); alphaT: the learning rate of
 // each of the batch's a.T * a.S frames, [T][S]
 struct Mog2Dev {
     float* state;

@@ -9,7 +9,7 @@
 // frame-parallel (k_small_blur or k_wide_blur, unchanged, blur bytes [F][x][CS] column-major); only the model is
 // sequential in time.
 //
-//   k_mog2_scan        k_small_scan's job shape and plumbing: one wave per (stream, image column, 64-row tile row),
+//   k_mog2_scan        fm_scan.h's scan_frames: one wave per (stream, image column, 64-row tile row),
 //                      lane = row, the frames of the launch in order.  The state of a pixel -- nmodes and five modes
 //                      {weight, mean, variance} sorted by weight -- sits in 15 VGPRs + 1 for the launch's frames.
 //                      Registers are not addressable, so every loop over modes is unrolled with compile-time
@@ -27,15 +27,12 @@
 //
 // Every float operation is one separately rounded IEEE operation (-ffp-contract=off; the divisions are the
 // compiler's correctly rounded sequence), in OpenCV's order, so the model is bit-identical to the scalar C++.
-#include "fm_internal.h"
+#include "fm_scan.h"
 
 namespace fm {
 namespace mg {
 
 constexpr int NM = 5;     // mixtures: the register budget of k_mog2_scan
-constexpr int ST = 256;   // k_mog2_scan threads (4 waves, each its own job)
-constexpr int PFD = 8;    // frames per group of blur-byte loads
-constexpr int NG = 2;     // groups in flight
 constexpr int BGT = 256;  // k_mog2_background threads
 
 struct Mog2Args {
@@ -43,14 +40,9 @@ struct Mog2Args {
     float* state;          // [S][15][w][CS]
     uint8_t* nmodes;       // [S][w][CS]
     const float* alphaT;   // [T][S] learning rate of frame t of stream s, (float) of the double the host computed
-    uint64_t* bits;        // [F][ntiles][64] threshold bits, a word per tile column
-    uint32_t* tflag;       // [F][ntiles][8] FLAG_* (word 0 is ORed into)
-    int S, h, w;
-    int t_begin, t_end;
-    int ntx, nty, ntiles;
+    Geom g;
     float Tb, Tg, TB, var_init, var_min, var_max, CT, tau;
     int shadows;
-    uint64_t* kstamp;
 };
 
 struct Px {
@@ -160,28 +152,26 @@ __device__ __forceinline__ bool mog2_step(Px& p, float d, float alphaT, const Mo
     return !bgd && !shadow;
 }
 
-__global__ __launch_bounds__(ST) void k_mog2_scan(Mog2Args a, int CS) {
-    const int tid = threadIdx.x, ln = tid & 63;
-    const int h = a.h, w = a.w, S = a.S;
-    kstamp_begin_grid(a.kstamp);
-    const int job = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (ST / 64) + (tid >> 6)));
-    const int njobs = S * w * a.nty;
-    if (job < njobs) {
-        const int s = job / (w * a.nty);
-        const int rem = job - s * w * a.nty;
-        const int ty = rem / w, x = rem - ty * w;
-        const int y = ty * 64 + ln;
-        const bool valid = y < h;
-        const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
-        const int tile = ty * a.ntx + x / 64, c = x & 63;
-        const int t0 = a.t_begin, t1 = a.t_end;
-        const int yl = valid ? y : 0;
+struct Mixture {  // scan_frames' model: the pixel's modes, and each frame's learning rate beside its blur byte
+    struct Group {
+        uint32_t b[PFD];
+        float al[PFD];
+    };
+    const Mog2Args& a;
+    int CS;
+    Px p;
+    size_t PS, fstride;
+    float* sp;
+    uint8_t* np;
+    const uint8_t* base;
+    const float* al;
+    __device__ __forceinline__ void open(const Lane& l) {
         // the pixel's state: field f of stream s at state[((s * 15 + f) * w + x) * CS + y]
-        const size_t PS = (size_t)w * CS, pix = (size_t)x * CS + yl;
-        float* const sp = a.state + (size_t)s * 15 * PS + pix;
-        uint8_t* const np = a.nmodes + (size_t)s * PS + pix;
-        Px p;
-        p.nm = valid ? (int)*np : 0;
+        PS = (size_t)a.g.w * CS;
+        const size_t pix = (size_t)l.x * CS + l.y;
+        sp = a.state + (size_t)l.s * 15 * PS + pix;
+        np = a.nmodes + (size_t)l.s * PS + pix;
+        p.nm = l.valid ? (int)*np : 0;
 #pragma unroll
         for (int M = 0; M < NM; M++) {
             const bool has = M < p.nm;
@@ -190,66 +180,19 @@ __global__ __launch_bounds__(ST) void k_mog2_scan(Mog2Args a, int CS) {
             p.v[M] = has ? sp[(size_t)(2 * NM + M) * PS] : 0.f;
         }
         // blur bytes of frame t of this pixel: blur[((t * S + s) * w + x) * CS + y]
-        const size_t fstride = (size_t)S * w * CS;
-        const uint8_t* base = a.blur + (size_t)s * w * CS + (size_t)x * CS + yl;
-        const float* const al = a.alphaT + s;  // frame t: al[t * S] (wave-uniform)
-        const uint32_t flagL = c < 2 ? (FLAG_L) : 0u, flagR = c >= 62 ? FLAG_R : 0u;
-        uint32_t rg[NG][PFD];  // blur bytes of NG groups of PFD frames in flight
-        float ra[NG][PFD];     // and the frames' learning rates
-        // each frame's column word into lane (t - t0) % 64 of (wlo, whi); every 64 frames the block's words are
-        // stored (one store, a frame per lane) and their flag words ORed into the tile-frame flags
-        uint32_t wlo = 0, whi = 0;
-        uint64_t* const bits0 = a.bits + ((size_t)s * a.ntiles + tile) * 64 + c;  // frame 0's word of (s, tile, c)
-        uint32_t* const flag0 = a.tflag + ((size_t)s * a.ntiles + tile) * 8;
-        const size_t bstride = (size_t)S * a.ntiles * 64, fstride8 = (size_t)S * a.ntiles * 8;
-        auto flush = [&](int tb, int n) __attribute__((always_inline)) {  // frames tb .. tb + n - 1 in lanes 0 .. n - 1
-            if (ln < n) {
-                const size_t ft = (size_t)(tb + ln);
-                const uint64_t word = ((uint64_t)whi << 32) | wlo;
-                bits0[ft * bstride] = word;
-                if (word) {
-                    const uint32_t fl = FLAG_ANY | flagL | flagR |
-                                        ((word & 3ull) ? (FLAG_T | (c < 2 ? FLAG_TL : 0u) | (c >= 62 ? FLAG_TR : 0u)) : 0u) |
-                                        ((word >> 62) ? (FLAG_B | (c < 2 ? FLAG_BL : 0u) | (c >= 62 ? FLAG_BR : 0u)) : 0u);
-                    atomicOr(&flag0[ft * fstride8], fl);
-                }
-            }
-        };
-        auto load_group = [&](uint32_t (&r)[PFD], float (&ar)[PFD], int tg) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < PFD; k++) {
-                const int tc = min(tg + k, t1 - 1);  // clamped: unconditional
-                r[k] = base[(size_t)tc * fstride];
-                ar[k] = al[(size_t)tc * S];
-            }
-        };
-        auto run_group = [&](const uint32_t (&r)[PFD], const float (&ar)[PFD], int tg) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < PFD; k++) {
-                const int t = tg + k;
-                if (t >= t1) break;  // wave-uniform
-                const bool fg = mog2_step(p, (float)r[k], ar[k], a);
-                const uint64_t word = __builtin_amdgcn_ballot_w64(fg) & vmask;
-                const int kb = (t - t0) & 63;
-                const bool mine = ln == kb;
-                wlo = mine ? (uint32_t)word : wlo;
-                whi = mine ? (uint32_t)(word >> 32) : whi;
-                if (kb == 63) flush(t - 63, 64);
-            }
-        };
-        static_for<NG>([&](auto g) {
-            constexpr int G = decltype(g)::value;
-            load_group(rg[G], ra[G], t0 + G * PFD);
-        });
-        for (int tg = t0; tg < t1; tg += NG * PFD) {
-            static_for<NG>([&](auto g) {
-                constexpr int G = decltype(g)::value;
-                run_group(rg[G], ra[G], tg + G * PFD);
-                load_group(rg[G], ra[G], tg + (NG + G) * PFD);
-            });
-        }
-        if (const int nrem = (t1 - t0) & 63) flush(t1 - nrem, nrem);  // the last, partial block
-        if (valid) {
+        fstride = (size_t)a.g.S * a.g.w * CS;
+        base = a.blur + (size_t)l.s * a.g.w * CS + (size_t)l.x * CS + l.y;
+        al = a.alphaT + l.s;  // frame t: al[t * S] (wave-uniform)
+    }
+    __device__ __forceinline__ void load(Group& r, int k, int tc) const {
+        r.b[k] = base[(size_t)tc * fstride];
+        r.al[k] = al[(size_t)tc * a.g.S];
+    }
+    __device__ __forceinline__ void step(const Group& r, int k, int, bool& fg) {
+        fg = mog2_step(p, (float)r.b[k], r.al[k], a);
+    }
+    __device__ __forceinline__ void close(const Lane& l) const {
+        if (l.valid) {
             *np = (uint8_t)p.nm;
 #pragma unroll
             for (int M = 0; M < NM; M++)
@@ -260,7 +203,10 @@ __global__ __launch_bounds__(ST) void k_mog2_scan(Mog2Args a, int CS) {
                 }
         }
     }
-    kstamp_end_wg(a.kstamp);
+};
+
+__global__ __launch_bounds__(ST) void k_mog2_scan(Mog2Args a, int CS) {
+    scan_frames(a.g, Mixture{a, CS});
 }
 
 // getBackgroundImage: the weighted mean of the strongest modes up to background_ratio, [h][w] row-major
@@ -297,19 +243,15 @@ hipError_t launch_mog2_scan(hipStream_t st, const FusedArgs& a, const Mog2Dev& m
     r.state = m.state;
     r.nmodes = m.nmodes;
     r.alphaT = m.alphaT;
-    r.bits = a.bits;
-    r.tflag = a.tflag;
-    r.S = a.S, r.h = a.h, r.w = a.w;
-    r.t_begin = a.t_begin, r.t_end = a.t_end;
-    r.ntx = a.ntx, r.nty = a.nty, r.ntiles = a.ntiles;
+    r.g = geom_of(a);
+    r.g.kstamp = ks;
     r.Tb = m.prm.var_threshold, r.Tg = m.prm.var_threshold_gen, r.TB = m.prm.background_ratio;
     r.var_init = m.prm.var_init, r.var_min = m.prm.var_min, r.var_max = m.prm.var_max;
     r.CT = m.prm.complexity_reduction, r.tau = m.prm.shadow_tau;
     r.shadows = m.prm.detect_shadows != 0;
-    r.kstamp = ks;
     const int njobs = a.S * a.w * a.nty;
-    const dim3 grid((njobs + mg::ST / 64 - 1) / (mg::ST / 64));
-    hipLaunchKernelGGL(mg::k_mog2_scan, grid, dim3(mg::ST), 0, st, r, a.nty * 64);
+    const dim3 grid((njobs + ST / 64 - 1) / (ST / 64));
+    hipLaunchKernelGGL(mg::k_mog2_scan, grid, dim3(ST), 0, st, r, a.nty * 64);
     return hipGetLastError();
 }
 

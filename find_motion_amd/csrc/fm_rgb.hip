@@ -20,14 +20,13 @@
 //               tile's blur bytes are transposed in LDS and stored column-major, 16 rows a store, to the scratch
 //               [F][3][x][CS] (k_small_blur's layout per channel, CS = nty * 64).  It clears the tile's flags and,
 //               in the last tile column, the bit words of the columns past the image.
-//   k_rgb_scan  k_small_scan with three backgrounds: one wave per (stream, image column, 64-row tile row), lane =
-//               row, the frames in order with three f64 backgrounds in registers; per frame three blur bytes,
-//               three diffs, and __ballot((dB > t) | (dG > t) | (dR > t)) is the tile's column word.  A block of 64
-//               frames' words is held one frame per lane and stored at once, the tile flags ORed atomically.
+//   k_rgb_scan  fm_scan.h's scan_frames (one wave per stream, image column and 64-row tile row, lane = row, the
+//               frames in order) around three f64 backgrounds in registers; per frame three blur bytes, three
+//               diffs, and (dB > t) | (dG > t) | (dR > t) is the lane's threshold bit.
 //               The background is read and written interleaved, [S][h][w][3]: the ABI's layout.
 //
 // No workgroup waits on another, no index depends on data, and the flag ORs are the only atomics.
-#include "fm_internal.h"
+#include "fm_scan.h"
 
 namespace fm {
 namespace rgb {
@@ -35,9 +34,6 @@ namespace rgb {
 constexpr int kMaxKsize = 49;  // Gaussian sizes of the colour path (k_fused's limit)
 constexpr int BT = 256;   // k_rgb_blur threads
 constexpr int LC = 10;    // k_rgb_blur: pixels a thread loads together
-constexpr int ST = 256;   // k_rgb_scan threads (4 waves, each its own job)
-constexpr int PFD = 8;    // k_rgb_scan: frames per group of blur-byte loads
-constexpr int NG = 2;     // groups in flight
 constexpr int OTS = 68;   // bytes between two columns of the transposed tile in LDS (17 dwords: 64 lanes that
                           // write one dword each to 64 columns meet 64 banks)
 
@@ -49,25 +45,12 @@ struct RgbArgs {
     const uint8_t* keep;      // [S][h*w]
     const uint8_t* has_keep;  // [S]
     const uint8_t* init;      // [S] or nullptr: 1 => bg := blur at the launch's first frame
-    uint64_t* bits;           // [F][ntiles][64] threshold bits, a word per tile column
-    uint32_t* tflag;          // [F][ntiles][8] FLAG_* (word 0 is ORed into)
-    int S, h, w, ksize, thresh;
-    int t_begin, t_end;       // frames of the batch this launch processes
-    int ntx, nty, ntiles;
+    Geom g;
+    int ksize, thresh;
     double alpha, beta;
     long long acc_vec_end;    // 3hw - 3hw % 16: elements below it take accumulateWeighted's fma body
-    uint64_t* kstamp;
     int32_t coef[kMaxKsize];
 };
-
-__device__ __forceinline__ int refl(int p, int len) {  // BORDER_REFLECT_101 (any distance)
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        p = (p < 0) ? -p : 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
 
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 
@@ -90,24 +73,21 @@ static_assert(blur_lds_bytes(kMaxKsize >> 1) <= 160 * 1024, "k_rgb_blur's tile d
 
 __global__ __launch_bounds__(BT) void k_rgb_blur(RgbArgs a, uint8_t* __restrict__ cblur, int CS) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int h = a.h, w = a.w, S = a.S, K = a.ksize, R = K >> 1, TW = tile_w(R), RB = row_bytes(R), NP = TW / 2;
+    const Geom& gm = a.g;
+    const int h = gm.h, w = gm.w, S = gm.S, K = a.ksize, R = K >> 1, TW = tile_w(R), RB = row_bytes(R), NP = TW / 2;
     const int tid = threadIdx.x;
-    const int fl = blockIdx.x / a.ntiles, tile = blockIdx.x - fl * a.ntiles;
-    const size_t f = (size_t)a.t_begin * S + fl;  // frame of the batch (t * S + s)
+    const int fl = blockIdx.x / gm.ntiles, tile = blockIdx.x - fl * gm.ntiles;
+    const size_t f = (size_t)gm.t_begin * S + fl;  // frame of the batch (t * S + s)
     const int s = (int)(f % S);
-    const int ty = tile / a.ntx, tx = tile - ty * a.ntx;
+    const int ty = tile / gm.ntx, tx = tile - ty * gm.ntx;
     const int x0 = tx * 64, y0 = ty * 64;
     uint8_t* raw = lds;
     uint32_t* H2 = reinterpret_cast<uint32_t*>(lds + raw_bytes(R));  // [3][NP][64]: H of rows 2p (low half), 2p + 1
     int* xi = reinterpret_cast<int*>(H2);  // [TW] byte offset of the source column } until the tile is loaded, where H2
     int* yi = xi + TW;                     // [TW] source row                      } is written later (k = 5: 40,800 B,
                                            //                                        a fourth workgroup on the CU)
-    kstamp_begin_grid(a.kstamp);
-    // this tile-frame's flags (k_rgb_scan ORs into word 0) and, in the last tile column, the bit words of the
-    // columns past the image (no scan wave writes them)
-    if (tid < 8) a.tflag[(f * a.ntiles + tile) * 8 + tid] = 0u;
-    if (tx == a.ntx - 1)
-        for (int c = w - x0 + tid; c < 64; c += BT) a.bits[(f * a.ntiles + tile) * 64 + c] = 0ull;
+    kstamp_begin_grid(gm.kstamp);
+    clear_tile_frame(gm, f, tile, tx, tid, BT);  // the scan's precondition
     for (int i = tid; i < TW; i += BT) {
         xi[i] = 3 * refl(x0 - R + i, w);
         yi[i] = refl(y0 - R + i, h);
@@ -224,113 +204,66 @@ __global__ __launch_bounds__(BT) void k_rgb_blur(RgbArgs a, uint8_t* __restrict_
                 make_uint4(p[0], p[1], p[2], p[3]);
         }
     }
-    kstamp_end_wg(a.kstamp);
+    kstamp_end_wg(gm.kstamp);
 }
 
 // TAILK: some elements take accumulateWeighted's scalar tail (3hw % 16 != 0); SIMD: convertScaleAbs's float path
 // (3hw >= 16)
 template <bool TAILK, bool SIMD>
-__global__ __launch_bounds__(ST) void k_rgb_scan(RgbArgs a, const uint8_t* __restrict__ cblur, int CS) {
-    const int tid = threadIdx.x, ln = tid & 63;
-    const int h = a.h, w = a.w, S = a.S;
-    const double alpha = a.alpha;
-    kstamp_begin_grid(a.kstamp);
-    const int job = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (ST / 64) + (tid >> 6)));
-    const int njobs = S * w * a.nty;
-    if (job < njobs) {
-        const int s = job / (w * a.nty);
-        const int rem = job - s * w * a.nty;
-        const int ty = rem / w, x = rem - ty * w;
-        const int y = ty * 64 + ln;
-        const bool valid = y < h;
-        const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
-        const int tile = ty * a.ntx + x / 64, c = x & 63;
-        const size_t plane3 = (size_t)h * w * 3;
-        const int yl = valid ? y : 0;
-        const long long e0 = 3 * ((long long)yl * w + x);  // element of channel B in the interleaved arrays
-        const double beta = a.beta;
-        const int thr = a.thresh;
-        const int t0 = a.t_begin, t1 = a.t_end;
-        const bool init0 = a.init != nullptr && a.init[s] != 0;
-        bool tail[3];
-        double bg[3];
+struct Colour {  // scan_frames' model: the running averages of one pixel's three channels
+    struct Group { uint32_t b[PFD][3]; };
+    const RgbArgs& a;
+    const uint8_t* cblur;  // blur bytes [F][3][x][CS]
+    int CS;
+    double alpha, beta, bg[3];
+    int thr, t0;
+    bool tail[3], init0;
+    size_t e0, cstride, fstride;
+    const uint8_t* base;
+    __device__ __forceinline__ void open(const Lane& l) {
+        alpha = a.alpha, beta = a.beta, thr = a.thresh, t0 = l.t0;
+        const long long e = 3 * ((long long)l.y * a.g.w + l.x);  // element of channel B in the interleaved arrays
+        e0 = (size_t)l.s * a.g.h * a.g.w * 3 + e;
+        init0 = a.init != nullptr && a.init[l.s] != 0;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            tail[ch] = TAILK && e0 + ch >= a.acc_vec_end;  // accumulateWeighted's scalar tail, counted in elements
-            bg[ch] = (valid && !init0) ? a.bg_in[(size_t)s * plane3 + e0 + ch] : 0.0;
+            tail[ch] = TAILK && e + ch >= a.acc_vec_end;  // accumulateWeighted's scalar tail, counted in elements
+            bg[ch] = (l.valid && !init0) ? a.bg_in[e0 + ch] : 0.0;
         }
         // blur byte of channel ch of frame t of this pixel: cblur[(((t * S + s) * 3 + ch) * w + x) * CS + y]
-        const size_t cstride = (size_t)w * CS, fstride = (size_t)S * 3 * cstride;
-        const uint8_t* base = cblur + (size_t)s * 3 * cstride + (size_t)x * CS + yl;
-        const uint32_t flagL = c < 2 ? (FLAG_L) : 0u, flagR = c >= 62 ? FLAG_R : 0u;
-        uint32_t rg[NG][PFD][3];  // blur bytes of NG groups of PFD frames in flight
-        // each frame's column word into lane (t - t0) % 64 of (wlo, whi); every 64 frames the block's words are
-        // stored (one store, a frame per lane) and their flag words ORed into the tile-frame flags
-        uint32_t wlo = 0, whi = 0;
-        uint64_t* const bits0 = a.bits + ((size_t)s * a.ntiles + tile) * 64 + c;  // frame 0's word of (s, tile, c)
-        uint32_t* const flag0 = a.tflag + ((size_t)s * a.ntiles + tile) * 8;
-        const size_t bstride = (size_t)S * a.ntiles * 64, fstride8 = (size_t)S * a.ntiles * 8;
-        auto flush = [&](int tb, int n) __attribute__((always_inline)) {  // frames tb .. tb + n - 1 in lanes 0 .. n - 1
-            if (ln < n) {
-                const size_t ft = (size_t)(tb + ln);
-                const uint64_t word = ((uint64_t)whi << 32) | wlo;
-                bits0[ft * bstride] = word;
-                if (word) {
-                    const uint32_t fl = FLAG_ANY | flagL | flagR |
-                                        ((word & 3ull) ? (FLAG_T | (c < 2 ? FLAG_TL : 0u) | (c >= 62 ? FLAG_TR : 0u)) : 0u) |
-                                        ((word >> 62) ? (FLAG_B | (c < 2 ? FLAG_BL : 0u) | (c >= 62 ? FLAG_BR : 0u)) : 0u);
-                    atomicOr(&flag0[ft * fstride8], fl);
-                }
-            }
-        };
-        auto load_group = [&](uint32_t (&r)[PFD][3], int tg) __attribute__((always_inline)) {
+        cstride = (size_t)a.g.w * CS, fstride = (size_t)a.g.S * 3 * cstride;
+        base = cblur + (size_t)l.s * 3 * cstride + (size_t)l.x * CS + l.y;
+    }
+    __device__ __forceinline__ void load(Group& r, int k, int tc) const {
+        const uint8_t* p = base + (size_t)tc * fstride;
 #pragma unroll
-            for (int k = 0; k < PFD; k++) {
-                const uint8_t* p = base + (size_t)min(tg + k, t1 - 1) * fstride;  // clamped: unconditional
+        for (int ch = 0; ch < 3; ch++) r.b[k][ch] = p[ch * cstride];
+    }
+    __device__ __forceinline__ void step(const Group& r, int k, int t, bool& over) {
+        const bool first = init0 && t == t0;
+        over = false;
 #pragma unroll
-                for (int ch = 0; ch < 3; ch++) r[k][ch] = p[ch * cstride];
-            }
-        };
-        auto run_group = [&](const uint32_t (&r)[PFD][3], int tg) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < PFD; k++) {
-                const int t = tg + k;
-                if (t >= t1) break;  // wave-uniform
-                const bool first = init0 && t == t0;
-                bool over = false;
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) {
-                    const uint32_t blur = r[k][ch];
-                    const double bv = first ? (double)blur : bg[ch];
-                    const int qr = SIMD ? __float2int_rn(fabsf(__double2float_rn(bv))) : __double2int_rn(fabs(bv));
-                    const int q = min(max(qr, 0), 255);
-                    over |= abs((int)blur - q) > thr;
-                    const double bl = __dmul_rn((double)blur, alpha);
-                    bg[ch] = tail[ch] ? __dadd_rn(bl, __dmul_rn(bv, beta)) : __fma_rn(bv, beta, bl);
-                }
-                const uint64_t word = __builtin_amdgcn_ballot_w64(over) & vmask;
-                const int kb = (t - t0) & 63;
-                const bool mine = ln == kb;
-                wlo = mine ? (uint32_t)word : wlo;
-                whi = mine ? (uint32_t)(word >> 32) : whi;
-                if (kb == 63) flush(t - 63, 64);
-            }
-        };
-        static_for<NG>([&](auto g) { load_group(rg[decltype(g)::value], t0 + decltype(g)::value * PFD); });
-        for (int tg = t0; tg < t1; tg += NG * PFD) {
-            static_for<NG>([&](auto g) {
-                constexpr int G = decltype(g)::value;
-                run_group(rg[G], tg + G * PFD);
-                load_group(rg[G], tg + (NG + G) * PFD);
-            });
-        }
-        if (const int nrem = (t1 - t0) & 63) flush(t1 - nrem, nrem);  // the last, partial block
-        if (valid) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) a.bg_out[(size_t)s * plane3 + e0 + ch] = bg[ch];
+        for (int ch = 0; ch < 3; ch++) {
+            const uint32_t blur = r.b[k][ch];
+            const double bv = first ? (double)blur : bg[ch];
+            const int qr = SIMD ? __float2int_rn(fabsf(__double2float_rn(bv))) : __double2int_rn(fabs(bv));
+            const int q = min(max(qr, 0), 255);
+            over |= abs((int)blur - q) > thr;
+            const double bl = __dmul_rn((double)blur, alpha);
+            bg[ch] = tail[ch] ? __dadd_rn(bl, __dmul_rn(bv, beta)) : __fma_rn(bv, beta, bl);
         }
     }
-    kstamp_end_wg(a.kstamp);
+    __device__ __forceinline__ void close(const Lane& l) const {
+        if (l.valid) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) a.bg_out[e0 + ch] = bg[ch];
+        }
+    }
+};
+
+template <bool TAILK, bool SIMD>
+__global__ __launch_bounds__(ST) void k_rgb_scan(RgbArgs a, const uint8_t* __restrict__ cblur, int CS) {
+    scan_frames(a.g, Colour<TAILK, SIMD>{a, cblur, CS});
 }
 
 }  // namespace rgb
@@ -340,8 +273,6 @@ bool rgb_supported(int h, int w, int ksize) {
 }
 
 int rgb_lds_bytes(int ksize) { return rgb::blur_lds_bytes(ksize >> 1); }
-
-size_t rgb_scratch_bytes(int w, int nty, size_t frames) { return frames * 3 * (size_t)w * nty * 64; }
 
 // frames [a.t_begin, a.t_end) of the batch on the three channels: blur of every frame and tile in parallel, then
 // the scan; a.init may mark first frames (bg := blur at t_begin); a.bg_in / a.bg_out hold [S][h][w][3] doubles.
@@ -355,11 +286,8 @@ hipError_t launch_rgb(hipStream_t st, const FusedArgs& a, uint8_t* cblur, uint64
     r.keep = a.keep;
     r.has_keep = a.has_keep;
     r.init = a.init;
-    r.bits = a.bits;
-    r.tflag = a.tflag;
-    r.S = a.S, r.h = a.h, r.w = a.w, r.ksize = a.ksize, r.thresh = a.thresh;
-    r.t_begin = a.t_begin, r.t_end = a.t_end;
-    r.ntx = a.ntx, r.nty = a.nty, r.ntiles = a.ntiles;
+    r.g = geom_of(a);
+    r.ksize = a.ksize, r.thresh = a.thresh;
     r.alpha = a.alpha, r.beta = a.beta;
     const long long n3 = 3ll * a.h * a.w;  // the element count OpenCV's loops see
     r.acc_vec_end = n3 - n3 % 16;
@@ -367,18 +295,18 @@ hipError_t launch_rgb(hipStream_t st, const FusedArgs& a, uint8_t* cblur, uint64
     const int CS = a.nty * 64;
     const int nf = (a.t_end - a.t_begin) * a.S;
     const int lds = rgb::blur_lds_bytes(a.ksize >> 1);
-    r.kstamp = ks1;
+    r.g.kstamp = ks1;
     (void)hipFuncSetAttribute((const void*)rgb::k_rgb_blur, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(rgb::k_rgb_blur, dim3((unsigned)nf * (unsigned)a.ntiles), dim3(rgb::BT), lds, st, r, cblur, CS);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    r.kstamp = ks2;
+    r.g.kstamp = ks2;
     const int njobs = a.S * a.w * a.nty;
-    const dim3 grid((njobs + rgb::ST / 64 - 1) / (rgb::ST / 64));
+    const dim3 grid((njobs + ST / 64 - 1) / (ST / 64));
     const bool tailk = r.acc_vec_end < n3, simd = n3 >= 16;
-    if (tailk && simd) hipLaunchKernelGGL((rgb::k_rgb_scan<true, true>), grid, dim3(rgb::ST), 0, st, r, cblur, CS);
-    else if (simd) hipLaunchKernelGGL((rgb::k_rgb_scan<false, true>), grid, dim3(rgb::ST), 0, st, r, cblur, CS);
-    else if (tailk) hipLaunchKernelGGL((rgb::k_rgb_scan<true, false>), grid, dim3(rgb::ST), 0, st, r, cblur, CS);
-    else hipLaunchKernelGGL((rgb::k_rgb_scan<false, false>), grid, dim3(rgb::ST), 0, st, r, cblur, CS);
+    if (tailk && simd) hipLaunchKernelGGL((rgb::k_rgb_scan<true, true>), grid, dim3(ST), 0, st, r, cblur, CS);
+    else if (simd) hipLaunchKernelGGL((rgb::k_rgb_scan<false, true>), grid, dim3(ST), 0, st, r, cblur, CS);
+    else if (tailk) hipLaunchKernelGGL((rgb::k_rgb_scan<true, false>), grid, dim3(ST), 0, st, r, cblur, CS);
+    else hipLaunchKernelGGL((rgb::k_rgb_scan<false, false>), grid, dim3(ST), 0, st, r, cblur, CS);
     return hipGetLastError();
 }
 

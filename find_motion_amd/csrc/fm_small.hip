@@ -13,41 +13,20 @@
 //                 (masked pixels blur to 0, fm.py:619-636) -> blur bytes [F][x][y] (column-major, column
 //                 stride CS = nty * 64), and it clears the frame's tile flags and the bit words of the
 //                 columns past the image;
-//   k_small_scan  one wave per (stream, image column, 64-row tile row), lane = row: the frames in order
-//                 with the f64 background in a register -- diff (convertScaleAbs + absdiff), threshold,
-//                 accumulateWeighted -- and __ballot of `d > t` is the tile's column word of threshold
-//                 bits directly (word c = column c, bit r = row r: the contour pass's layout).  A block of
-//                 64 frames' words is held one frame per lane and stored at once, with the frames' flags
-//                 ORed atomically into word 0 of each tile-frame's 8 (the reader ORs them) where a word has
-//                 bits: no per-frame store, branch or address arithmetic (1,450 -> 1,002 instructions in the
-//                 kernel, the scan 120 -> 65 us per 256 frames beside the resize, round 5).
+//   k_small_scan  fm_scan.h's scan_frames (one wave per stream, image column and 64-row tile row, lane = row,
+//                 the frames in order) around the f64 background in a register: diff (convertScaleAbs +
+//                 absdiff), threshold, accumulateWeighted; `d > t` is the lane's threshold bit.
 //
 // Same arithmetic as k_pix5 / the oracle: gray (1868 B + 9617 G + 4899 R + 8192) >> 14, blur
 // (sum_y c_y sum_x c_x g + 2^15) >> 16 with OpenCV's 8-bit taps, q = sat_u8(rne(|(float)bg|)),
 // d = |blur - q| > t, bg = fma(bg, 1 - a, blur * a) (scalar tail past acc_vec_end: blur * a + bg * (1 - a)),
 // the stream's first frame bg := blur before the diff.
-#include "fm_internal.h"
+#include "fm_scan.h"
 
 namespace fm {
 namespace sm {
 
 constexpr int BT = 256;  // k_small_blur threads
-constexpr int ST = 256;  // k_small_scan threads (4 waves, each its own job)
-constexpr int PFD = 8;  // k_small_scan: frames per group of blur-byte loads
-constexpr int NG = 2;   // groups in flight (4 and 8: scans 5 % shorter, mode D unchanged, round 5)
-
-__device__ __forceinline__ int refl(int p, int len) {  // BORDER_REFLECT_101 (any distance)
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        p = (p < 0) ? -p : 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
-__device__ __forceinline__ uint32_t gray_px(uint32_t b, uint32_t g, uint32_t r) {
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
 
 // H's row stride in dwords: odd, so that the vertical pass's 64 lanes (consecutive rows of one column)
 // read 64 distinct banks (at w = 100 the unpadded stride put them on 16 banks: 4-way conflicts)
@@ -73,14 +52,7 @@ __global__ __launch_bounds__(BT) void k_small_blur(FusedArgs a, uint8_t* __restr
     kstamp_begin_grid(a.kstamp);
     for (int i = tid; i < w + 2 * R; i += BT) xi[i] = refl(i - R, w);
     for (int i = tid; i < h + 2 * R; i += BT) yi[i] = refl(i - R, h);
-    // this frame's tile flags (k_small_scan ORs into word 0 of each) and the bit words of the columns
-    // past the image in the last tile column (no scan wave writes them)
-    for (int i = tid; i < a.ntiles * 8; i += BT) a.tflag[f * a.ntiles * 8 + i] = 0u;
-    const int xpad = a.ntx * 64 - w;
-    for (int i = tid; i < a.nty * xpad; i += BT) {
-        const int ty = i / xpad, c = w - (a.ntx - 1) * 64 + (i - ty * xpad);
-        a.bits[(f * a.ntiles + ty * a.ntx + a.ntx - 1) * 64 + c] = 0ull;
-    }
+    clear_tile_frame(geom_of(a), f, tid, BT);  // the scan's precondition
     // gray: pixel quads as three dwords where the frame allows (4-B aligned), single pixels otherwise
     const uint8_t* src = a.src + f * (size_t)n * 3;
     const int nq = ((reinterpret_cast<uintptr_t>(src) & 3) == 0) ? n / 4 : 0;
@@ -119,97 +91,49 @@ __global__ __launch_bounds__(BT) void k_small_blur(FusedArgs a, uint8_t* __restr
     kstamp_end_wg(a.kstamp);
 }
 
+// the running average of one pixel: scan_frames' model of k_small_scan (after k_small_blur or k_wide_blur)
+template <bool TAILK>
+struct Average {
+    struct Group { uint32_t b[PFD]; };
+    const FusedArgs& a;
+    const uint8_t* sblur;  // blur bytes [F][x][CS]
+    int CS;
+    double alpha, beta, bg;
+    int thr, t0;
+    bool tail, init0;
+    size_t px, fstride;
+    const uint8_t* base;
+    __device__ __forceinline__ void open(const Lane& l) {
+        alpha = a.alpha, beta = a.beta, thr = a.thresh, t0 = l.t0;
+        const long long li = (long long)l.y * a.w + l.x;
+        tail = TAILK && li >= a.acc_vec_end;  // accumulateWeighted's scalar tail
+        init0 = a.init != nullptr && a.init[l.s] != 0;
+        px = (size_t)l.s * a.h * a.w + li;
+        bg = (l.valid && !init0) ? a.bg_in[px] : 0.0;
+        // blur bytes of frame t of this pixel: sblur[((t * S + s) * w + x) * CS + y]
+        fstride = (size_t)a.S * a.w * CS;
+        base = sblur + (size_t)l.s * a.w * CS + (size_t)l.x * CS + l.y;
+    }
+    __device__ __forceinline__ void load(Group& r, int k, int tc) const { r.b[k] = base[(size_t)tc * fstride]; }
+    __device__ __forceinline__ void step(const Group& r, int k, int t, bool& fg) {
+        const uint32_t blur = r.b[k];
+        const double bv = (init0 && t == t0) ? (double)blur : bg;
+        const int q = min(max(__float2int_rn(fabsf(__double2float_rn(bv))), 0), 255);
+        fg = abs((int)blur - q) > thr;
+        // blur * alpha on the VALU (the pixel kernels' LDS table holds the same correctly rounded
+        // product): a 256-entry f64 table read by 64 unrelated bytes averaged 1.95 bank-conflict
+        // cycles per LDS cycle here, and the product is off the background's dependency chain
+        const double bl = __dmul_rn((double)blur, alpha);
+        bg = tail ? __dadd_rn(bl, __dmul_rn(bv, beta)) : __fma_rn(bv, beta, bl);
+    }
+    __device__ __forceinline__ void close(const Lane& l) const {
+        if (l.valid) a.bg_out[px] = bg;
+    }
+};
+
 template <bool TAILK>
 __global__ __launch_bounds__(ST) void k_small_scan(FusedArgs a, const uint8_t* __restrict__ sblur, int CS) {
-    const int tid = threadIdx.x, ln = tid & 63;
-    const int h = a.h, w = a.w, S = a.S;
-    const double alpha = a.alpha;
-    kstamp_begin_grid(a.kstamp);
-    const int job = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (ST / 64) + (tid >> 6)));
-    const int njobs = S * w * a.nty;
-    if (job < njobs) {
-        const int s = job / (w * a.nty);
-        const int rem = job - s * w * a.nty;
-        const int ty = rem / w, x = rem - ty * w;
-        const int y = ty * 64 + ln;
-        const bool valid = y < h;
-        const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
-        const int tile = ty * a.ntx + x / 64, c = x & 63;
-        const size_t plane = (size_t)h * w;
-        const long long li = (long long)y * w + x;
-        const bool tail = TAILK && li >= a.acc_vec_end;  // accumulateWeighted's scalar tail
-        const double beta = a.beta;
-        const int thr = a.thresh;
-        const int t0 = a.t_begin, t1 = a.t_end;
-        const bool init0 = a.init != nullptr && a.init[s] != 0;
-        double bg = (valid && !init0) ? a.bg_in[(size_t)s * plane + li] : 0.0;
-        const int yl = valid ? y : 0;
-        // blur bytes of frame t of this pixel: sblur[((t * S + s) * w + x) * CS + y]
-        const uint8_t* col = sblur + (size_t)x * CS + yl;
-        const size_t fstride = (size_t)S * w * CS;
-        const uint8_t* base = col + (size_t)s * w * CS;
-        const uint32_t flagL = c < 2 ? (FLAG_L) : 0u, flagR = c >= 62 ? FLAG_R : 0u;
-        // blur bytes of NG groups of PFD frames in flight (HBM latency is ~2 us beside the resize; one group
-        // of 8 frames ahead left the scan waiting for every group)
-        uint32_t rg[NG][PFD];
-        // each frame's column word into lane (t - t0) % 64 of (wlo, whi); every 64 frames the
-        // block's words are stored (one store, a frame per lane) and their flag words ORed into the tile-frame
-        // flags (one atomic, lanes with bits): no per-frame store, branch or address arithmetic
-        uint32_t wlo = 0, whi = 0;
-        uint64_t* const bits0 = a.bits + ((size_t)s * a.ntiles + tile) * 64 + c;  // frame 0's word of (s, tile, c)
-        uint32_t* const flag0 = a.tflag + ((size_t)s * a.ntiles + tile) * 8;
-        const size_t bstride = (size_t)S * a.ntiles * 64, fstride8 = (size_t)S * a.ntiles * 8;
-        auto flush = [&](int tb, int n) __attribute__((always_inline)) {  // frames tb .. tb + n - 1 in lanes 0 .. n - 1
-            if (ln < n) {
-                const size_t ft = (size_t)(tb + ln);
-                const uint64_t word = ((uint64_t)whi << 32) | wlo;
-                bits0[ft * bstride] = word;
-                if (word) {
-                    const uint32_t fl = FLAG_ANY | flagL | flagR |
-                                        ((word & 3ull) ? (FLAG_T | (c < 2 ? FLAG_TL : 0u) | (c >= 62 ? FLAG_TR : 0u)) : 0u) |
-                                        ((word >> 62) ? (FLAG_B | (c < 2 ? FLAG_BL : 0u) | (c >= 62 ? FLAG_BR : 0u)) : 0u);
-                    atomicOr(&flag0[ft * fstride8], fl);
-                }
-            }
-        };
-        auto load_group = [&](uint32_t (&r)[PFD], int tg) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < PFD; k++) r[k] = base[(size_t)min(tg + k, t1 - 1) * fstride];  // clamped: unconditional
-        };
-        auto run_group = [&](const uint32_t (&r)[PFD], int tg) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < PFD; k++) {
-                const int t = tg + k;
-                if (t >= t1) break;  // wave-uniform
-                const uint32_t blur = r[k];
-                const double bv = (init0 && t == t0) ? (double)blur : bg;
-                const int q = min(max(__float2int_rn(fabsf(__double2float_rn(bv))), 0), 255);
-                const int d = abs((int)blur - q);
-                const uint64_t word = __builtin_amdgcn_ballot_w64(d > thr) & vmask;
-                // blur * alpha on the VALU (the pixel kernels' LDS table holds the same correctly rounded
-                // product): a 256-entry f64 table read by 64 unrelated bytes averaged 1.95 bank-conflict
-                // cycles per LDS cycle here, and the product is off the background's dependency chain
-                const double bl = __dmul_rn((double)blur, alpha);
-                bg = tail ? __dadd_rn(bl, __dmul_rn(bv, beta)) : __fma_rn(bv, beta, bl);
-                const int kb = (t - t0) & 63;
-                const bool mine = ln == kb;
-                wlo = mine ? (uint32_t)word : wlo;
-                whi = mine ? (uint32_t)(word >> 32) : whi;
-                if (kb == 63) flush(t - 63, 64);
-            }
-        };
-        static_for<NG>([&](auto g) { load_group(rg[decltype(g)::value], t0 + decltype(g)::value * PFD); });
-        for (int tg = t0; tg < t1; tg += NG * PFD) {
-            static_for<NG>([&](auto g) {
-                constexpr int G = decltype(g)::value;
-                run_group(rg[G], tg + G * PFD);
-                load_group(rg[G], tg + (NG + G) * PFD);
-            });
-        }
-        if (const int nrem = (t1 - t0) & 63) flush(t1 - nrem, nrem);  // the last, partial block
-        if (valid) a.bg_out[(size_t)s * plane + li] = bg;
-    }
-    kstamp_end_wg(a.kstamp);
+    scan_frames(geom_of(a), Average<TAILK>{a, sblur, CS});
 }
 
 }  // namespace sm
@@ -218,12 +142,10 @@ bool small_supported(int h, int w, int ksize) {
     return (long long)h * w <= 16384 && ksize <= kMaxK && sm::blur_lds_bytes(h, w, ksize >> 1) <= 64 * 1024;
 }
 
-size_t small_scratch_bytes(int h, int w, int nty, size_t frames) { return frames * (size_t)w * nty * 64; }
-
 // frames [a.t_begin, a.t_end) of the batch: blur of every frame in parallel, then the scan; a.init may mark
 // first frames (bg := blur at t_begin).  ks1 / ks2: launch stamps of the two kernels (or nullptr)
 hipError_t launch_small(hipStream_t st, const FusedArgs& a, uint8_t* sblur, uint64_t* ks1, uint64_t* ks2) {
-    (void)launch_small_blur(st, a, sblur, ks1);
+    if (hipError_t e = launch_small_blur(st, a, sblur, ks1); e != hipSuccess) return e;
     return launch_small_scan(st, a, sblur, ks2);
 }
 
@@ -245,9 +167,9 @@ hipError_t launch_small_scan(hipStream_t st, const FusedArgs& a, const uint8_t* 
     FusedArgs b = a;
     b.kstamp = ks;
     const int njobs = a.S * a.w * a.nty;
-    const dim3 grid((njobs + sm::ST / 64 - 1) / (sm::ST / 64));
-    if (a.acc_vec_end < (long long)a.h * a.w) hipLaunchKernelGGL(sm::k_small_scan<true>, grid, dim3(sm::ST), 0, st, b, sblur, CS);
-    else hipLaunchKernelGGL(sm::k_small_scan<false>, grid, dim3(sm::ST), 0, st, b, sblur, CS);
+    const dim3 grid((njobs + ST / 64 - 1) / (ST / 64));
+    if (a.acc_vec_end < (long long)a.h * a.w) hipLaunchKernelGGL(sm::k_small_scan<true>, grid, dim3(ST), 0, st, b, sblur, CS);
+    else hipLaunchKernelGGL(sm::k_small_scan<false>, grid, dim3(ST), 0, st, b, sblur, CS);
     return hipGetLastError();
 }
 

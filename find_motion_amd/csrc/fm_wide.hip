@@ -32,7 +32,7 @@
 //
 // Rows below the band's first output row and above its last come from refl() like the columns, so a radius
 // larger than the image (k = 255 on 72 rows) walks back and forth over the same rows: correct at any distance.
-#include "fm_internal.h"
+#include "fm_scan.h"
 
 namespace fm {
 namespace wd {
@@ -41,19 +41,6 @@ constexpr int kLds = 160 * 1024;  // LDS of a gfx950 workgroup
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 constexpr int PD = 8;             // rows of a block: loaded together, a block ahead of the rows being summed
 constexpr int GP = 4;             // gray pixels a thread loads per row, at most (make_geo checks)
-
-__device__ __forceinline__ int refl(int p, int len) {  // BORDER_REFLECT_101 (any distance): sm::refl's loop
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        p = (p < 0) ? -p : 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
-__device__ __forceinline__ uint32_t gray_px(uint32_t b, uint32_t g, uint32_t r) {
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
 
 // launch geometry of one (ksize, taps): NT threads own a strip of SW = 2 NT columns
 struct Geo {
@@ -113,16 +100,7 @@ __global__ __launch_bounds__(NT) void k_wide_blur(FusedArgs a, uint8_t* __restri
     uint8_t* growA = lds + (size_t)RP * SW * 4;         // [PD][2][gwp]: gray of columns x0 - rp .. x0 + SW + rp - 1
     uint8_t* growB = growA + L.gwp;                     // (reflected) of PD rows, and the same two bytes ahead
     kstamp_begin_grid(a.kstamp);
-    if (blockIdx.y == 0 && blockIdx.z == 0) {
-        // this frame's tile flags (k_small_scan ORs into word 0 of each) and the bit words of the columns
-        // past the image in the last tile column (no scan wave writes them)
-        for (int i = tid; i < a.ntiles * 8; i += NT) a.tflag[f * a.ntiles * 8 + i] = 0u;
-        const int xpad = a.ntx * 64 - w;
-        for (int i = tid; i < a.nty * xpad; i += NT) {
-            const int ty = i / xpad, c = w - (a.ntx - 1) * 64 + (i - ty * xpad);
-            a.bits[(f * a.ntiles + ty * a.ntx + a.ntx - 1) * 64 + c] = 0ull;
-        }
-    }
+    if (blockIdx.y == 0 && blockIdx.z == 0) clear_tile_frame(geom_of(a), f, tid, NT);  // the scan's precondition
     // the source byte offsets of this thread's gray pixels within a row (the same in every row)
     int sxo[GP];
 #pragma unroll
@@ -288,8 +266,6 @@ bool wide_supported(int ksize, const int32_t* coef) {
 }
 
 int wide_lds_bytes(int ksize, const int32_t* coef) { return wd::make_geo(ksize, coef).lds; }
-
-size_t wide_scratch_bytes(int w, int nty, size_t frames) { return frames * (size_t)w * nty * 64; }
 
 // frames [a.t_begin, a.t_end) of the batch: blur of every frame in parallel, then the scan; a.init may mark
 // first frames (bg := blur at t_begin).  ks1 / ks2: launch stamps of the two kernels (or nullptr)

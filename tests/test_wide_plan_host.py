@@ -90,6 +90,46 @@ def test_selection_table(W, H, box, k, flags, path, work, tiles, depth):
     assert got == {"work_shape": work, "tiles": tiles, "max_inflight": out.max_inflight, "pixel_path": path}
 
 
+# The paths that flags select, and what they refuse: source W x H, box, k, max_batch, flags -> return code,
+# pixel_path, max_inflight.  A colour slot's blur scratch is 3 B per pixel-frame with the rows padded to whole
+# tiles: 1080p at 42 frames is 3 * 1920 * 1088 * 42 = 263,208,960 B, under the 256 MiB above which a context
+# keeps 4 slots, and at 43 frames 269,475,840 B, over it.
+COLOUR, MOG2, PLANES = _native.FM_FLAG_COLOUR_MOTION, _native.FM_FLAG_MOG2, FM_FLAG_KEEP_PLANES
+FLAG_TABLE = [
+    (1920, 1080, 1920, 5, 42, COLOUR, FM_OK, "rgb", 10),
+    (1920, 1080, 1920, 5, 43, COLOUR, FM_OK, "rgb", 4),
+    (1920, 1080, 100, 5, 4, COLOUR, FM_OK, "rgb", 10),             # (the small path's shape: colour takes it over)
+    (1920, 1080, 1920, 49, 4, COLOUR, FM_OK, "rgb", 10),
+    (1920, 1080, 1920, 51, 4, COLOUR, FM_ENOTSUP, "", 0),           # colour takes ksize up to 49
+    (1920, 1080, 100, 5, 4, MOG2, FM_OK, "mog2", 4),               # k_small_blur in front
+    (1920, 1080, 1920, 5, 4, MOG2, FM_OK, "mog2", 4),              # k_wide_blur in front
+    (328, 136, 328, 5, 4, MOG2, FM_OK, "mog2", 4),
+    (1920, 1080, 1920, 97, 4, MOG2, FM_OK, "mog2", 4),
+    (1920, 1080, 1920, 5, 4, MOG2 | COLOUR, FM_ENOTSUP, "", 0),
+    (1920, 1080, 1920, 5, 4, MOG2 | PLANES, FM_ENOTSUP, "", 0),
+    (1920, 1080, 1920, 5, 4, COLOUR | PLANES, FM_ENOTSUP, "", 0),
+    (1920, 1080, 100, 5, 4, 0, FM_OK, "small", 10),
+    (1920, 1080, 100, 5, 4, PLANES, FM_OK, "pix", 10),             # kept planes: k_pix writes them
+    (1920, 1080, 1920, 5, 4, 0, FM_OK, "pix", 10),
+    (640, 480, 640, 11, 4, 0, FM_OK, "fused", 10),
+    (1920, 1080, 1920, 97, 4, 0, FM_OK, "wide", 4),
+    (1920, 1080, 1920, 97, 4, PLANES, FM_OK, "pixel", 1),
+]
+
+
+@pytest.mark.parametrize("W,H,box,k,batch,flags,code,path,depth", FLAG_TABLE)
+def test_flag_selection_table(W, H, box, k, batch, flags, code, path, depth):
+    L = _native.load()
+    out = _native.FMPlan()
+    p = params(src_w=W, src_h=H, box_size=box, ksize=k, max_batch=batch, flags=flags)
+    assert L.fm_plan(C.byref(p), C.byref(out)) == code, L.fm_last_error(None)
+    assert (out.pixel_path.decode(), out.max_inflight) == (path, depth)
+    if code != FM_OK:
+        assert L.fm_last_error(None)
+        h = C.c_void_p()
+        assert L.fm_create(C.byref(h), C.byref(p)) == code and not h.value
+
+
 def test_every_odd_ksize_above_49_fits():
     """The wide kernels' LDS need fits for every odd k from 51 to 255 (the ring of row sums shrinks the strip
     from 512 to 256 columns where it has to)."""
